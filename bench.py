@@ -12,8 +12,12 @@ pipeline (next clip's inversion beside this clip's edit; run_group_anyv2v) is me
 Everything inside the step runs in the hand-written HIP kernels (anyv2v_amd/libanyv2v_hip.so); weights are random
 (seeded) with the exact I2VGen-XL architecture, inputs synthetic and HBM-resident; VAE/CLIP pre/post are outside.
 
-Launch:  python bench.py --gpus 1 --steps K --warmup W
+Launch:  python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
          python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...
+A plain run sets up, warms up, times the K step pairs and prints the result line.  Everything else the bench can report (the other
+schedule, `flops`, `step_traffic`, the roofline launches, one whole clip, multi-edit, configs 2 and 5, the CPU baseline) runs only
+with --full; the --no-* options then leave single parts of it out.  --dump-outputs DIR writes the latents of the last timed step pair
+(inversion_latent.npy: the inverted latent, = the trajectory entry it wrote; edit_latent.npy: the edited latent) as float32.
 """
 from __future__ import annotations
 
@@ -574,11 +578,25 @@ def finish_distributed(dist, dt, latents, world, device):
     return float(tmax.item()), out
 
 
+def dump_outputs(out_dir, arrays):
+    """``arrays`` (name -> device tensor) as ``out_dir/<name>.npy`` in float32: what the timed path hands its caller, for comparing
+    two builds output for output (the inputs are seeded, so equal arguments give equal inputs)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().float().cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also measure everything beyond the headline (other schedule, flops, roofline launches, "
+                         "whole clip, multi-edit, configs 2 and 5, CPU baseline); the --no-* options below then skip single parts")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the latents of the last timed step pair to DIR/<name>.npy (float32)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-clip", action="store_true", help="skip the end-to-end timing of one whole clip")
@@ -587,7 +605,7 @@ def main():
     ap.add_argument("--pipelined", action="store_true",
                     help="time the job-level two-clip software pipeline (inversion step of the NEXT clip beside the edit step of the "
                          "current clip, two streams, as run_group_anyv2v runs a multi-clip job) instead of the single-clip serial order; "
-                         "by default the pipelined rate is measured after the timed region and reported as config.pipelined_ms_per_step")
+                         "with --full the pipelined rate is measured after the timed region and reported as config.pipelined_ms_per_step")
     ap.add_argument("--serial", action="store_true", help="(default since round 5; kept for old command lines)")
     ap.add_argument("--overlap", dest="pipelined", action="store_true", help=argparse.SUPPRESS)   # rounds 3-4 name of --pipelined
     ap.add_argument("--no-configs", action="store_true", help="skip the `configs` object (BASELINE configs 2 and 5)")
@@ -595,6 +613,8 @@ def main():
                     help="skip the measurement of the other schedule behind the timed region (profiling runs: the trace then holds the timed pairs only)")
     args = ap.parse_args()
     args.overlap = args.pipelined and not args.serial   # (the timed schedule; also the top-level "schedule" key of the line)
+    if not args.full:   # a plain run measures the headline only
+        args.no_cpu_baseline = args.no_roofline = args.no_clip = args.no_multi_edit = args.no_configs = args.no_job_schedule = True
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -730,6 +750,11 @@ def main():
         dt, _gathered = finish_distributed(dist, dt, s_pnp[2:3].contiguous(), world, device)
     finite = bool(torch.isfinite(s_pnp.float()).all() and torch.isfinite(s_inv.float()).all())
     rccl_ranks = len(_gathered) if dist is not None else None
+    if args.dump_outputs and rank == 0:   # before anything below reuses the buffers
+        outs = {"inversion_latent": s_inv, "edit_latent": s_pnp[e_pnp.lat_slot:e_pnp.lat_slot + 1]}
+        if dist is not None:
+            outs["edit_latent_all_ranks"] = torch.cat(_gathered)
+        dump_outputs(args.dump_outputs, outs)
     serial_ms = pipelined_ms = None
     bit_equal = None
     if world == 1 and not args.no_job_schedule:
@@ -800,22 +825,23 @@ def main():
         if rccl_ranks is not None:   # how many ranks' edited latents the one all_gather of the job delivered to rank 0
             line["rccl_ranks"] = rccl_ranks
             line["rccl_gathered_finite"] = bool(all(torch.isfinite(g.float()).all() for g in _gathered))
-        # what is executed vs what the metric prices: one eager forward of each step kind with every GEMM / attention launch recorded
-        ex1 = executed_flops(e_inv)
-        ex3 = executed_flops(e_pnp, hooks_t=ts_pnp[0])
-        ex_t = (ex1["gemm"] + ex1["attention"] + ex3["gemm"] + ex3["attention"]) / 1e12
-        alg_t = ALGORITHMIC_TFLOP["B1"] + ALGORITHMIC_TFLOP["B3"]
-        line["flops"] = {"algorithmic_tflop_per_step": alg_t, "executed_tflop_per_step": round(ex_t, 3),
-                         "executed_tflop_B1": round((ex1["gemm"] + ex1["attention"]) / 1e12, 3),
-                         "executed_tflop_B3": round((ex3["gemm"] + ex3["attention"]) / 1e12, 3),
-                         "executed_attention_tflop_B3": round(ex3["attention"] / 1e12, 3),
-                         "gemm_attention_launches_B1_B3": [ex1["launches"], ex3["launches"]],
-                         "step_frac_algorithmic": round(alg_t / (ms * 1e-3) / PEAK_MFMA_F16_TFLOPS, 4),
-                         "step_frac_executed": round(ex_t / (ms * 1e-3) / PEAK_MFMA_F16_TFLOPS, 4),
-                         "what": "MFMA work per bench step (1 inversion step B=1 + 1 edit step B=3) / ms_per_step / 2500 TFLOP/s; algorithmic = the "
-                                 "reference architecture's count (SURVEY 8(d)), executed = summed over the launches of one eager forward of each kind "
-                                 "(exact savings: hoisted conditioning, V-only projections, shared softmax, shared stem, source-only conv path, source branch stopped behind the last hook site)"}
-        traffic = sorted(__import__("glob").glob(os.path.join(ROOT, "profiles", "r*_step_traffic.json")))
+        if args.full:
+            # what is executed vs what the metric prices: one eager forward of each step kind with every GEMM / attention launch recorded
+            ex1 = executed_flops(e_inv)
+            ex3 = executed_flops(e_pnp, hooks_t=ts_pnp[0])
+            ex_t = (ex1["gemm"] + ex1["attention"] + ex3["gemm"] + ex3["attention"]) / 1e12
+            alg_t = ALGORITHMIC_TFLOP["B1"] + ALGORITHMIC_TFLOP["B3"]
+            line["flops"] = {"algorithmic_tflop_per_step": alg_t, "executed_tflop_per_step": round(ex_t, 3),
+                             "executed_tflop_B1": round((ex1["gemm"] + ex1["attention"]) / 1e12, 3),
+                             "executed_tflop_B3": round((ex3["gemm"] + ex3["attention"]) / 1e12, 3),
+                             "executed_attention_tflop_B3": round(ex3["attention"] / 1e12, 3),
+                             "gemm_attention_launches_B1_B3": [ex1["launches"], ex3["launches"]],
+                             "step_frac_algorithmic": round(alg_t / (ms * 1e-3) / PEAK_MFMA_F16_TFLOPS, 4),
+                             "step_frac_executed": round(ex_t / (ms * 1e-3) / PEAK_MFMA_F16_TFLOPS, 4),
+                             "what": "MFMA work per bench step (1 inversion step B=1 + 1 edit step B=3) / ms_per_step / 2500 TFLOP/s; algorithmic = the "
+                                     "reference architecture's count (SURVEY 8(d)), executed = summed over the launches of one eager forward of each kind "
+                                     "(exact savings: hoisted conditioning, V-only projections, shared softmax, shared stem, source-only conv path, source branch stopped behind the last hook site)"}
+        traffic = sorted(__import__("glob").glob(os.path.join(ROOT, "profiles", "r*_step_traffic.json"))) if args.full else []
         if traffic:
             try:
                 line["step_traffic"] = dict(json.load(open(traffic[-1])), source=os.path.relpath(traffic[-1], ROOT))
