@@ -10,7 +10,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libanyv2v_hip.so")
-ABI_VERSION = 103   # ANYV2V_ABI_VERSION of include/anyv2v_hip.h the structures below mirror
+ABI_VERSION = 104   # ANYV2V_ABI_VERSION of include/anyv2v_hip.h the structures below mirror
 
 
 class HipExtensionMissing(RuntimeError):
@@ -66,6 +66,9 @@ SYMBOLS = {
     "anyv2v_groupnorm_partial_floats": (C.c_int64, [_I32, _I32, _I32, _I32]),
     "anyv2v_groupnorm_partial_f16": (C.c_int, [_VP, _VP, _I32, _I32, _VP, _I32, _I32, _I32, _VP]),
     "anyv2v_groupnorm_apply_f16": (C.c_int, [_VP, _VP, _I32, _I32, _VP, _VP, _VP, _VP, _I32, _I32, _I32, _F32, _I32, _I32, _VP]),
+    "anyv2v_groupnorm_pivot_f16": (C.c_int, [_VP, _VP, _I32, _I32, _VP, _I32, _I32, _I32, _I32, _VP]),
+    "anyv2v_groupnorm_partial_pivot_f16": (C.c_int, [_VP, _VP, _I32, _I32, _VP, _VP, _I32, _I32, _I32, _VP]),
+    "anyv2v_groupnorm_apply_pivot_f16": (C.c_int, [_VP, _VP, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _I32, _I32, _I32, _F32, _I32, _I32, _VP]),
     "anyv2v_layernorm_f16": (C.c_int, [_VP, _VP, _VP, _VP, _I32, _I32, _F32, _VP]),
     "anyv2v_attention_f16": (C.c_int, [C.POINTER(AttnDesc), _VP]),
     "anyv2v_attention_small_f16": (C.c_int, [C.POINTER(AttnDesc), _I32, _VP]),

@@ -9,14 +9,37 @@
 // (mean, rstd) in a fixed order (a separate 7-us finalize launch per GroupNorm used to cost 2 % of the step; a
 // last-arriver finalize would need device-scope fences, which flush the per-XCD L2 on gfx950).
 // Algorithmic traffic: 2 reads + 1 write of X.
+// The sums are shifted: s = sum(x - K), q = sum((x - K)^2) about one pivot K per (stat group, channel group), the fp16 value at
+// the group's first row and first channel; mean = K + s/n, var = q/n - (s/n)^2.  Unshifted one-pass sums cancel catastrophically
+// once a group's mean is large against its spread (|mean| = 1000 sigma or near-constant groups: errors of 1e-1); about a member of
+// the group, s/n is of the order of the spread.  The shift keeps the sums additive over chunks (and over ranks, for the pivoted
+// sharded entry points, which agree on one pivot first).  The ABI-101 sharded pair (anyv2v_groupnorm_partial_f16 / _apply_f16)
+// keeps its one-all-reduce contract and therefore the rank-independent pivot K = 0: unshifted sums, as before.
 #include "common.h"
 
 #define GN_MAX_CHUNKS 256
 
+// pivot of (stat group sg, channel group g): the caller's agreed value, x[first row of sg][first channel of g] (pivot == nullptr,
+// from_data) or 0 (pivot == nullptr, !from_data: the unshifted sums of the one-all-reduce sharded pair)
+__device__ __forceinline__ float gn_pivot(const half_t* X0, const half_t* X1, int C0, int C1, const float* pivot, int from_data,
+                                          int sg, int rows_per_group, int G, int g) {
+    if (pivot) return pivot[(size_t)sg * G + g];
+    if (!from_data) return 0.f;
+    const int c = g * ((C0 + C1) / G);
+    return c < C0 ? (float)X0[(size_t)sg * rows_per_group * C0 + c] : (float)X1[(size_t)sg * rows_per_group * C1 + (c - C0)];
+}
+
+// sharded entry points: pivot[sg][g] = this rank's pivot / shards (all-reduced by the caller into the agreed pivot)
+__global__ void gn_pivot_kernel(const half_t* __restrict__ X0, const half_t* __restrict__ X1, int C0, int C1,
+                                float* __restrict__ pivot, int rows_per_group, int G, float shards) {
+    const int sg = blockIdx.x, g = threadIdx.x;
+    if (g < G) pivot[(size_t)sg * G + g] = gn_pivot(X0, X1, C0, C1, nullptr, 1, sg, rows_per_group, G, g) / shards;
+}
+
 // (1) per-(stat group, row chunk) partial sums, reduced deterministically through LDS (no atomics)
 __global__ void gn_partial_kernel(const half_t* __restrict__ X0, const half_t* __restrict__ X1, int C0, int C1,
-                                  float* __restrict__ partial, int rows_per_group, int G, int rows_chunk, int rpb,
-                                  int nchunks) {
+                                  const float* __restrict__ pivot, int from_data, float* __restrict__ partial,
+                                  int rows_per_group, int G, int rows_chunk, int rpb, int nchunks) {
     extern __shared__ __attribute__((aligned(16))) float red[];  // [rpb][C][2]
     const int C = C0 + C1, V = C >> 3, cpg = C / G;
     const int sg = blockIdx.x, chunk = blockIdx.y;
@@ -31,7 +54,19 @@ __global__ void gn_partial_kernel(const half_t* __restrict__ X0, const half_t* _
         const half_t* base = from0 ? X0 : X1;
         const int ld = from0 ? C0 : C1;
         const int cc = from0 ? c0 : c0 - C0;
-        float s[8], q[8];
+        // pivots straight from memory, no barrier (in flight with the first row loads); with >= 8 channels per group the
+        // thread's 8 channels span at most two groups: two loads
+        float s[8], q[8], k[8];
+        if (cpg >= 8) {
+            const int g0 = c0 / cpg, split = (g0 + 1) * cpg - c0;
+            const float k0 = gn_pivot(X0, X1, C0, C1, pivot, from_data, sg, rows_per_group, G, g0);
+            const float k1 = split < 8 ? gn_pivot(X0, X1, C0, C1, pivot, from_data, sg, rows_per_group, G, g0 + 1) : k0;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) k[e] = e < split ? k0 : k1;
+        } else {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) k[e] = gn_pivot(X0, X1, C0, C1, pivot, from_data, sg, rows_per_group, G, (c0 + e) / cpg);
+        }
 #pragma unroll
         for (int e = 0; e < 8; ++e) s[e] = q[e] = 0.f;
         const half_t* ptr = base + ((size_t)sg * rows_per_group) * ld + cc;
@@ -44,7 +79,7 @@ __global__ void gn_partial_kernel(const half_t* __restrict__ X0, const half_t* _
             for (int u = 0; u < 4; ++u)
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
-                    const float f = (float)x[u][e];
+                    const float f = (float)x[u][e] - k[e];
                     s[e] += f;
                     q[e] += f * f;
                 }
@@ -53,7 +88,7 @@ __global__ void gn_partial_kernel(const half_t* __restrict__ X0, const half_t* _
             const h8 x = *(const h8*)(ptr + (size_t)r * ld);
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
-                const float f = (float)x[e];
+                const float f = (float)x[e] - k[e];
                 s[e] += f;
                 q[e] += f * f;
             }
@@ -90,9 +125,10 @@ __device__ __forceinline__ float gn_silu(float x) {  // x * sigmoid(x) on raw v_
 template <int U>
 __global__ __launch_bounds__(1024) void gn_apply_kernel(const half_t* __restrict__ X0, const half_t* __restrict__ X1, int C0,
                                                         int C1, half_t* __restrict__ Y, const half_t* __restrict__ gamma,
-                                                        const half_t* __restrict__ beta, const float* __restrict__ partial,
-                                                        int nchunks, float inv_cnt, float eps, int rows_per_group, int G,
-                                                        int silu, int rpb, int rows_per_block) {
+                                                        const half_t* __restrict__ beta, const float* __restrict__ pivot,
+                                                        int from_data, const float* __restrict__ partial, int nchunks, float inv_cnt,
+                                                        float eps, int rows_per_group, int G, int silu, int rpb,
+                                                        int rows_per_block) {
     __shared__ float rs[256], rq[256], smean[64], srstd[64];
     const int C = C0 + C1, V = C >> 3, cpg = C / G;
     const int sg = blockIdx.y, tid = threadIdx.x;
@@ -100,6 +136,8 @@ __global__ __launch_bounds__(1024) void gn_apply_kernel(const half_t* __restrict
         const int nt = blockDim.x < 256 ? blockDim.x : 256;
         const int parts = nt / G;  // G <= 64 <= blockDim.x
         const int g = tid % G, part = tid / G;
+        // this group's pivot, loaded before the chunk sums so that its latency overlaps theirs
+        const float kpiv = tid < G ? gn_pivot(X0, X1, C0, C1, pivot, from_data, sg, rows_per_group, G, tid) : 0.f;
         if (tid < 256) {
             float as = 0.f, aq = 0.f;
             if (part < parts)
@@ -118,9 +156,9 @@ __global__ __launch_bounds__(1024) void gn_apply_kernel(const half_t* __restrict
                 s += rs[p2 * G + tid];
                 q += rq[p2 * G + tid];
             }
-            const float mean = s * inv_cnt;
-            const float var = fmaxf(q * inv_cnt - mean * mean, 0.f);
-            smean[tid] = mean;
+            const float m = s * inv_cnt;  // mean - pivot
+            const float var = fmaxf(q * inv_cnt - m * m, 0.f);
+            smean[tid] = kpiv + m;
             srstd[tid] = rsqrtf(var + eps);
         }
         __syncthreads();
@@ -182,8 +220,8 @@ struct GnPlan {
 };
 
 template <int U>
-__global__ void gn_apply_kernel(const half_t*, const half_t*, int, int, half_t*, const half_t*, const half_t*, const float*, int, float,
-                                float, int, int, int, int, int);
+__global__ void gn_apply_kernel(const half_t*, const half_t*, int, int, half_t*, const half_t*, const half_t*, const float*,
+                                int, const float*, int, float, float, int, int, int, int, int);
 
 // resident gn_apply blocks on the whole device for a block size (occupancy query, cached per size)
 static int gn_apply_slots(int threads) {
@@ -243,22 +281,23 @@ static int gn_plan(GnPlan& pl, const void* X0, const void* X1, int32_t C0, int32
     return ANYV2V_OK;
 }
 
-static int gn_partial(const GnPlan& pl, const void* X0, const void* X1, int32_t C0, int32_t C1, float* stats,
-                      int32_t rows_per_group, int32_t G, hipStream_t s) {
+// pivot: [nsg][G] agreed pivots, or nullptr: each stat group's own first element per channel group (from_data) or 0
+static int gn_partial(const GnPlan& pl, const void* X0, const void* X1, int32_t C0, int32_t C1, const float* pivot,
+                      int from_data, float* stats, int32_t rows_per_group, int32_t G, hipStream_t s) {
     // stats: [nsg][nchunks][G][2]
     hipLaunchKernelGGL(gn_partial_kernel, dim3(pl.nsg, pl.nchunks), dim3(pl.threads), pl.lds, s, (const half_t*)X0,
-                       (const half_t*)X1, C0, C1, stats, rows_per_group, G, pl.rows_chunk, pl.rpb, pl.nchunks);
+                       (const half_t*)X1, C0, C1, pivot, from_data, stats, rows_per_group, G, pl.rows_chunk, pl.rpb, pl.nchunks);
     return av_launch_status("groupnorm<partial>");
 }
 
 static int gn_apply(const GnPlan& pl, const void* X0, const void* X1, int32_t C0, int32_t C1, void* Y, const void* gamma,
-                    const void* beta, const float* stats, int32_t rows_per_group, int32_t G, float eps, int32_t silu,
-                    int32_t shards, hipStream_t s) {
+                    const void* beta, const float* pivot, int from_data, const float* stats, int32_t rows_per_group,
+                    int32_t G, float eps, int32_t silu, int32_t shards, hipStream_t s) {
     AV_CHECK(av_aligned16(Y) && av_aligned16(gamma) && av_aligned16(beta), "groupnorm: pointers must be 16-byte aligned");
     const float inv_cnt = 1.0f / ((float)rows_per_group * (float)((C0 + C1) / G) * (float)shards);
     hipLaunchKernelGGL(gn_apply_kernel<4>, dim3((unsigned)pl.bps, (unsigned)pl.nsg), dim3(pl.threads), 0, s,
                        (const half_t*)X0, (const half_t*)X1, C0, C1, (half_t*)Y, (const half_t*)gamma, (const half_t*)beta,
-                       stats, pl.nchunks, inv_cnt, eps, rows_per_group, G, silu, pl.rpb, pl.rows_block);
+                       pivot, from_data, stats, pl.nchunks, inv_cnt, eps, rows_per_group, G, silu, pl.rpb, pl.rows_block);
     return av_launch_status("groupnorm");
 }
 
@@ -268,13 +307,27 @@ extern "C" int anyv2v_groupnorm_f16(const void* X0, const void* X1, int32_t C0, 
     AV_CHECK(X0 && Y && gamma && beta && stats, "groupnorm: null pointer");
     GnPlan pl;
     if (int rc = gn_plan(pl, X0, X1, C0, C1, M, rows_per_group, G)) return rc;
-    if (int rc = gn_partial(pl, X0, X1, C0, C1, stats, rows_per_group, G, (hipStream_t)stream)) return rc;
-    return gn_apply(pl, X0, X1, C0, C1, Y, gamma, beta, stats, rows_per_group, G, eps, silu, 1, (hipStream_t)stream);
+    if (int rc = gn_partial(pl, X0, X1, C0, C1, nullptr, 1, stats, rows_per_group, G, (hipStream_t)stream)) return rc;
+    return gn_apply(pl, X0, X1, C0, C1, Y, gamma, beta, nullptr, 1, stats, rows_per_group, G, eps, silu, 1, (hipStream_t)stream);
 }
 
 // Sharded GroupNorm (a clip whose frames or pixels are split over `shards` ranks, every rank holding the same local
-// shape): phase 1 writes this rank's partial sums; the caller adds the first anyv2v_groupnorm_partial_floats() floats
-// of `stats` over the ranks (all-reduce SUM, RCCL); phase 2 normalises with shards x the local element count.
+// shape).  Pivoted form: phase 0 writes this rank's pivot / shards, which the caller adds over the ranks (all-reduce SUM)
+// into the agreed pivot; phase 1 writes this rank's partial sums about it; the caller adds the first
+// anyv2v_groupnorm_partial_floats() floats of `stats` over the ranks (all-reduce SUM, RCCL); phase 2 normalises with the
+// agreed pivot and shards x the local element count.  The ABI-101 pair (partial_f16 / apply_f16, one all-reduce) is the
+// same with pivot 0.
+extern "C" int anyv2v_groupnorm_pivot_f16(const void* X0, const void* X1, int32_t C0, int32_t C1, float* pivot, int32_t M,
+                                          int32_t rows_per_group, int32_t G, int32_t shards, void* stream) {
+    AV_CHECK(X0 && pivot, "groupnorm_pivot: null pointer");
+    AV_CHECK(shards >= 1, "groupnorm_pivot: shards must be >= 1");
+    GnPlan pl;
+    if (int rc = gn_plan(pl, X0, X1, C0, C1, M, rows_per_group, G)) return rc;
+    hipLaunchKernelGGL(gn_pivot_kernel, dim3(pl.nsg), dim3(64), 0, (hipStream_t)stream, (const half_t*)X0, (const half_t*)X1, C0,
+                       C1, pivot, rows_per_group, G, (float)shards);
+    return av_launch_status("groupnorm<pivot>");
+}
+
 extern "C" int64_t anyv2v_groupnorm_partial_floats(int32_t M, int32_t rows_per_group, int32_t G, int32_t C) {
     GnPlan pl;
     static const int dummy __attribute__((aligned(16))) = 0;
@@ -282,12 +335,31 @@ extern "C" int64_t anyv2v_groupnorm_partial_floats(int32_t M, int32_t rows_per_g
     return (int64_t)pl.nsg * pl.nchunks * G * 2;
 }
 
+extern "C" int anyv2v_groupnorm_partial_pivot_f16(const void* X0, const void* X1, int32_t C0, int32_t C1, const float* pivot,
+                                                  float* stats, int32_t M, int32_t rows_per_group, int32_t G, void* stream) {
+    AV_CHECK(X0 && pivot && stats, "groupnorm_partial: null pointer");
+    GnPlan pl;
+    if (int rc = gn_plan(pl, X0, X1, C0, C1, M, rows_per_group, G)) return rc;
+    return gn_partial(pl, X0, X1, C0, C1, pivot, 0, stats, rows_per_group, G, (hipStream_t)stream);
+}
+
+extern "C" int anyv2v_groupnorm_apply_pivot_f16(const void* X0, const void* X1, int32_t C0, int32_t C1, void* Y,
+                                                const void* gamma, const void* beta, const float* pivot, const float* stats,
+                                                int32_t M, int32_t rows_per_group, int32_t G, float eps, int32_t silu,
+                                                int32_t shards, void* stream) {
+    AV_CHECK(X0 && Y && gamma && beta && pivot && stats, "groupnorm_apply: null pointer");
+    AV_CHECK(shards >= 1, "groupnorm_apply: shards must be >= 1");
+    GnPlan pl;
+    if (int rc = gn_plan(pl, X0, X1, C0, C1, M, rows_per_group, G)) return rc;
+    return gn_apply(pl, X0, X1, C0, C1, Y, gamma, beta, pivot, 0, stats, rows_per_group, G, eps, silu, shards, (hipStream_t)stream);
+}
+
 extern "C" int anyv2v_groupnorm_partial_f16(const void* X0, const void* X1, int32_t C0, int32_t C1, float* stats, int32_t M,
                                             int32_t rows_per_group, int32_t G, void* stream) {
     AV_CHECK(X0 && stats, "groupnorm_partial: null pointer");
     GnPlan pl;
     if (int rc = gn_plan(pl, X0, X1, C0, C1, M, rows_per_group, G)) return rc;
-    return gn_partial(pl, X0, X1, C0, C1, stats, rows_per_group, G, (hipStream_t)stream);
+    return gn_partial(pl, X0, X1, C0, C1, nullptr, 0, stats, rows_per_group, G, (hipStream_t)stream);
 }
 
 extern "C" int anyv2v_groupnorm_apply_f16(const void* X0, const void* X1, int32_t C0, int32_t C1, void* Y,
@@ -298,7 +370,7 @@ extern "C" int anyv2v_groupnorm_apply_f16(const void* X0, const void* X1, int32_
     AV_CHECK(shards >= 1, "groupnorm_apply: shards must be >= 1");
     GnPlan pl;
     if (int rc = gn_plan(pl, X0, X1, C0, C1, M, rows_per_group, G)) return rc;
-    return gn_apply(pl, X0, X1, C0, C1, Y, gamma, beta, stats, rows_per_group, G, eps, silu, shards, (hipStream_t)stream);
+    return gn_apply(pl, X0, X1, C0, C1, Y, gamma, beta, nullptr, 0, stats, rows_per_group, G, eps, silu, shards, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------

@@ -203,7 +203,8 @@ def gn_scratch_floats(M: int, rows_per_group: int, groups: int = 32) -> int:
 def groupnorm(x0: torch.Tensor, gamma, beta, stats: torch.Tensor, rows_per_group: int, *, x1=None, groups: int = 32,
               eps: float = 1e-5, silu: bool = False, out=None, shard=None):
     """``shard`` = (shards, all_reduce_sum): this rank holds 1/shards of every statistics group (frame- / pixel-parallel
-    clip, ``anyv2v_amd.parallel.FrameParallel``); the partial sums are added over the ranks between the two kernels."""
+    clip, ``anyv2v_amd.parallel.FrameParallel``).  ``all_reduce_sum`` is called twice, in the same order on every rank: on the
+    ranks' pivots / shards (the agreed pivot of the shifted sums), then on the partial sums about that pivot."""
     if shard is not None:
         return _groupnorm_sharded(x0, gamma, beta, stats, rows_per_group, x1, groups, eps, silu, out, shard)
     lib = _lib.load()
@@ -240,13 +241,18 @@ def _groupnorm_sharded(x0, gamma, beta, stats, rows_per_group, x1, groups, eps, 
         out = torch.empty((M, C0 + C1), dtype=torch.float16, device=x0.device)
     assert out.is_contiguous()
     n = int(lib.anyv2v_groupnorm_partial_floats(M, rows_per_group, groups, C0 + C1))
-    assert n > 0 and stats.dtype == torch.float32 and stats.numel() >= n, "GroupNorm scratch too small"
-    _lib.check(lib.anyv2v_groupnorm_partial_f16(_p(x0), _p(x1), C0, C1, _p(stats), M, rows_per_group, groups, _stream()),
-               "anyv2v_groupnorm_partial_f16")
+    npiv = (M // rows_per_group) * groups
+    assert n > 0 and stats.dtype == torch.float32 and stats.numel() >= n + npiv, "GroupNorm scratch too small"
+    piv = stats[n:n + npiv]   # behind the partial sums (a gn_scratch_floats() buffer always has room for both)
+    _lib.check(lib.anyv2v_groupnorm_pivot_f16(_p(x0), _p(x1), C0, C1, _p(piv), M, rows_per_group, groups, int(shards), _stream()),
+               "anyv2v_groupnorm_pivot_f16")
+    all_reduce_sum(piv)
+    _lib.check(lib.anyv2v_groupnorm_partial_pivot_f16(_p(x0), _p(x1), C0, C1, _p(piv), _p(stats), M, rows_per_group, groups,
+                                                      _stream()), "anyv2v_groupnorm_partial_pivot_f16")
     all_reduce_sum(stats[:n])
-    _lib.check(lib.anyv2v_groupnorm_apply_f16(_p(x0), _p(x1), C0, C1, _p(out), _p(gamma), _p(beta), _p(stats), M,
-                                              rows_per_group, groups, eps, int(silu), int(shards), _stream()),
-               "anyv2v_groupnorm_apply_f16")
+    _lib.check(lib.anyv2v_groupnorm_apply_pivot_f16(_p(x0), _p(x1), C0, C1, _p(out), _p(gamma), _p(beta), _p(piv), _p(stats), M,
+                                                    rows_per_group, groups, eps, int(silu), int(shards), _stream()),
+               "anyv2v_groupnorm_apply_pivot_f16")
     return out
 
 

@@ -109,8 +109,9 @@ class FrameParallel:
     and need no communication.  Around each temporal layer (``TemporalConvLayer``, ``TransformerTemporalModel``) the
     tokens are re-sharded frames -> pixels with ONE all-to-all (rank r then holds pixels ``[r HW/world, (r+1) HW/world)``
     of ALL frames: the temporal conv and the temporal attention are independent per pixel), and back with another; the
-    5-D GroupNorm statistics inside those layers are the only reduction (``ops.groupnorm(shard=...)``: one all-reduce
-    of a few KiB of fp32 partial sums).  The v-prediction (8 channels) is all-gathered at the end of the forward, so the
+    5-D GroupNorm statistics inside those layers are the only reduction (``ops.groupnorm(shard=...)``: two all-reduces,
+    one of the ranks' pivots -- one float per statistics and channel group -- then one of a few KiB of fp32 partial sums
+    about the agreed pivot).  The v-prediction (8 channels) is all-gathered at the end of the forward, so the
     scheduler step, the PnP bookkeeping and the pipeline loops run unchanged -- and identically -- on every rank.
 
     Per 64x64 layer at B=3, F=128 the re-shard moves 7/8 of a 1 GiB activation: 7 x 16 MiB per rank and direction,

@@ -133,11 +133,23 @@ int anyv2v_groupnorm_f16(const void* X0, const void* X1, int32_t C0, int32_t C1,
                          int32_t silu, void* stream);
 
 /* Sharded 5-D GroupNorm, for a clip whose frames / pixels are split over `shards` ranks (the 128-frame mode,
- * gradio_demo.py:129-131; every rank holds the same local shape).  Phase 1 writes this rank's partial sums into
- * `stats`; the caller adds the first anyv2v_groupnorm_partial_floats(M, rows_per_group, G, C0 + C1) floats over the
- * ranks (one all-reduce SUM: RCCL on the node); phase 2 normalises with shards x the local element count.
- * partial + apply(shards = 1) on one rank is exactly anyv2v_groupnorm_f16. */
+ * gradio_demo.py:129-131; every rank holds the same local shape).  The statistics are sums about one pivot per
+ * (statistics group, channel group), which all ranks must share: phase 0 writes this rank's pivot / shards into `pivot`
+ * ((M / rows_per_group) x G floats) and the caller adds them over the ranks (all-reduce SUM); phase 1 writes this rank's
+ * partial sums about the agreed pivot into `stats`; the caller adds the first
+ * anyv2v_groupnorm_partial_floats(M, rows_per_group, G, C0 + C1) floats over the ranks (all-reduce SUM: RCCL on the
+ * node); phase 2 normalises with the agreed pivot and shards x the local element count.
+ * pivot(shards = 1) + partial_pivot + apply_pivot(shards = 1) on one rank is exactly anyv2v_groupnorm_f16. */
 int64_t anyv2v_groupnorm_partial_floats(int32_t M, int32_t rows_per_group, int32_t G, int32_t C);
+int anyv2v_groupnorm_pivot_f16(const void* X0, const void* X1, int32_t C0, int32_t C1, float* pivot, int32_t M,
+                               int32_t rows_per_group, int32_t G, int32_t shards, void* stream);
+int anyv2v_groupnorm_partial_pivot_f16(const void* X0, const void* X1, int32_t C0, int32_t C1, const float* pivot,
+                                       float* stats, int32_t M, int32_t rows_per_group, int32_t G, void* stream);
+int anyv2v_groupnorm_apply_pivot_f16(const void* X0, const void* X1, int32_t C0, int32_t C1, void* Y, const void* gamma,
+                                     const void* beta, const float* pivot, const float* stats, int32_t M,
+                                     int32_t rows_per_group, int32_t G, float eps, int32_t silu, int32_t shards, void* stream);
+/* The pre-104 sharded pair, kept for existing callers: ONE all-reduce (of the partial sums), i.e. the pivot fixed at 0 --
+ * unshifted sums, which lose precision once a group's |mean| is large against its spread (hundreds of sigma). */
 int anyv2v_groupnorm_partial_f16(const void* X0, const void* X1, int32_t C0, int32_t C1, float* stats, int32_t M,
                                  int32_t rows_per_group, int32_t G, void* stream);
 int anyv2v_groupnorm_apply_f16(const void* X0, const void* X1, int32_t C0, int32_t C1, void* Y, const void* gamma,
@@ -281,8 +293,10 @@ const char* anyv2v_last_error(void);
 /* ABI version = major * 100 + minor.  Descriptors carry no size field: a caller MUST be compiled against the header of the
  * library it loads (check anyv2v_version() >= the ANYV2V_ABI_VERSION it was built with) and MUST zero-initialise every
  * descriptor (new fields are appended with 0 = "off").  101: AnyV2VGemmDesc grew ln_c1 / ln_eps / reserved0 (round 3), flags
- * bits 13-16 select the persistent kernel's tile order (round 4).  102: anyv2v_ff_geglu_f16.  103: anyv2v_guided_step_f16, anyv2v_guided_step_noise_f16. */
-#define ANYV2V_ABI_VERSION 103
+ * bits 13-16 select the persistent kernel's tile order (round 4).  102: anyv2v_ff_geglu_f16.  103: anyv2v_guided_step_f16, anyv2v_guided_step_noise_f16.
+ * 104: GroupNorm sums about a pivot; pivoted sharded entry points anyv2v_groupnorm_pivot_f16 / _partial_pivot_f16 /
+ * _apply_pivot_f16 (the earlier pair is unchanged). */
+#define ANYV2V_ABI_VERSION 104
 int anyv2v_version(void);
 /* MFMA / LDS layout self-test used by the gpu test-suite (returns 0 when the layouts the kernels assume hold) */
 int anyv2v_selftest(void* scratch, int64_t scratch_bytes, void* stream);

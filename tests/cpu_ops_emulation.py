@@ -89,17 +89,23 @@ def groupnorm(x0, gamma, beta, stats, rows_per_group, *, x1=None, groups=32, eps
     x = x0.float() if x1 is None else torch.cat([x0.float(), x1.float()], 1)
     M, C = x.shape
     n = M // rows_per_group
-    if shard is not None:  # two-phase contract of anyv2v_groupnorm_partial_f16 / _apply_f16: sums -> all-reduce -> apply
-        shards, all_reduce_sum = shard
+    if shard is not None:  # contract of anyv2v_groupnorm_pivot_f16 / _partial_f16 / _apply_f16: pivot -> all-reduce -> sums about it
+        shards, all_reduce_sum = shard  # -> all-reduce -> apply
         xg = x.view(n, rows_per_group, groups, C // groups)
-        sums = torch.stack([xg.sum((1, 3)), (xg * xg).sum((1, 3))], -1).contiguous()  # [n, G, 2]
+        nsum = n * groups * 2
+        piv = stats[nsum: nsum + n * groups]
+        piv.copy_((xg[:, 0, :, 0] / shards).reshape(-1))  # first row, first channel of each group
+        all_reduce_sum(piv)
+        d = xg - piv.view(n, 1, groups, 1)
+        sums = torch.stack([d.sum((1, 3)), (d * d).sum((1, 3))], -1).contiguous()  # [n, G, 2]
         buf = stats[: sums.numel()]
         buf.copy_(sums.reshape(-1))
         all_reduce_sum(buf)
         sums = buf.view(n, groups, 2)
         cnt = rows_per_group * (C // groups) * shards
-        mean = sums[..., 0] / cnt
-        rstd = torch.rsqrt((sums[..., 1] / cnt - mean * mean).clamp_min(0) + eps)
+        m = sums[..., 0] / cnt
+        mean = piv.view(n, groups) + m
+        rstd = torch.rsqrt((sums[..., 1] / cnt - m * m).clamp_min(0) + eps)
         y = ((xg - mean[:, None, :, None]) * rstd[:, None, :, None]).reshape(n, rows_per_group, C)
         y = (y * gamma.float() + beta.float()).permute(0, 2, 1)
     else:

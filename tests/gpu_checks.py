@@ -413,7 +413,7 @@ def check_gemm_ws_ln():
     out = []
     eps = 1e-5
     for (M, K, N, act, shift) in [(40000, 320, 960, 0, 0.0), (33001, 320, 320, 0, 6.0), (36000, 320, 2560, ops.ACT_GEGLU, 0.0),
-                                  (34000, 512, 4096, ops.ACT_GEGLU, 3.0)]:
+                                  (34000, 512, 4096, ops.ACT_GEGLU, 3.0), (33001, 320, 320, 0, 12.0), (33001, 320, 960, 0, 24.0)]:
         x = (rnd(M, K).float() * (1.0 + 0.5 * torch.rand(M, 1, device=DEV)) + shift * torch.randn(M, 1, device=DEV)).half()
         gamma, beta = (1.0 + 0.3 * rnd(K).float()).half(), (0.2 * rnd(K, seed=7).float()).half()
         geglu = act == ops.ACT_GEGLU
@@ -629,11 +629,7 @@ def check_norms():
     halves = [xs[:, :, i * hw // 2:(i + 1) * hw // 2].reshape(-1, c0).contiguous() for i in range(2)]
     ga0, be0 = ga[:c0].contiguous(), be[:c0].contiguous()
     full = ops.groupnorm(x0, ga0, be0, stats, Fr * hw, groups=32, eps=1e-5, silu=True).view(B, Fr, hw, c0)
-    st = [torch.zeros_like(stats) for _ in range(2)]
-    ops.groupnorm(halves[1], ga0, be0, st[1], Fr * hw // 2, groups=32, silu=True, shard=(1, lambda t: t))  # rank 1's sums
-    other = st[1].clone()
-    got = ops.groupnorm(halves[0], ga0, be0, st[0], Fr * hw // 2, groups=32, eps=1e-5, silu=True,
-                        shard=(2, lambda t: t.add_(other[:t.numel()])))
+    got = gn_sharded_emulated(halves, None, ga0, be0, Fr * hw // 2, eps=1e-5, silu=True)[0]   # rank 0 of 2
     out.append(_res("groupnorm sharded over 2 pixel halves vs unsharded", got,
                     full[:, :, :hw // 2].reshape(-1, c0).float(), 2e-3))
     for (m, c) in [(1000, 320), (77, 1280), (333, 512), (50, 4), (64, 64)]:
@@ -641,6 +637,362 @@ def check_norms():
         ga, be = rnd(c) + 1.0, rnd(c)
         y = ops.layernorm(x, ga, be, 1e-5)
         out.append(_res(f"layernorm m{m} c{c}", y, F.layer_norm(x.float(), (c,), ga.float(), be.float(), 1e-5), KTOL))
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ norms at production shapes
+# References here are float64 two-pass statistics on the GPU, on the same fp16 inputs (not F.group_norm in fp32: MIOpen's fp32
+# paths have misbehaved at large sizes, profiles/r04_eager_size_probe_fp32.txt).
+def _gn_ref64(x0, x1, ga, be, rpg, groups, eps, silu):
+    x = x0.double() if x1 is None else torch.cat([x0.double(), x1.double()], 1)
+    M, C = x.shape
+    xg = x.view(M // rpg, rpg, groups, C // groups)
+    mean = xg.mean((1, 3), keepdim=True)
+    var = (xg - mean).square_().mean((1, 3), keepdim=True)
+    y = (xg - mean).mul_(torch.rsqrt(var + eps)).view(M, C).mul_(ga.double()).add_(be.double())
+    return y * torch.sigmoid(y) if silu else y
+
+
+def _ln_ref64(x, ga, be, eps):
+    xd = x.double()
+    mean = xd.mean(1, keepdim=True)
+    var = (xd - mean).square_().mean(1, keepdim=True)
+    return (xd - mean).mul_(torch.rsqrt(var + eps)).mul_(ga.double()).add_(be.double())
+
+
+def _gn_run(x0, x1, ga, be, rpg, groups, eps, silu, shard=None):
+    M = x0.shape[0]
+    stats = torch.zeros(ops.gn_scratch_floats(M, rpg, groups), dtype=torch.float32, device=DEV)
+    return ops.groupnorm(x0, ga, be, stats, rpg, x1=x1, groups=groups, eps=eps, silu=silu, shard=shard)
+
+
+def _gn_row(name, x0, x1, ga, be, rpg, groups, eps, silu, tol=KTOL):
+    y = _gn_run(x0, x1, ga, be, rpg, groups, eps, silu)
+    return _res(name, y, _gn_ref64(x0, x1, ga, be, rpg, groups, eps, silu), tol)
+
+
+def _affine(C, seed):
+    return (rnd(C, seed=seed) * 0.3 + 1.0).half(), (rnd(C, seed=seed + 1) * 0.2).half()
+
+
+def _offset_data(nsg, rpg, C, groups, offset, seed, sigma=1.0):
+    """Per (statistics group, channel group): a random sign x ``offset`` sigma on top of N(0, sigma^2) noise."""
+    g = torch.Generator(device="cpu").manual_seed(seed)
+    sign = (torch.randint(0, 2, (nsg, 1, groups, 1), generator=g) * 2 - 1).float().to(DEV)
+    x = torch.randn(nsg, rpg, groups, C // groups, generator=g).to(DEV) * sigma + sign * (offset * sigma)
+    return x.view(nsg * rpg, C).half()
+
+
+_NORM_CALLS = None
+
+
+def recorded_norm_calls():
+    """Every distinct ``ops.groupnorm`` signature (C0, C1, rows_per_group, G, eps, silu) and ``ops.layernorm`` signature (C, eps)
+    that one forward pass of the product's models issues: the full-width I2VGen-XL UNet at config 1 (8 f x 32^2 latents, B = 1),
+    the mini and full-architecture VAE (encode + decode), the ConsistI2V and SEINE UNets at the toy widths of their fixtures.
+    Weights are random (the call signatures depend on shapes only)."""
+    global _NORM_CALLS
+    if _NORM_CALLS is not None:
+        return _NORM_CALLS
+    import consisti2v_spec as c2spec
+    import seine_spec as snspec
+    from anyv2v_amd import consisti2v as c2
+    from anyv2v_amd import seine as sn
+    from anyv2v_amd.unet import I2VGenXLUNet, I2VGenXLUNetConfig
+    from anyv2v_amd.vae import AutoencoderKL, VAEConfig
+    from oracle import vae_oracle as vo
+    from oracle.unet_oracle import UNetConfig
+    gn, ln = {}, {}
+    real_gn, real_ln = ops.groupnorm, ops.layernorm
+
+    def rec_gn(x0, gamma, beta, stats, rows_per_group, *, x1=None, groups=32, eps=1e-5, silu=False, out=None, shard=None):
+        key = (x0.shape[1], 0 if x1 is None else x1.shape[1], rows_per_group, groups, float(eps), bool(silu))
+        gn.setdefault(key, 0)
+        gn[key] += 1
+        return real_gn(x0, gamma, beta, stats, rows_per_group, x1=x1, groups=groups, eps=eps, silu=silu, out=out, shard=shard)
+
+    def rec_ln(x, gamma, beta, eps=1e-5, out=None):
+        key = (x.shape[1], float(eps))
+        ln.setdefault(key, 0)
+        ln[key] += 1
+        return real_ln(x, gamma, beta, eps, out)
+
+    ops.groupnorm, ops.layernorm = rec_gn, rec_ln
+    try:
+        with torch.no_grad():
+            # full-width I2VGen-XL UNet: seeded weights drawn on the GPU with random_state_dict's init rule
+            with torch.device("meta"):
+                unet = I2VGenXLUNet(I2VGenXLUNetConfig())
+            gen = torch.Generator(device=DEV).manual_seed(1234)
+            sd = {}
+            for k, v in unet.state_dict().items():
+                t = torch.randn(tuple(v.shape), generator=gen, device=DEV)
+                fan_in = max(1, v[0].numel()) if v.dim() > 1 else 1
+                sd[k] = (t * 0.02 if k.endswith(".bias") else (1.0 + 0.05 * t) if v.dim() == 1 else t / math.sqrt(fan_in)).half()
+            unet = unet.to_empty(device=DEV)
+            unet.load_state_dict(sd, strict=True)
+            del sd
+            inp = config1_inputs(UNetConfig.i2vgen_xl(), 1, 8, 32)
+            unet(inp["sample"].half().to(DEV), 981, **_cond_kw({k: (v.half() if v.is_floating_point() else v) for k, v in inp.items()},
+                                                               DEV, torch.float16))
+            _sync()
+            del unet
+            for ncfg, ocfg, xs, zs in [(VAEConfig.mini(), vo.VAEConfig.mini(), (1, 3, 32, 48), (1, 4, 8, 12)),
+                                       (VAEConfig(), vo.VAEConfig(), (1, 3, 64, 64), (1, 4, 8, 8))]:
+                vae = AutoencoderKL(ncfg)
+                vae.load_state_dict(vo.random_state_dict(ocfg, 11))
+                vae.to(DEV)
+                g = torch.Generator().manual_seed(5)
+                vae.encode_moments(torch.randn(*xs, generator=g).clamp(-1, 1).to(DEV))
+                vae.decode(torch.randn(*zs, generator=g).to(DEV))
+                del vae
+            cu = c2spec.fill_weights(c2.VideoLDMUNet3DConditionModel(**c2spec.UNET_CFG)).to(DEV)
+            sample, first, ehs = c2spec.unet_inputs()
+            cu(sample.to(DEV).half(), c2spec.UNET_T, encoder_hidden_states=ehs.to(DEV).half(), first_frame_latents=first.to(DEV).half(),
+               frame_stride=c2spec.UNET_STRIDE)
+            del cu
+            su = snspec.fill_weights(sn.UNet3DConditionModel(**snspec.UNET_CFG), snspec.WEIGHT_SEED).to(DEV)
+            sample, ehs = snspec.unet_inputs()
+            su(sample.to(DEV).half(), 981, encoder_hidden_states=ehs.to(DEV).half())
+            del su
+            _sync()
+    finally:
+        ops.groupnorm, ops.layernorm = real_gn, real_ln
+        torch.cuda.empty_cache()
+    _NORM_CALLS = (gn, ln)
+    return _NORM_CALLS
+
+
+def check_norms_at_recorded_shapes():
+    """Every distinct GroupNorm / LayerNorm signature the product issues (``recorded_norm_calls``), run at its real rows_per_group
+    with two statistics groups, plus the bench's 5-D size (16 frames x 64^2 latents) and the VAE's 512^2 groups, against float64
+    two-pass statistics.  Inputs carry a per-channel offset of up to ~2 sigma."""
+    gn, ln = recorded_norm_calls()
+    out = []
+    n_two = sum(1 for k in gn if k[1] > 0)
+    # a silent change in the hooks must not be able to empty (or thin) the list
+    # (73 / 20 / 8 when this was written; the full-width up-block skip concat 1280 + 640 at 8 x 8 latents must be among them)
+    out.append(dict(name=f"recorded {len(gn)} GroupNorm signatures ({n_two} two-source), {len(ln)} LayerNorm signatures",
+                    err=0.0, tol=0.0, ok=bool(len(gn) >= 70 and n_two >= 20 and len(ln) >= 8 and (1280, 640, 64, 32, 1e-5, True) in gn)))
+    cases = sorted(gn)
+    cases += [(320, 0, 16 * 4096, 32, 1e-5, True), (320, 0, 16 * 4096, 32, 1e-5, False), (1280, 0, 16 * 64, 32, 1e-5, True),
+              (128, 0, 512 * 512, 32, 1e-6, True), (256, 0, 512 * 512, 32, 1e-6, True)]
+    for i, (C0, C1, rpg, G, eps, silu) in enumerate(cases):
+        nsg = 2 if rpg * (C0 + C1) <= (1 << 24) else 1
+        C = C0 + C1
+        g = torch.Generator(device="cpu").manual_seed(100 + i)
+        off = (torch.randn(C, generator=g) * 2.0).to(DEV)
+        x = (rnd(nsg * rpg, C, seed=200 + i).float() + off).half()
+        x0, x1 = (x[:, :C0].contiguous(), x[:, C0:].contiguous()) if C1 else (x, None)
+        ga, be = _affine(C, 300 + i)
+        out.append(_gn_row(f"groupnorm C{C0}+{C1} rows/group {rpg} x {nsg} G{G} eps {eps:g} silu={silu}", x0, x1, ga, be, rpg, G, eps,
+                           silu))
+        del x, x0, x1
+    for i, (C, eps) in enumerate(sorted(ln)):
+        M = 2 * 4096 + 3
+        x = (rnd(M, C, seed=400 + i).float() + (torch.randn(M, 1, device=DEV) * 2.0)).half()
+        ga, be = _affine(C, 500 + i)
+        out.append(_res(f"layernorm recorded C{C} eps {eps:g} M{M}", ops.layernorm(x, ga, be, eps), _ln_ref64(x, ga, be, eps), KTOL))
+    return out
+
+
+def check_groupnorm_ill_conditioned():
+    """Groups whose mean is large against their spread (offset / sigma up to 1000), near-constant groups (level 3-40, noise
+    0.1-1 % of the level), exactly constant and all-zero groups (-> fp16(beta), up to SiLU), and a two-source call whose X0 and
+    X1 carry different offsets inside the group that straddles the boundary (1280 + 640: 60 channels per group).  4-D (4096
+    rows per group) and 5-D (16 x 1024 rows per group) shapes, with and without SiLU, eps 1e-5 and 1e-6."""
+    out = []
+    shapes = [("4-D", 2, 4096, 320), ("5-D", 1, 16 * 1024, 320)]
+    for tag, nsg, rpg, C in shapes:
+        ga, be = _affine(C, 11)
+        for offset in (0, 10, 100, 1000):
+            x = _offset_data(nsg, rpg, C, 32, offset, seed=offset + rpg)
+            for silu in (False, True):
+                for eps in (1e-5, 1e-6):
+                    out.append(_gn_row(f"groupnorm {tag} rows/group {rpg} offset {offset} sigma silu={silu} eps {eps:g}", x, None,
+                                       ga, be, rpg, 32, eps, silu))
+        g = torch.Generator(device="cpu").manual_seed(rpg)
+        for level in (3.0, 40.0):
+            for frac in (1e-3, 1e-2):
+                lv = (level * (torch.rand(nsg, 1, 32, 1, generator=g) + 0.5)).to(DEV)
+                x = (lv * (1.0 + frac * torch.randn(nsg, rpg, 32, C // 32, generator=g).to(DEV))).view(nsg * rpg, C).half()
+                for silu in (False, True):
+                    for eps in (1e-5, 1e-6):
+                        out.append(_gn_row(f"groupnorm {tag} near-constant level {level:g} noise {frac:g} silu={silu} eps {eps:g}", x,
+                                           None, ga, be, rpg, 32, eps, silu))
+        # group 0 exactly constant, group 1 all zero, the rest random with an offset
+        x = _offset_data(nsg, rpg, C, 32, 5, seed=7).view(nsg, rpg, C)
+        cpg = C // 32
+        x[:, :, :cpg] = 7.0
+        x[:, :, cpg:2 * cpg] = 0.0
+        x = x.view(nsg * rpg, C)
+        for silu in (False, True):
+            for eps in (1e-5, 1e-6):
+                y = _gn_run(x, None, ga, be, rpg, 32, eps, silu).view(nsg, rpg, C)[:, :, :2 * cpg].float()
+                want = be[:2 * cpg].double()
+                want = (want * torch.sigmoid(want) if silu else want).half().float().expand_as(y)
+                err = float((y - want).abs().max())
+                tol = 0.0 if not silu else 1e-3   # SiLU on the raw v_exp / v_rcp: within 1 fp16 ulp of |beta| <= 1
+                out.append(dict(name=f"groupnorm {tag} constant and all-zero groups -> fp16(beta) silu={silu} eps {eps:g}", err=err,
+                                tol=tol, ok=bool(torch.isfinite(y).all() and err <= tol)))
+    # two sources, different offsets in X0 (+100 sigma) and X1 (-300 sigma)
+    B, rpg, c0, c1 = 2, 4096, 1280, 640
+    x0 = (rnd(B * rpg, c0, seed=21).float() + 100.0).half()
+    x1 = (rnd(B * rpg, c1, seed=22).float() - 300.0).half()
+    ga, be = _affine(c0 + c1, 23)
+    for silu in (False, True):
+        out.append(_gn_row(f"groupnorm two-source 1280 + 640, offsets +100 / -300 sigma, silu={silu}", x0, x1, ga, be, rpg, 32, 1e-5,
+                           silu))
+    return out
+
+
+def _guarded(M, C, pad=64, bits=0x7E5A):
+    """A [M, C] fp16 output carved as a row slice of a larger buffer filled with a NaN bit pattern no kernel computes."""
+    buf = torch.full((M + 2 * pad, C), bits, dtype=torch.int16, device=DEV)
+    return buf, buf.view(torch.float16)[pad:pad + M], (pad, bits)
+
+
+def _guard_intact(buf, M, guard):
+    pad, bits = guard
+    return bool((buf[:pad] == bits).all() and (buf[pad + M:] == bits).all())
+
+
+def check_groupnorm_plan_edges():
+    """The launch plan's edges: rows_per_group that is not a multiple of the rows per block or of the chunk size, the 256-chunk
+    cap, the same tensor under ``batch_hint(3, 2)`` (another chunk count: within KTOL and bit-reproducible call to call),
+    C = 2560 (one row per block), C = 8; every call writes nothing outside its output rows nor past the stats scratch."""
+    out = []
+    TAIL = 4096
+    cases = [  # (C0, C1, rows_per_group, nsg, G, silu)
+        (320, 0, 4099, 2, 32, True),        # 86 chunks of 48 rows, rpb = 6: neither divides 4099
+        (640, 0, 1021, 3, 32, False),       # a prime row count, rpb = 3
+        (320, 0, 65536 + 37, 1, 32, True),  # the 256-chunk cap, ragged last chunk
+        (1280, 640, 12289, 2, 32, True),    # two sources at the cap
+        (2560, 0, 2053, 2, 32, False),      # V = 320: one row per block
+        (2560, 0, 1024, 2, 32, True),
+        (8, 0, 3001, 2, 4, True),           # C = 8: one vector per row, 256 rows per block
+        (8, 0, 70001, 1, 8, False),
+    ]
+    for C0, C1, rpg, nsg, G, silu in cases:
+        C, M = C0 + C1, nsg * rpg
+        x = _offset_data(nsg, rpg, C, G, 3, seed=rpg)
+        x0, x1 = (x[:, :C0].contiguous(), x[:, C0:].contiguous()) if C1 else (x, None)
+        ga, be = _affine(C, 31)
+        buf, y, guard = _guarded(M, C)
+        need = ops.gn_scratch_floats(M, rpg, G)
+        stats = torch.full((need + TAIL,), -1234.5, dtype=torch.float32, device=DEV)
+        ops.groupnorm(x0, ga, be, stats, rpg, x1=x1, groups=G, eps=1e-5, silu=silu, out=y)
+        ref = _gn_ref64(x0, x1, ga, be, rpg, G, 1e-5, silu)
+        name = f"groupnorm edge C{C0}+{C1} rows/group {rpg} x {nsg} G{G} silu={silu}"
+        out.append(_res(name, y, ref, KTOL))
+        out.append(dict(name=name + ": output guard rows and stats tail untouched", err=0.0, tol=0.0,
+                        ok=_guard_intact(buf, M, guard) and bool((stats[need:] == -1234.5).all())))
+    # batch hint: 8 groups of 16 x 1024 rows -> 192 chunks; hinted as 12 groups -> 128 chunks
+    nsg, rpg, C = 8, 16 * 1024, 320
+    x = _offset_data(nsg, rpg, C, 32, 50, seed=99)
+    ga, be = _affine(C, 41)
+    ref = _gn_ref64(x, None, ga, be, rpg, 32, 1e-5, True)
+    plain = _gn_run(x, None, ga, be, rpg, 32, 1e-5, True)
+    with ops.batch_hint(3, 2):
+        h1 = _gn_run(x, None, ga, be, rpg, 32, 1e-5, True)
+        h2 = _gn_run(x, None, ga, be, rpg, 32, 1e-5, True)
+    out.append(_res("groupnorm 8 x 16384 rows, offset 50 sigma: plain", plain, ref, KTOL))
+    out.append(_res("groupnorm 8 x 16384 rows, offset 50 sigma: under batch_hint(3, 2)", h1, ref, KTOL))
+    out.append(dict(name="groupnorm under batch_hint(3, 2): bit-reproducible call to call", err=0.0, tol=0.0, ok=bool(torch.equal(h1, h2))))
+    return out
+
+
+def gn_sharded_emulated(xs0, xs1, ga, be, rpg_local, *, groups=32, eps=1e-5, silu=False):
+    """``len(xs0)`` ranks of a sharded GroupNorm run in one process through ``ops.groupnorm(shard=...)``.  The all-reduce callback
+    is emulated in passes: in pass p every rank's callback answers rounds < p with the sums agreed so far, records its own
+    buffer of round p, and leaves later rounds alone; the recorded buffers are added in rank order and the next pass starts.  The
+    pass in which no rank reaches a new round returns the ranks' outputs.  (Works for any number of all-reduce rounds.)"""
+    S = len(xs0)
+    stats = [torch.zeros(ops.gn_scratch_floats(x.shape[0], rpg_local, groups), dtype=torch.float32, device=DEV) for x in xs0]
+    agreed = []
+    while True:
+        contrib = [None] * S
+        ys = []
+        for r in range(S):
+            k = [0]
+
+            def cb(t, r=r, k=k):
+                if k[0] < len(agreed):
+                    t.copy_(agreed[k[0]])
+                elif k[0] == len(agreed):
+                    contrib[r] = t.clone()
+                k[0] += 1
+            ys.append(ops.groupnorm(xs0[r], ga, be, stats[r], rpg_local, x1=None if xs1 is None else xs1[r], groups=groups, eps=eps,
+                                    silu=silu, shard=(S, cb)))
+        if contrib[0] is None:
+            return ys
+        tot = contrib[0].clone()
+        for c in contrib[1:]:
+            tot += c
+        agreed.append(tot)
+
+
+def check_groupnorm_sharded_offsets():
+    """Sharded GroupNorm (frame-parallel clips) on data with large group offsets: a clip split into 2 and 4 pixel ranges over
+    emulated ranks equals the unsharded call and the float64 reference; shards = 1 through the same path is the one call, bit for
+    bit."""
+    out = []
+    B, Fr, hw, c0, c1 = 1, 16, 1024, 320, 320
+    rpg = Fr * hw
+    x = _offset_data(B, rpg, c0 + c1, 32, 200, seed=5)
+    x0, x1 = x[:, :c0].contiguous(), x[:, c0:].contiguous()
+    ga, be = _affine(c0 + c1, 51)
+    full = _gn_run(x0, x1, ga, be, rpg, 32, 1e-5, True)
+    ref = _gn_ref64(x0, x1, ga, be, rpg, 32, 1e-5, True)
+    out.append(_res("groupnorm 5-D two-source offset 200 sigma, unsharded", full, ref, KTOL))
+    one = gn_sharded_emulated([x0], [x1], ga, be, rpg, silu=True)[0]
+    out.append(_res("groupnorm sharded path, shards = 1 == one call (bit-equal)", one, full.float(), 0.0 if DEV != "cpu" else 2e-3))
+    for S in (2, 4):
+        def split(t):
+            v = t.view(B, Fr, hw, t.shape[1])
+            return [v[:, :, i * hw // S:(i + 1) * hw // S].reshape(-1, t.shape[1]).contiguous() for i in range(S)]
+        ys = gn_sharded_emulated(split(x0), split(x1), ga, be, rpg // S, silu=True)
+        got = torch.cat([y.view(B, Fr, hw // S, c0 + c1) for y in ys], 2).reshape(B * rpg, c0 + c1)
+        out.append(_res(f"groupnorm sharded over {S} pixel ranges, offset 200 sigma, vs unsharded", got, full.float(), 2e-3))
+        out.append(_res(f"groupnorm sharded over {S} pixel ranges, offset 200 sigma, vs float64", got, ref, KTOL))
+    if DEV == "cpu":   # (the op emulation has no counterpart of the raw C entry points below)
+        return out
+    # the pre-104 one-all-reduce pair (pivot 0, no longer used by ops) on moderately offset data: two identical shards, the
+    # 'all-reduce' doubling the partial sums
+    from anyv2v_amd import _lib
+    lib = _lib.load()
+    xm = (rnd(2 * 4096, 320, seed=61).float() + 0.5).half()
+    gam, bet = _affine(320, 62)
+    st = torch.zeros(ops.gn_scratch_floats(xm.shape[0], 4096), dtype=torch.float32, device=DEV)
+    ym = torch.empty_like(xm)
+    n = int(lib.anyv2v_groupnorm_partial_floats(xm.shape[0], 4096, 32, 320))
+    _lib.check(lib.anyv2v_groupnorm_partial_f16(xm.data_ptr(), None, 320, 0, st.data_ptr(), xm.shape[0], 4096, 32, ops._stream()))
+    st[:n].mul_(2)
+    _lib.check(lib.anyv2v_groupnorm_apply_f16(xm.data_ptr(), None, 320, 0, ym.data_ptr(), gam.data_ptr(), bet.data_ptr(), st.data_ptr(),
+                                              xm.shape[0], 4096, 32, 1e-5, 1, 2, ops._stream()))
+    out.append(_res("groupnorm pre-104 sharded pair (one all-reduce), 2 identical shards", ym,
+                    _gn_ref64(xm, None, gam, bet, 4096, 32, 1e-5, True), KTOL))
+    return out
+
+
+def check_layernorm_large():
+    """LayerNorm beyond the 8192-block grid cap (several grid-stride iterations per wave), at C = 1024 / 1280 / 2048 (largest
+    fast-kernel row) / 2056 and 12 (the one-thread-per-row kernel), with row offsets of 100 and 1000 sigma; outputs carved from a
+    guarded buffer (nothing written outside the rows)."""
+    out = []
+    cases = [(3 * 16 * 4096, 320, 0.0), (100001, 320, 0.0), (100001, 320, 100.0), (100001, 320, 1000.0), (66001, 1024, 0.0),
+             (4099, 1280, 1000.0), (20001, 2048, 0.0), (20001, 2048, 100.0), (20001, 2056, 0.0), (20001, 2056, 1000.0),
+             (70001, 12, 0.0), (70001, 12, 100.0)]
+    for i, (M, C, offset) in enumerate(cases):
+        g = torch.Generator(device="cpu").manual_seed(i)
+        sign = (torch.randint(0, 2, (M, 1), generator=g) * 2 - 1).float().to(DEV)
+        x = (rnd(M, C, seed=600 + i).float() + sign * offset).half()
+        ga, be = _affine(C, 700 + i)
+        buf, y, guard = _guarded(M, C)
+        ops.layernorm(x, ga, be, 1e-5, out=y)
+        name = f"layernorm M{M} C{C} offset {offset:g} sigma"
+        out.append(_res(name, y, _ln_ref64(x, ga, be, 1e-5), KTOL))
+        out.append(dict(name=name + ": output guard rows untouched", err=0.0, tol=0.0, ok=_guard_intact(buf, M, guard)))
     return out
 
 

@@ -29,7 +29,7 @@ def test_library_exports_every_symbol_the_header_declares():
     for name in decl:
         assert hasattr(lib, name), f"{name} declared in include/anyv2v_hip.h but not exported"
     assert set(decl) == set(_lib.SYMBOLS), "ctypes binding table and header disagree"
-    assert _lib.load().anyv2v_version() >= 103
+    assert _lib.load().anyv2v_version() >= 104
 
 
 def test_graft_entry_build_runs_here():
@@ -58,6 +58,22 @@ def test_abi_argument_validation_without_gpu():
     assert lib.anyv2v_groupnorm_partial_f16(16, None, 64, 0, 16, 9, 8, 32, None) == -1      # M % rows_per_group
     assert lib.anyv2v_groupnorm_apply_f16(16, None, 64, 0, 16, 16, 16, 16, 8, 8, 32, 1e-5, 0, 0, None) == -1
     assert b"shards" in lib.anyv2v_last_error()
+    # the pivoted sharded entry points (ABI 104): the same checks, plus the agreed pivot
+    assert lib.anyv2v_groupnorm_partial_pivot_f16(None, None, 64, 0, 16, None, 8, 8, 32, None) == -1
+    assert b"null pointer" in lib.anyv2v_last_error()
+    assert lib.anyv2v_groupnorm_partial_pivot_f16(16, None, 64, 0, None, 16, 8, 8, 32, None) == -1   # no agreed pivot
+    assert b"null pointer" in lib.anyv2v_last_error()
+    assert lib.anyv2v_groupnorm_partial_pivot_f16(16, None, 60, 0, 16, 16, 8, 8, 32, None) == -1      # C0 % 8
+    assert lib.anyv2v_groupnorm_partial_pivot_f16(16, None, 64, 0, 16, 16, 9, 8, 32, None) == -1      # M % rows_per_group
+    assert lib.anyv2v_groupnorm_apply_pivot_f16(16, None, 64, 0, 16, 16, 16, 16, 16, 8, 8, 32, 1e-5, 0, 0, None) == -1
+    assert b"shards" in lib.anyv2v_last_error()
+    assert lib.anyv2v_groupnorm_apply_pivot_f16(16, None, 64, 0, 16, 16, 16, None, 16, 8, 8, 32, 1e-5, 0, 1, None) == -1
+    assert b"null pointer" in lib.anyv2v_last_error()
+    assert lib.anyv2v_groupnorm_pivot_f16(16, None, 64, 0, None, 8, 8, 32, 1, None) == -1
+    assert b"null pointer" in lib.anyv2v_last_error()
+    assert lib.anyv2v_groupnorm_pivot_f16(16, None, 64, 0, 16, 8, 8, 32, 0, None) == -1
+    assert b"shards" in lib.anyv2v_last_error()
+    assert lib.anyv2v_groupnorm_pivot_f16(16, None, 64, 0, 16, 9, 8, 32, 1, None) == -1       # M % rows_per_group
     assert lib.anyv2v_groupnorm_partial_floats(8, 9, 32, 64) == -1 and lib.anyv2v_groupnorm_partial_floats(64, 8, 32, 64) == 8 * 32 * 2
     assert lib.anyv2v_groupnorm_partial_floats(64, 8, 32, 64) <= lib.anyv2v_groupnorm_scratch_floats(64, 8, 32)
     # round 3: LayerNorm fold only on the weight-stationary shapes; rotary / row gather / attention bias argument checks

@@ -20,7 +20,7 @@ def _assert_all(results):
 
 def test_hip_library_loaded_and_mfma_layouts():
     from anyv2v_amd import _lib
-    assert _lib.load().anyv2v_version() >= 103
+    assert _lib.load().anyv2v_version() >= 104
     _assert_all(gc.check_selftest())
 
 
@@ -84,6 +84,31 @@ def test_conv(variant):
 
 def test_norms():
     _assert_all(gc.check_norms())
+
+
+def test_norms_at_every_shape_the_models_issue():
+    """Every distinct GroupNorm / LayerNorm call signature of one forward of the full-width I2VGen-XL UNet (config 1), the mini and
+    full VAE and the ConsistI2V / SEINE UNets, at its real rows per group, plus the bench's 5-D groups and the VAE's 512^2 groups,
+    against float64 two-pass statistics."""
+    _assert_all(gc.check_norms_at_recorded_shapes())
+
+
+def test_groupnorm_ill_conditioned_groups():
+    """Group offsets up to 1000 sigma, near-constant, constant and all-zero groups, a two-source group with different offsets in
+    X0 and X1: the shifted statistics keep every row within KTOL of float64."""
+    _assert_all(gc.check_groupnorm_ill_conditioned())
+
+
+def test_groupnorm_plan_edges_and_write_guards():
+    _assert_all(gc.check_groupnorm_plan_edges())
+
+
+def test_groupnorm_sharded_with_offsets():
+    _assert_all(gc.check_groupnorm_sharded_offsets())
+
+
+def test_layernorm_large_grids_wide_rows_offsets_and_write_guards():
+    _assert_all(gc.check_layernorm_large())
 
 
 

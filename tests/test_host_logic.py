@@ -94,7 +94,7 @@ def test_step_engines_are_reused_across_clips_without_stale_state(cpu_ops):
 
 def test_kernel_check_references_are_self_consistent(cpu_ops):
     """The references used by the gpu kernel tests agree with the op contracts (so a gpu failure is a kernel bug)."""
-    for f in (gc.check_gemm, gc.check_conv, gc.check_norms, gc.check_attention, gc.check_elementwise):
+    for f in (gc.check_gemm, gc.check_conv, gc.check_norms, gc.check_groupnorm_sharded_offsets, gc.check_attention, gc.check_elementwise):
         _ok(f())
 
 
