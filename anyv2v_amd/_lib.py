@@ -10,7 +10,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libanyv2v_hip.so")
-ABI_VERSION = 104   # ANYV2V_ABI_VERSION of include/anyv2v_hip.h the structures below mirror
+ABI_VERSION = 105   # ANYV2V_ABI_VERSION of include/anyv2v_hip.h the structures below mirror
 
 
 class HipExtensionMissing(RuntimeError):
@@ -33,6 +33,7 @@ class GemmDesc(C.Structure):
         ("act", C.c_int32), ("flags", C.c_int32),
         ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64),
         ("ln_c1", C.c_void_p), ("ln_eps", C.c_float), ("reserved0", C.c_int32),
+        ("gn_stats", C.c_void_p), ("gn_stats_floats", C.c_int64), ("gn_rows_per_group", C.c_int32), ("gn_groups", C.c_int32),
     ]
 
 
@@ -60,9 +61,13 @@ class AttnDesc(C.Structure):
 _VP, _I32, _I64, _F32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 SYMBOLS = {
     "anyv2v_gemm_f16": (C.c_int, [C.POINTER(GemmDesc), _VP]),
+    "anyv2v_gemm_gn_stats_floats": (C.c_int64, [C.POINTER(GemmDesc)]),
+    "anyv2v_gemm_gn_launches": (C.c_int64, [_I32]),
     "anyv2v_ff_geglu_f16": (C.c_int, [C.POINTER(FFDesc), _VP]),
     "anyv2v_groupnorm_f16": (C.c_int, [_VP, _VP, _I32, _I32, _VP, _VP, _VP, _VP, _I32, _I32, _I32, _F32, _I32, _VP]),
     "anyv2v_groupnorm_scratch_floats": (C.c_int64, [_I32, _I32, _I32]),
+    "anyv2v_groupnorm_stats_floats": (C.c_int64, [_I32, _I32, _I32]),
+    "anyv2v_groupnorm_apply_stats_f16": (C.c_int, [_VP, _VP, _VP, _VP, _VP, C.POINTER(C.c_int32), _F32, _I32, _VP]),
     "anyv2v_groupnorm_partial_floats": (C.c_int64, [_I32, _I32, _I32, _I32]),
     "anyv2v_groupnorm_partial_f16": (C.c_int, [_VP, _VP, _I32, _I32, _VP, _I32, _I32, _I32, _VP]),
     "anyv2v_groupnorm_apply_f16": (C.c_int, [_VP, _VP, _I32, _I32, _VP, _VP, _VP, _VP, _I32, _I32, _I32, _F32, _I32, _I32, _VP]),

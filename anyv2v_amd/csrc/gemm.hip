@@ -24,7 +24,8 @@ __device__ __attribute__((aligned(256))) half_t g_zero_line[128];  // 256 B of z
 // ---------------------------------------------------------------------------------------------------------
 // Shared epilogue: accumulators -> (+bias, +temb row vector, activation / GEGLU) -> fp16 tile staged in LDS ->
 // (+residual) -> coalesced 16-byte stores.  Caller guarantees all waves are done with the pipeline LDS.
-template <int NF, bool GEGLU, int BM, int NTHREADS>
+// GN: the launch also writes GroupNorm records of the stored tile (gn_slab_records; NF = 5, no GEGLU / split-K / fp32 output).
+template <int NF, bool GEGLU, int BM, int NTHREADS, bool GN = false>
 __device__ __forceinline__ void epilogue(const GemmK& p, f4 (&acc)[4][NF], char* smem, int m_blk, int n_blk, int wr,
                                          int wc, int lane, int tid, int split = 0, long long* tr = nullptr) {
     constexpr int BN = NF * 32;
@@ -172,8 +173,20 @@ __device__ __forceinline__ void epilogue(const GemmK& p, f4 (&acc)[4][NF], char*
             h8 v = *(const h8*)(Cs + r * CS_LD + cc * 8);
             if (p.R != nullptr) {
                 v = v + rr[it];  // fp16 add: correctly rounded, i.e. what the fp32 add + rounding of two fp16 values gives
+                if constexpr (GN) *(h8*)(Cs + r * CS_LD + cc * 8) = v;  // the records are taken of what is stored
             }
             if (m < p.M && n0 < Nout) *(h8*)(p.C + (size_t)m * p.ldc + n0) = v;
+        }
+        if constexpr (GN) {
+            static_assert(!GEGLU && BN == 160 && BM % 16 == 0, "GroupNorm records: 160-column tiles of 16-row fragments");
+            if (p.R != nullptr) __syncthreads();  // (block-uniform) the tile with the residual added is back in LDS
+            const int wv = tid >> 6;
+            for (int f = wv; f < BM / 16; f += NTHREADS / 64) {
+                const int m0 = m_blk + f * 16;   // M % 16 == 0 (dispatch): a fragment lies inside M or outside, never across
+                if (m0 < p.M)
+                    gn_slab_records(Cs + f * 16 * CS_LD, CS_LD, p.gn_cg, lane,
+                                    p.gn_stats + ((size_t)(m0 >> 4) * p.gn_groups + n_blk / p.gn_cg) * 3);
+            }
         }
         return;
     }
@@ -373,7 +386,7 @@ __device__ __forceinline__ void mma_tile_asm(f4 (&acc)[4][NF], const char* as, c
 
 // ---------------------------------------------------------------------------------------------------------
 // KO (debug knock-outs): 2 = K loop issues only the W tiles, 3 = K loop issues no loads, 4 / 5 see mma_tile
-template <int NF, bool GLDS, bool GEGLU, int MODE, bool TRACE = false, int KO = 0>
+template <int NF, bool GLDS, bool GEGLU, int MODE, bool TRACE = false, int KO = 0, bool GN = false>
 __global__ __launch_bounds__(256, 2) void gemm_mfma_kernel(const GemmK p) {
     constexpr int BM = 128, BN = NF * 32;
     constexpr int A_BYTES = BM * 64 * 2;
@@ -482,7 +495,7 @@ __global__ __launch_bounds__(256, 2) void gemm_mfma_kernel(const GemmK p) {
         if constexpr (TRACE) if (tid == 0 && kt < 8) tr[12 + kt] = (long long)__builtin_amdgcn_s_memtime();
     }
     if constexpr (TRACE) if (tid == 0) tr[20] = (long long)__builtin_amdgcn_s_memtime();
-    epilogue<NF, GEGLU, BM, 256>(p, acc, smem, m_blk, n_blk, wr, wc, lane, tid, split, tr);
+    epilogue<NF, GEGLU, BM, 256, GN>(p, acc, smem, m_blk, n_blk, wr, wc, lane, tid, split, tr);
     if constexpr (TRACE) {
         if (tid == 0) tr[26] = (long long)__builtin_amdgcn_s_memtime();
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -565,9 +578,11 @@ __device__ __forceinline__ void mma_tile_big(f4 (&acc)[MF][10], const char* as, 
 // RES: the launch adds a residual (p.R != nullptr).  A separate instantiation: its epilogue holds the residual rows of the whole
 // wave tile in registers (requested right after the K loop, so that they land under the settle wait and the barrier that follow,
 // and the epilogue itself issues no load at all -- a load there makes hipcc wait for the stores of the slabs before it).
-template <int MF, bool GEGLU, int MODE, bool TRACE = false, bool SPLIT = false, bool RES = false>
+// GN: the launch also writes GroupNorm records of every stored 16-row slab (gn_slab_records), a separate instantiation as well.
+template <int MF, bool GEGLU, int MODE, bool TRACE = false, bool SPLIT = false, bool RES = false, bool GN = false>
 __global__ __launch_bounds__(512) void gemm_big_kernel(const GemmK p) {
     static_assert(!(RES && (GEGLU || SPLIT)), "no residual on GEGLU / split-K launches");
+    static_assert(!(GN && (GEGLU || SPLIT)), "no GroupNorm records on GEGLU / split-K launches");
     constexpr int BM = 64 * MF, BN = 320;  // four wave rows of MF 16-row fragments
     constexpr int A_BYTES = BM * 128, B_BYTES = BN * 128, STAGE_BYTES = A_BYTES + B_BYTES;
     constexpr int SLAB_LD = (GEGLU ? 80 : 160) + 8;          // halves; 16-byte aligned rows
@@ -803,7 +818,15 @@ __global__ __launch_bounds__(512) void gemm_big_kernel(const GemmK p) {
                 const bool ok = (16 * CPRW % 64 == 0 || c < 16 * CPRW) && m_wave + mf * 16 + row < p.M;
                 h8 v = *(const h8*)(slab + (ok ? row * SLAB_LD + cc * 8 : 0));
                 if constexpr (RES) v = v + rr[mf][it];  // fp16 add: correctly rounded, == the fp32 add + rounding of two fp16 values
+                if constexpr (RES && GN) {   // the records are taken of what is stored
+                    if (ok) *(h8*)(slab + row * SLAB_LD + cc * 8) = v;
+                }
                 if (ok) *(h8*)(p.C + (size_t)(m_wave + mf * 16 + row) * p.ldc + n_out_wave + cc * 8) = v;
+            }
+            if constexpr (GN) {   // M % 16 == 0 (dispatch): a slab lies inside M or outside, never across
+                const int m0 = m_wave + mf * 16;
+                if (m0 < p.M)
+                    gn_slab_records(slab, SLAB_LD, p.gn_cg, lane_e, p.gn_stats + ((size_t)(m0 >> 4) * p.gn_groups + n_wave / p.gn_cg) * 3);
             }
         }
 
@@ -1166,10 +1189,29 @@ static const half_t* zero_line() {
 // tile's start-up hoisted in front of the tile-switch barrier was slower throughout (r04_gemm_pp_ab_v2_*.txt, not kept).
 constexpr int AV_PP_MIN_KTILES = 1 << 30;
 
+// GroupNorm records from the epilogue (AnyV2VGemmDesc.gn_stats): shapes the record layout covers, whatever the plan.
+static bool gn_shape_ok(const AnyV2VGemmDesc* d) {
+    if (d->gn_groups <= 0 || d->gn_rows_per_group <= 0 || d->N % 160 != 0 || d->N % d->gn_groups != 0) return false;
+    const int cg = d->N / d->gn_groups;
+    return 40 % cg == 0 && d->M % 16 == 0 && d->gn_rows_per_group % 16 == 0 && d->M % d->gn_rows_per_group == 0 &&
+           (d->act == ACT_NONE || d->act == ACT_SILU || d->act == ACT_GELU);
+}
+static int64_t g_gn_launches = 0;   // launches that emitted records (anyv2v_gemm_gn_launches); host-side, like the batch hint
+
+// gn_query != nullptr: plan only -- *gn_query = 1 when the launch this descriptor gets can emit GroupNorm records, nothing is
+// enqueued.  One function plans for the query and for the launch, so the two cannot disagree.
+#define AV_GN_DECLINE(what)                                                                                              \
+    do {                                                                                                                 \
+        if (gn_query != nullptr) return ANYV2V_OK;                                                                       \
+        AV_CHECK(d->gn_stats == nullptr, "gemm: gn_stats set, but this launch runs on " what                            \
+                                         ", which writes no GroupNorm statistics (ask anyv2v_gemm_gn_stats_floats first)"); \
+    } while (0)
 template <int MODE>
-static int dispatch(GemmK& k, const AnyV2VGemmDesc* d, bool fast, hipStream_t s) {
+static int dispatch(GemmK& k, const AnyV2VGemmDesc* d, bool fast, hipStream_t s, int* gn_query) {
     const bool geglu = d->act == ACT_GEGLU;
+    const bool gn = gn_query != nullptr || d->gn_stats != nullptr;
     if (!fast) {
+        AV_GN_DECLINE("the naive kernel");
         const int Nout = geglu ? d->N / 2 : d->N;
         const long long total = (long long)d->M * Nout;
         hipLaunchKernelGGL(gemm_naive_kernel<MODE>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, k);
@@ -1182,12 +1224,21 @@ static int dispatch(GemmK& k, const AnyV2VGemmDesc* d, bool fast, hipStream_t s)
     if (glds && (d->flags & ((1 << 26) | (1 << 27))) && !(d->flags & (1 << 22)) && av_gemm_sw_eligible(d) && av_hint_rows(d->M) == d->M &&
         d->workspace != nullptr) {
         const int blocks = av_gemm_sw_sk_blocks(d, (d->flags & (1 << 27)) != 0);
-        if (blocks > 0 && av_gemm_sw_sk_workspace(blocks) <= (size_t)d->workspace_bytes) return av_gemm_sw_sk_launch(k, d, blocks, s);
+        if (blocks > 0 && av_gemm_sw_sk_workspace(blocks) <= (size_t)d->workspace_bytes) {
+            AV_GN_DECLINE("the stream-K kernel");
+            return av_gemm_sw_sk_launch(k, d, blocks, s);
+        }
     }
     // 3x3 convolution with LDS reuse of the A operand across the dx taps (gemm_swh.hip): flags bit28 takes it where eligible.
-    if (glds && (d->flags & (1 << 28)) && !(d->flags & (1 << 22)) && av_gemm_swh_eligible(d)) return av_gemm_swh_launch(k, d, s);
+    if (glds && (d->flags & (1 << 28)) && !(d->flags & (1 << 22)) && av_gemm_swh_eligible(d)) {
+        AV_GN_DECLINE("the LDS-patch convolution kernel");
+        return av_gemm_swh_launch(k, d, s);
+    }
     // One-wave-per-SIMD persistent kernel (gemm_sw.hip): flags bit21 takes it wherever the shape allows, bit22 forbids it.
-    if (glds && (d->flags & (1 << 21)) && !(d->flags & (1 << 22)) && av_gemm_sw_eligible(d)) return av_gemm_sw_launch(k, d, s);
+    if (glds && (d->flags & (1 << 21)) && !(d->flags & (1 << 22)) && av_gemm_sw_eligible(d)) {
+        AV_GN_DECLINE("the one-wave-per-SIMD kernel");
+        return av_gemm_sw_launch(k, d, s);
+    }
     // 128-row kernel tile width: 160 columns (NF = 5) where N allows it, except where 128-column tiles (NF = 4) quantise better onto
     // the 256 CUs x 2 resident blocks -- more CUs busy when there is less than one tile per CU, or the same number of rounds with
     // 20 % smaller tiles (flags bit11 / bit12 force NF = 4 / 5: A/B in tools/gemm_nf_ab.py).  Same arithmetic per output either way.
@@ -1273,6 +1324,7 @@ static int dispatch(GemmK& k, const AnyV2VGemmDesc* d, bool fast, hipStream_t s)
             const int tb = ((d->M + bm - 1) / bm) * (d->N / 320), r = (tb + 255) / 256;
             return (double)tb / (r * 256.0);
         };
+        AV_GN_DECLINE("the ping-pong kernel");
         const int mf = (d->flags & (1 << 19)) ? 3 : ((d->flags & (1 << 20)) ? 4 : (eff(256) + 0.02 >= eff(192) ? 4 : 3));
         const int tb = ((d->M + 64 * mf - 1) / (64 * mf)) * (d->N / 320);
         const dim3 gridp(tb < 256 ? tb : 256);
@@ -1290,6 +1342,25 @@ static int dispatch(GemmK& k, const AnyV2VGemmDesc* d, bool fast, hipStream_t s)
             AV_PP(3);
 #undef AV_PP
         return av_launch_status("gemm_pp");
+    }
+    // GroupNorm records: both tile kernels emit them in their unsplit, fp16-output, non-GEGLU forms (LDS-DMA staging); a split-K plan
+    // finishes in the reduce kernel, which has no tile to take them of.  Decided on `use`, i.e. under the batch hint, like the launch.
+    if (gn) {
+        if (use.splits > 1) AV_GN_DECLINE("a split-K plan");
+        if (geglu || d->act == ACT_F32OUT || !glds || !gn_shape_ok(d))
+            AV_GN_DECLINE("a GEGLU / fp32-output / register-staged launch or a shape the record layout does not cover (N %% 160 = 0, N / gn_groups "
+                          "dividing 40, M and gn_rows_per_group multiples of 16)");
+        if (gn_query != nullptr) {
+            *gn_query = 1;
+            return ANYV2V_OK;
+        }
+        AV_CHECK(d->gn_stats_floats >= (int64_t)3 * (d->M / 16) * d->gn_groups, "gemm: gn_stats holds %lld floats, the launch writes %lld",
+                 (long long)d->gn_stats_floats, (long long)3 * (d->M / 16) * d->gn_groups);
+        AV_CHECK((((uintptr_t)d->gn_stats) & 3) == 0, "gemm: gn_stats must be 4-byte aligned");
+        k.gn_stats = d->gn_stats;
+        k.gn_groups = d->gn_groups;
+        k.gn_cg = d->N / d->gn_groups;
+        ++g_gn_launches;
     }
     {   // ANYV2V_GEMM_LOG=1: one line per launch plan on stderr (diagnostics: which launches split, and how, under a batch hint)
         static const bool log_on = getenv("ANYV2V_GEMM_LOG") != nullptr;
@@ -1331,6 +1402,13 @@ static int dispatch(GemmK& k, const AnyV2VGemmDesc* d, bool fast, hipStream_t s)
 #ifdef ANYV2V_EXPERIMENTS  // probe build only (make experiments): phase-timestamp instantiations, tools/gemm_big_trace.py
 #include "../../tools/experiments/gemm_dispatch_big_probe.inc"
 #endif
+        if (gn) {   // (never GEGLU: declined above)
+            if (d->R != nullptr)
+                hipLaunchKernelGGL((gemm_big_kernel<3, false, MODE, false, false, true, true>), grid, dim3(512), 0, s, k);
+            else
+                hipLaunchKernelGGL((gemm_big_kernel<3, false, MODE, false, false, false, true>), grid, dim3(512), 0, s, k);
+            return av_launch_status("gemm_big<gn>");
+        }
         if constexpr (MODE == MODE_LINEAR) {
             if (geglu)
                 hipLaunchKernelGGL((gemm_big_kernel<3, true, MODE_LINEAR>), grid, dim3(512), 0, s, k);
@@ -1345,7 +1423,9 @@ static int dispatch(GemmK& k, const AnyV2VGemmDesc* d, bool fast, hipStream_t s)
         }
         return av_launch_status("gemm_big");
     }
-    k.tilesN = tilesN_small;
+    // (with records: always the 160-column tile -- a channel group must not straddle the tile, and the width does not touch the
+    //  arithmetic; the plan above, split-K factor included, is the one the launch without records gets)
+    k.tilesN = gn ? d->N / 160 : tilesN_small;
     const int tiles = ((d->M + 127) / 128) * k.tilesN;
     const int nk = nk_all;
     (void)nk;
@@ -1364,7 +1444,9 @@ static int dispatch(GemmK& k, const AnyV2VGemmDesc* d, bool fast, hipStream_t s)
         else                                                                                             \
             hipLaunchKernelGGL((gemm_mfma_kernel<NF_, false, GEGLU_, MODE>), grid, dim3(256), 0, s, k);  \
     } while (0)
-    if (geglu)
+    if (gn)
+        hipLaunchKernelGGL((gemm_mfma_kernel<5, true, false, MODE, false, 0, true>), grid, dim3(256), 0, s, k);
+    else if (geglu)
         AV_LAUNCH2(4, true);
     else if (nf == 5)
         AV_LAUNCH2(5, false);
@@ -1380,9 +1462,9 @@ static int dispatch(GemmK& k, const AnyV2VGemmDesc* d, bool fast, hipStream_t s)
     return av_launch_status("gemm_mfma");
 }
 
-extern "C" int anyv2v_gemm_f16(const AnyV2VGemmDesc* d, void* stream) {
+static int gemm_impl(const AnyV2VGemmDesc* d, void* stream, int* gn_query) {
     AV_CHECK(d != nullptr, "gemm: null descriptor");
-    AV_CHECK(d->A0 && d->W && d->C, "gemm: null A0/W/C");
+    AV_CHECK(d->A0 && d->W && (d->C || gn_query != nullptr), "gemm: null A0/W/C");
     AV_CHECK(d->M > 0 && d->N > 0 && d->C0 > 0 && d->C1 >= 0, "gemm: bad M/N/C0/C1 (%d %d %d %d)", d->M, d->N, d->C0, d->C1);
     AV_CHECK(d->mode >= 0 && d->mode <= 2, "gemm: bad mode %d", d->mode);
     AV_CHECK(d->act >= 0 && d->act <= 4, "gemm: bad act %d", d->act);
@@ -1431,6 +1513,8 @@ extern "C" int anyv2v_gemm_f16(const AnyV2VGemmDesc* d, void* stream) {
     k.ln_c1 = nullptr;
     k.ln_eps = 0.f;
     k.rast_gm = k.rast_gn = k.rast_sm = k.rast_sn = k.rast_nfast = 0;
+    k.gn_stats = nullptr;
+    k.gn_groups = k.gn_cg = 0;
     k.vec_epi = (((uintptr_t)d->bias & 7) == 0) && (((uintptr_t)d->rowvec & 7) == 0) && (d->ldrv % 4 == 0) && (d->N % 4 == 0);
     hipStream_t s = (hipStream_t)stream;
 
@@ -1443,6 +1527,7 @@ extern "C" int anyv2v_gemm_f16(const AnyV2VGemmDesc* d, void* stream) {
     // K = 320 Linear layers with many rows (the 64x64 level): weight-stationary streaming kernel (gemm_ws.hip).
     // flags bit9 (512): never, bit10 (1024): whenever the shape allows (tests; small M leaves most waves idle)
     if (d->ln_c1 != nullptr) {   // LayerNorm folded into the GEMM: only the weight-stationary kernel implements it
+        AV_GN_DECLINE("the LayerNorm-fold kernel");
         if (!(fast && (d->flags & 2) && !(d->flags & 1) && av_gemm_ws_eligible(d) && (((uintptr_t)d->ln_c1) & 15) == 0)) {
             anyv2v_set_error("gemm: ln_c1 (LayerNorm fold) needs mode 0, C0 = 320 (N %% 160 = 0) or C0 = 512 with GEGLU (N %% 128 = 0), no "
                              "residual / rowvec, 16-byte aligned operands -- got C0 %d N %d act %d", d->C0, d->N, d->act);
@@ -1451,9 +1536,26 @@ extern "C" int anyv2v_gemm_f16(const AnyV2VGemmDesc* d, void* stream) {
         return av_gemm_ws_launch(k, d, s);
     }
     if (fast && (d->flags & 2) && !(d->flags & (512 | 4 | 1)) && av_gemm_ws_eligible(d) &&
-        (av_hint_rows(d->M) >= 32768 || (d->flags & 1024)))
+        (av_hint_rows(d->M) >= 32768 || (d->flags & 1024))) {
+        AV_GN_DECLINE("the weight-stationary kernel");
         return av_gemm_ws_launch(k, d, s);
-    if (d->mode == MODE_CONV2D) return dispatch<MODE_CONV2D>(k, d, fast, s);
-    if (d->mode == MODE_TEMPORAL) return dispatch<MODE_TEMPORAL>(k, d, fast, s);
-    return dispatch<MODE_LINEAR>(k, d, fast, s);
+    }
+    if (d->mode == MODE_CONV2D) return dispatch<MODE_CONV2D>(k, d, fast, s, gn_query);
+    if (d->mode == MODE_TEMPORAL) return dispatch<MODE_TEMPORAL>(k, d, fast, s, gn_query);
+    return dispatch<MODE_LINEAR>(k, d, fast, s, gn_query);
+}
+#undef AV_GN_DECLINE
+
+extern "C" int anyv2v_gemm_f16(const AnyV2VGemmDesc* d, void* stream) { return gemm_impl(d, stream, nullptr); }
+
+extern "C" int64_t anyv2v_gemm_gn_stats_floats(const AnyV2VGemmDesc* d) {
+    int can = 0;
+    if (d == nullptr || gemm_impl(d, nullptr, &can) != ANYV2V_OK || !can) return 0;
+    return (int64_t)3 * (d->M / 16) * d->gn_groups;
+}
+
+extern "C" int64_t anyv2v_gemm_gn_launches(int32_t reset) {
+    const int64_t n = g_gn_launches;
+    if (reset) g_gn_launches = 0;
+    return n;
 }

@@ -28,6 +28,9 @@ struct GemmK {
     // persistent kernel, rastered tile order (0 = classic): an XCD round covers rast_gm x rast_gn output tiles; rast_sm x rast_sn
     // super-tiles, walked M-fastest (rast_nfast = 0) or N-fastest
     int rast_gm, rast_gn, rast_sm, rast_sn, rast_nfast;
+    // GroupNorm records from the epilogue (GN instantiations only): [M / 16][gn_groups][3] floats, gn_cg = N / gn_groups
+    float* gn_stats;
+    int gn_groups, gn_cg;
 };
 
 struct RowInfo {
@@ -99,6 +102,40 @@ __device__ __forceinline__ void glds16(const half_t* g, char* lds_wave_base) {
                                      (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
 }
 
+
+// GroupNorm records (K, sum(x - K), sum((x - K)^2)) of one 16-row x 160-column slab of the stored fp16 output, read back from LDS
+// (row stride `ld` halves): one record per channel group of `cg` channels (cg divides 40), K = the record's first element.  Lane
+// (r = lane & 15, q = lane >> 4) sums row r of the groups of column quarter q in ascending channel order; the 16 rows are then
+// combined by an xor butterfly (every lane ends with the same bits).  The order depends on nothing but the position inside the
+// record, and both tile kernels call this one function: a record's bits do not depend on the tile origin or the kernel family.
+// dst: the record of (this 16-row fragment, first channel group of the slab).  Vector stores only.
+__device__ __forceinline__ void gn_slab_records(const half_t* slab, int ld, int cg, int lane, float* dst) {
+    const int r = lane & 15, q = lane >> 4;
+    const int ngq = 40 / cg;  // channel groups per column quarter
+    for (int gi = 0; gi < ngq; ++gi) {
+        const int gl = q * ngq + gi;
+        const half_t* g0 = slab + gl * cg;
+        const float K = (float)g0[0];
+        const half_t* x = g0 + r * ld;
+        float s = 0.f, qq = 0.f;
+        for (int c = 0; c < cg; ++c) {
+            const float f = (float)x[c] - K;
+            s += f;
+            qq = fmaf(f, f, qq);
+        }
+#pragma unroll
+        for (int o = 1; o < 16; o <<= 1) {
+            s += __shfl_xor(s, o, 64);
+            qq += __shfl_xor(qq, o, 64);
+        }
+        if (r == 0) {
+            float* o = dst + gl * 3;
+            o[0] = K;
+            o[1] = s;
+            o[2] = qq;
+        }
+    }
+}
 
 // ---- weight-stationary kernel (gemm_ws.hip): launch plan + host entry points used by gemm.hip's dispatch ----
 struct WsPlan {

@@ -122,47 +122,15 @@ __device__ __forceinline__ float gn_silu(float x) {  // x * sigmoid(x) on raw v_
     return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * x));
 }
 
+// The streaming part shared by the apply kernels: a thread owns ONE 16-byte channel vector and walks the rows of its block with U
+// row loads in flight; smean / srstd: the statistics of this block's statistics group (LDS).
 template <int U>
-__global__ __launch_bounds__(1024) void gn_apply_kernel(const half_t* __restrict__ X0, const half_t* __restrict__ X1, int C0,
-                                                        int C1, half_t* __restrict__ Y, const half_t* __restrict__ gamma,
-                                                        const half_t* __restrict__ beta, const float* __restrict__ pivot,
-                                                        int from_data, const float* __restrict__ partial, int nchunks, float inv_cnt,
-                                                        float eps, int rows_per_group, int G, int silu, int rpb,
-                                                        int rows_per_block) {
-    __shared__ float rs[256], rq[256], smean[64], srstd[64];
+__device__ __forceinline__ void gn_apply_rows(const half_t* __restrict__ X0, const half_t* __restrict__ X1, int C0, int C1,
+                                              half_t* __restrict__ Y, const half_t* __restrict__ gamma,
+                                              const half_t* __restrict__ beta, const float* smean, const float* srstd,
+                                              int rows_per_group, int G, int silu, int rpb, int rows_per_block) {
     const int C = C0 + C1, V = C >> 3, cpg = C / G;
     const int sg = blockIdx.y, tid = threadIdx.x;
-    {   // statistics of this stat group: same order of additions in every block -> identical in all of them
-        const int nt = blockDim.x < 256 ? blockDim.x : 256;
-        const int parts = nt / G;  // G <= 64 <= blockDim.x
-        const int g = tid % G, part = tid / G;
-        // this group's pivot, loaded before the chunk sums so that its latency overlaps theirs
-        const float kpiv = tid < G ? gn_pivot(X0, X1, C0, C1, pivot, from_data, sg, rows_per_group, G, tid) : 0.f;
-        if (tid < 256) {
-            float as = 0.f, aq = 0.f;
-            if (part < parts)
-                for (int c = part; c < nchunks; c += parts) {
-                    const float* src = partial + (((size_t)sg * nchunks + c) * G + g) * 2;
-                    as += src[0];
-                    aq += src[1];
-                }
-            rs[tid] = as;
-            rq[tid] = aq;
-        }
-        __syncthreads();
-        if (tid < G) {
-            float s = 0.f, q = 0.f;
-            for (int p2 = 0; p2 < parts; ++p2) {
-                s += rs[p2 * G + tid];
-                q += rq[p2 * G + tid];
-            }
-            const float m = s * inv_cnt;  // mean - pivot
-            const float var = fmaxf(q * inv_cnt - m * m, 0.f);
-            smean[tid] = kpiv + m;
-            srstd[tid] = rsqrtf(var + eps);
-        }
-        __syncthreads();
-    }
     const int rl = tid / V, v = tid - rl * V;
     if (rl >= rpb) return;
     const int c0 = v * 8;
@@ -207,6 +175,125 @@ __global__ __launch_bounds__(1024) void gn_apply_kernel(const half_t* __restrict
     for (; r < r_end; r += rpb) *(h8*)(dst + (size_t)r * C) = norm8(*(const h8*)(src + (size_t)r * ld));
 }
 
+template <int U>
+__global__ __launch_bounds__(1024) void gn_apply_kernel(const half_t* __restrict__ X0, const half_t* __restrict__ X1, int C0,
+                                                        int C1, half_t* __restrict__ Y, const half_t* __restrict__ gamma,
+                                                        const half_t* __restrict__ beta, const float* __restrict__ pivot,
+                                                        int from_data, const float* __restrict__ partial, int nchunks, float inv_cnt,
+                                                        float eps, int rows_per_group, int G, int silu, int rpb,
+                                                        int rows_per_block) {
+    __shared__ float rs[256], rq[256], smean[64], srstd[64];
+    const int C = C0 + C1, V = C >> 3, cpg = C / G;
+    const int sg = blockIdx.y, tid = threadIdx.x;
+    {   // statistics of this stat group: same order of additions in every block -> identical in all of them
+        const int nt = blockDim.x < 256 ? blockDim.x : 256;
+        const int parts = nt / G;  // G <= 64 <= blockDim.x
+        const int g = tid % G, part = tid / G;
+        // this group's pivot, loaded before the chunk sums so that its latency overlaps theirs
+        const float kpiv = tid < G ? gn_pivot(X0, X1, C0, C1, pivot, from_data, sg, rows_per_group, G, tid) : 0.f;
+        if (tid < 256) {
+            float as = 0.f, aq = 0.f;
+            if (part < parts)
+                for (int c = part; c < nchunks; c += parts) {
+                    const float* src = partial + (((size_t)sg * nchunks + c) * G + g) * 2;
+                    as += src[0];
+                    aq += src[1];
+                }
+            rs[tid] = as;
+            rq[tid] = aq;
+        }
+        __syncthreads();
+        if (tid < G) {
+            float s = 0.f, q = 0.f;
+            for (int p2 = 0; p2 < parts; ++p2) {
+                s += rs[p2 * G + tid];
+                q += rq[p2 * G + tid];
+            }
+            const float m = s * inv_cnt;  // mean - pivot
+            const float var = fmaxf(q * inv_cnt - m * m, 0.f);
+            smean[tid] = kpiv + m;
+            srstd[tid] = rsqrtf(var + eps);
+        }
+        __syncthreads();
+    }
+    gn_apply_rows<U>(X0, X1, C0, C1, Y, gamma, beta, smean, srstd, rows_per_group, G, silu, rpb, rows_per_block);
+}
+
+// GroupNorm from the records a producing GEMM wrote (AnyV2VGemmDesc.gn_stats): gn_apply_kernel with another statistics prologue.
+// rec: [statistics group][record][G][3] = (K_i, s_i, q_i), nrec records per (statistics group, channel group), each over n_rec
+// values except the last (n_last).  Every block moves them to the pivot of record 0 exactly -- s += s_i + n_i d,
+// q += q_i + 2 d s_i + n_i d^2, d = K_i - K (a difference of two fp16 values: exact) -- thread (part, g) taking records part,
+// part + parts, ... in ascending order, then the parts in ascending order: the same additions in every block.
+template <int U>
+__global__ __launch_bounds__(1024) void gn_apply_stats_kernel(const half_t* __restrict__ X, half_t* __restrict__ Y,
+                                                              const half_t* __restrict__ gamma, const half_t* __restrict__ beta,
+                                                              const float* __restrict__ rec, int nrec, float n_rec, float n_last,
+                                                              float inv_cnt, float eps, int C, int rows_per_group, int G, int silu,
+                                                              int rpb, int rows_per_block) {
+    __shared__ float rs[256], rq[256], smean[64], srstd[64];
+    const int sg = blockIdx.y, tid = threadIdx.x;
+    {
+        const int nt = blockDim.x < 256 ? blockDim.x : 256;
+        const int parts = nt / G;  // G <= 64 <= blockDim.x
+        const int g = tid % G, part = tid / G;
+        const float* base = rec + ((size_t)sg * nrec * G + g) * 3;
+        const float kpiv = base[0];
+        if (tid < 256) {
+            float as = 0.f, aq = 0.f;
+            if (part < parts)
+                for (int c = part; c < nrec; c += parts) {
+                    const float* src = base + (size_t)c * G * 3;
+                    const float n = c + 1 == nrec ? n_last : n_rec;
+                    const float d = src[0] - kpiv, si = src[1], qi = src[2];
+                    const float nd = n * d;
+                    as += si + nd;
+                    aq += qi + (2.f * d * si + nd * d);
+                }
+            rs[tid] = as;
+            rq[tid] = aq;
+        }
+        __syncthreads();
+        if (tid < G) {
+            float s = 0.f, q = 0.f;
+            for (int p2 = 0; p2 < parts; ++p2) {
+                s += rs[p2 * G + tid];
+                q += rq[p2 * G + tid];
+            }
+            const float m = s * inv_cnt;  // mean - pivot
+            const float var = fmaxf(q * inv_cnt - m * m, 0.f);
+            smean[tid] = kpiv + m;
+            srstd[tid] = rsqrtf(var + eps);
+        }
+        __syncthreads();
+    }
+    // (X twice: the second source is never read with C1 = 0, and a literal nullptr here crashes hipcc 7.2's inliner)
+    gn_apply_rows<U>(X, X, C, 0, Y, gamma, beta, smean, srstd, rows_per_group, G, silu, rpb, rows_per_block);
+}
+
+// Long statistics groups (the 5-D norms: 16 frames x 4096 pixels = 4096 records per channel group): runs of `run` consecutive
+// records are first moved to the pivot of the run's first record and written as one record each, so that the apply blocks fold at
+// most GN_MAX_CHUNKS of them.  One thread per (statistics group, run, channel group), ascending order.
+__global__ void gn_fold_records_kernel(const float* __restrict__ rec, float* __restrict__ out, int nrec, int run, int nruns, int G,
+                                       float n_rec) {
+    const int sg = blockIdx.y, j = blockIdx.x, g = threadIdx.x;
+    if (g >= G) return;
+    const float* base = rec + (((size_t)sg * nrec + (size_t)j * run) * G + g) * 3;
+    int cnt = nrec - j * run;
+    if (cnt > run) cnt = run;
+    const float kpiv = base[0];
+    float as = 0.f, aq = 0.f;
+    for (int c = 0; c < cnt; ++c) {
+        const float* src = base + (size_t)c * G * 3;
+        const float d = src[0] - kpiv, si = src[1], qi = src[2];
+        const float nd = n_rec * d;
+        as += si + nd;
+        aq += qi + (2.f * d * si + nd * d);
+    }
+    float* o = out + (((size_t)sg * nruns + j) * G + g) * 3;
+    o[0] = kpiv;
+    o[1] = as;
+    o[2] = aq;
+}
 extern "C" int64_t anyv2v_groupnorm_scratch_floats(int32_t M, int32_t rows_per_group, int32_t G) {
     const int64_t nsg = rows_per_group > 0 ? M / rows_per_group : 0;
     return nsg * G * 2 * (int64_t)(1 + GN_MAX_CHUNKS);
@@ -309,6 +396,44 @@ extern "C" int anyv2v_groupnorm_f16(const void* X0, const void* X1, int32_t C0, 
     if (int rc = gn_plan(pl, X0, X1, C0, C1, M, rows_per_group, G)) return rc;
     if (int rc = gn_partial(pl, X0, X1, C0, C1, nullptr, 1, stats, rows_per_group, G, (hipStream_t)stream)) return rc;
     return gn_apply(pl, X0, X1, C0, C1, Y, gamma, beta, nullptr, 1, stats, rows_per_group, G, eps, silu, 1, (hipStream_t)stream);
+}
+
+extern "C" int64_t anyv2v_groupnorm_stats_floats(int32_t M, int32_t rows_per_group, int32_t G) {
+    if (M <= 0 || rows_per_group <= 0 || G <= 0 || rows_per_group % 16 != 0 || M % rows_per_group != 0) return 0;
+    return (int64_t)3 * (M / 16) * G + (int64_t)3 * (M / rows_per_group) * GN_MAX_CHUNKS * G;
+}
+
+extern "C" int anyv2v_groupnorm_apply_stats_f16(const void* X, void* Y, const void* gamma, const void* beta, float* stats,
+                                                const int32_t* sizes, float eps, int32_t silu, void* stream) {
+    AV_CHECK(X && Y && gamma && beta && stats && sizes, "groupnorm_apply_stats: null pointer");
+    const int32_t M = sizes[0], C = sizes[1], rows_per_group = sizes[2], G = sizes[3];
+    GnPlan pl;
+    if (int rc = gn_plan(pl, X, nullptr, C, 0, M, rows_per_group, G)) return rc;
+    AV_CHECK(av_aligned16(Y) && av_aligned16(gamma) && av_aligned16(beta), "groupnorm: pointers must be 16-byte aligned");
+    AV_CHECK(rows_per_group % 16 == 0, "groupnorm_apply_stats: rows_per_group must be a multiple of 16 (%d)", rows_per_group);
+    AV_CHECK((int64_t)sizes[4] >= anyv2v_groupnorm_stats_floats(M, rows_per_group, G),
+             "groupnorm_apply_stats: stats holds %d floats, needs anyv2v_groupnorm_stats_floats() = %lld", sizes[4],
+             (long long)anyv2v_groupnorm_stats_floats(M, rows_per_group, G));
+    const int cpg = C / G;
+    int nrec = rows_per_group / 16;
+    float n_rec = 16.f * (float)cpg, n_last = n_rec;
+    const float* rec = stats;
+    hipStream_t s = (hipStream_t)stream;
+    if (nrec > GN_MAX_CHUNKS) {   // fold runs of records first, into the tail of `stats`
+        const int run = (nrec + GN_MAX_CHUNKS - 1) / GN_MAX_CHUNKS, nruns = (nrec + run - 1) / run;
+        float* folded = stats + (size_t)3 * (M / 16) * G;
+        hipLaunchKernelGGL(gn_fold_records_kernel, dim3(nruns, pl.nsg), dim3(64), 0, s, rec, folded, nrec, run, nruns, G, n_rec);
+        if (int rc = av_launch_status("groupnorm<fold records>")) return rc;
+        n_last = n_rec * (float)(nrec - (nruns - 1) * run);
+        n_rec *= (float)run;
+        nrec = nruns;
+        rec = folded;
+    }
+    const float inv_cnt = 1.0f / ((float)rows_per_group * (float)cpg);
+    hipLaunchKernelGGL(gn_apply_stats_kernel<4>, dim3((unsigned)pl.bps, (unsigned)pl.nsg), dim3(pl.threads), 0, s, (const half_t*)X,
+                       (half_t*)Y, (const half_t*)gamma, (const half_t*)beta, rec, nrec, n_rec, n_last, inv_cnt, eps, C,
+                       rows_per_group, G, silu, pl.rpb, pl.rows_block);
+    return av_launch_status("groupnorm<from records>");
 }
 
 // Sharded GroupNorm (a clip whose frames or pixels are split over `shards` ranks, every rank holding the same local

@@ -20,6 +20,15 @@ GEMM_FLAGS = int(os.environ.get("ANYV2V_GEMM_FLAGS", "0"))  # bit2 (4): no persi
 USE_GLDS = os.environ.get("ANYV2V_GLDS", "1") == "1"   # LDS-DMA (global_load_lds) staging variant of the GEMM
 
 
+def _parse_switch(value: Optional[str]) -> bool:
+    return (value or "0").strip() == "1"
+
+
+# A/B switch, off by default: GroupNorm statistics from the producing GEMM's epilogue (gemm(..., gn=...) + groupnorm_from_stats)
+# for conv1 -> norm2 of ResnetBlock2D and conv i -> norm i + 1 of TemporalConvLayer, where the library's query says the plan can
+GN_EPILOGUE = _parse_switch(os.environ.get("ANYV2V_GN_EPILOGUE"))
+
+
 def _stream() -> int:
     return torch.cuda.current_stream().cuda_stream
 
@@ -67,8 +76,13 @@ def _workspace(device) -> torch.Tensor:
 
 def gemm(a0: torch.Tensor, w: torch.Tensor, *, a1: Optional[torch.Tensor] = None, bias=None, rowvec=None,
          rowvec_div: int = 0, residual=None, act: int = ACT_NONE, out: Optional[torch.Tensor] = None,
-         mode: int = MODE_LINEAR, conv=None, temporal=None, M: Optional[int] = None, naive: bool = False, ln=None):
+         mode: int = MODE_LINEAR, conv=None, temporal=None, M: Optional[int] = None, naive: bool = False, ln=None, gn=None,
+         _query: bool = False):
     """out[M, N'] = epilogue(gather(A) @ W^T).  ``w`` is [N, taps*K] packed (see anyv2v_hip.h).
+
+    ``gn`` = (stats fp32, rows_per_group, groups): the launch also writes the GroupNorm records of its stored output into ``stats``
+    for ``groupnorm_from_stats`` (``gn_stats_floats(M, rows_per_group, groups)`` floats).  Only where ``gemm_gn_stats_floats`` --
+    same arguments -- answers > 0; anywhere else the launch is an error, not a fallback.
 
     ``ln`` = (c1 fp32 [N], eps): LayerNorm folded into the projection -- ``a0`` holds the un-normalised rows, ``w`` / ``bias`` the
     gamma- / beta-folded weights (``ln_fold``); only shapes ``ln_gemm_supported`` accepts.
@@ -91,7 +105,9 @@ def gemm(a0: torch.Tensor, w: torch.Tensor, *, a1: Optional[torch.Tensor] = None
     if M is None:
         M = a0.shape[0]
     n_out = N // 2 if act == ACT_GEGLU else N
-    if act == ACT_F32OUT:  # raw fp32 accumulator (+bias) -> float32 matrix
+    if _query and out is None:
+        pass   # the query plans without an output buffer (fresh allocations are 16-byte aligned)
+    elif act == ACT_F32OUT:  # raw fp32 accumulator (+bias) -> float32 matrix
         if out is None:
             out = torch.empty((M, n_out), dtype=torch.float32, device=a0.device)
         assert out.dim() == 2 and out.stride(1) == 1 and out.dtype == torch.float32 and out.is_cuda
@@ -100,14 +116,14 @@ def gemm(a0: torch.Tensor, w: torch.Tensor, *, a1: Optional[torch.Tensor] = None
         if out is None:
             out = torch.empty((M, n_out), dtype=torch.float16, device=a0.device)
         _rowmajor(out, "C")
-    assert out.shape[0] >= M and out.shape[1] >= n_out
+    assert out is None or (out.shape[0] >= M and out.shape[1] >= n_out)
     d = GemmDesc()
     d.A0, d.A1, d.W, d.C = _p(a0), _p(a1), _p(w), _p(out)
     d.bias, d.rowvec, d.R = _p(bias), _p(rowvec), _p(residual)
     d.M, d.N, d.C0, d.C1 = M, N, C0, C1
     d.lda0 = a0.stride(0)
     d.lda1 = a1.stride(0) if a1 is not None else 0
-    d.ldc = out.stride(0)
+    d.ldc = out.stride(0) if out is not None else n_out
     d.ldr = residual.stride(0) if residual is not None else 0
     d.ldrv = rowvec.stride(0) if rowvec is not None else 0
     d.rowvec_div = rowvec_div
@@ -125,7 +141,51 @@ def gemm(a0: torch.Tensor, w: torch.Tensor, *, a1: Optional[torch.Tensor] = None
         d.ln_c1, d.ln_eps = _p(c1), float(eps)
     ws = _workspace(a0.device)
     d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel() * 4
+    if gn is not None:
+        stats, rows_per_group, groups = gn
+        d.gn_rows_per_group, d.gn_groups = int(rows_per_group), int(groups)
+        if stats is not None:
+            assert stats.dtype == torch.float32 and stats.is_cuda and stats.is_contiguous()
+            d.gn_stats, d.gn_stats_floats = stats.data_ptr(), stats.numel()
+    if _query:
+        return int(lib.anyv2v_gemm_gn_stats_floats(C.byref(d)))
     _lib.check(lib.anyv2v_gemm_f16(C.byref(d), _stream()), "anyv2v_gemm_f16")
+    return out
+
+
+def gemm_gn_stats_floats(a0: torch.Tensor, w: torch.Tensor, *, rows_per_group: int, groups: int = 32, **kw) -> int:
+    """Floats of records ``gemm(a0, w, gn=(stats, rows_per_group, groups), **kw)`` would write, or 0 when the plan that launch gets
+    cannot emit them (``anyv2v_gemm_gn_stats_floats``: split-K, naive, GEGLU, ...).  Same arguments as the launch, the batch hint
+    in force included; launches nothing, so a host can choose before a graph capture."""
+    return gemm(a0, w, gn=(None, rows_per_group, groups), _query=True, **kw)
+
+
+def gn_launches(reset: bool = True) -> int:
+    """GEMM launches that emitted GroupNorm records since the last reset (counted at enqueue time; for tests)."""
+    return int(_lib.load().anyv2v_gemm_gn_launches(int(reset)))
+
+
+def gn_stats_floats(M: int, rows_per_group: int, groups: int = 32) -> int:
+    """Size of the record buffer shared by ``gemm(gn=...)`` and ``groupnorm_from_stats`` (== anyv2v_groupnorm_stats_floats): one
+    3-float record per (16 rows, channel group), plus room to pre-fold statistics groups of more than 256 records."""
+    return int(_lib.load().anyv2v_groupnorm_stats_floats(int(M), int(rows_per_group), int(groups)))
+
+
+def groupnorm_from_stats(x: torch.Tensor, gamma, beta, stats: torch.Tensor, rows_per_group: int, *, groups: int = 32,
+                         eps: float = 1e-5, silu: bool = False, out=None):
+    """GroupNorm (+ SiLU) of ``x`` from the records the GEMM that produced ``x`` wrote into ``stats``: no statistics pass over
+    ``x``.  Single source."""
+    lib = _lib.load()
+    _rowmajor(x, "X")
+    assert x.is_contiguous()
+    M, Cc = x.shape
+    if out is None:
+        out = torch.empty((M, Cc), dtype=torch.float16, device=x.device)
+    assert out.is_contiguous()
+    assert stats.dtype == torch.float32 and stats.is_contiguous() and stats.numel() >= gn_stats_floats(M, rows_per_group, groups) > 0
+    sizes = (C.c_int32 * 5)(M, Cc, rows_per_group, groups, min(stats.numel(), 2 ** 31 - 1))
+    _lib.check(lib.anyv2v_groupnorm_apply_stats_f16(_p(x), _p(out), _p(gamma), _p(beta), _p(stats), sizes, eps, int(silu),
+                                                    _stream()), "anyv2v_groupnorm_apply_stats_f16")
     return out
 
 

@@ -139,11 +139,16 @@ class Conv2d(nn.Module):
         return y.view(n, Ho, Wo, self.cout).permute(0, 3, 1, 2)
 
     def tokens(self, x, H, W, *, x1=None, up=False, act=ACT_NONE, rowvec=None, rowvec_div=0, residual=None, out=None,
-               asym=False):
+               asym=False, gn=None, _launch=None):
         """x: [N*H*W, Cin] tokens -> [N*Ho*Wo, Cout].  ``asym``: zero padding only after the last row / column
-        (``F.pad(x, (0, 1, 0, 1))`` + padding-0 conv of the AutoencoderKL encoder's Downsample2D)."""
+        (``F.pad(x, (0, 1, 0, 1))`` + padding-0 conv of the AutoencoderKL encoder's Downsample2D).  ``gn`` = (records,
+        rows_per_group, groups): also write the consumer GroupNorm's records (``ops.gemm``)."""
+        if _launch is not None:   # tokens_gn_floats: the same descriptor, handed to the query instead of the launch
+            launch, kw = _launch, {}
+        else:
+            launch, kw = ops.gemm, ({"out": out} if gn is None else {"out": out, "gn": gn})
         if self.k == 1:
-            return ops.gemm(x, self._w, a1=x1, bias=self.bias, act=act, residual=residual, out=out)
+            return launch(x, self._w, a1=x1, bias=self.bias, act=act, residual=residual, **kw)
         if up:
             Ho, Wo = 2 * H, 2 * W
         elif asym:
@@ -151,9 +156,32 @@ class Conv2d(nn.Module):
         else:
             Ho, Wo = (H + 2 - 3) // self.stride + 1, (W + 2 - 3) // self.stride + 1
         n_img = x.shape[0] // (H * W)
-        return ops.gemm(x, self._w, a1=x1, bias=self.bias, act=act, rowvec=rowvec, rowvec_div=rowvec_div,
-                        residual=residual, mode=MODE_CONV2D, conv=(H, W, Ho, Wo, self.stride, int(up), int(asym)),
-                        M=n_img * Ho * Wo, out=out)
+        return launch(x, self._w, a1=x1, bias=self.bias, act=act, rowvec=rowvec, rowvec_div=rowvec_div,
+                      residual=residual, mode=MODE_CONV2D, conv=(H, W, Ho, Wo, self.stride, int(up), int(asym)),
+                      M=n_img * Ho * Wo, **kw)
+
+    def tokens_gn_floats(self, x, H, W, rows_per_group, groups, **kw):
+        """Floats of GroupNorm records ``tokens(x, H, W, gn=(records, rows_per_group, groups), **kw)`` would write, 0 when that
+        launch's plan cannot emit them (``ops.gemm_gn_stats_floats``); launches nothing."""
+        return self.tokens(x, H, W, _launch=lambda *a, **k: ops.gemm_gn_stats_floats(*a, rows_per_group=rows_per_group, groups=groups, **k),
+                           **kw)
+
+
+def _gn_records(ctx, M, rows_per_group, groups):
+    """Record buffer for GroupNorm statistics from a GEMM epilogue (``ANYV2V_GN_EPILOGUE=1``), or None: switch off, a
+    frame-parallel clip (its norms are sharded), or a statistics group that is not a whole number of 16-row records.  One buffer
+    per step engine (``ctx``), sized in ``_prepare_clip``; a context without one gets it on its first, eager forward -- never
+    inside a graph capture."""
+    if not ops.GN_EPILOGUE or getattr(ctx, "fp", None) is not None:
+        return None
+    need = ops.gn_stats_floats(M, rows_per_group, groups)
+    if need == 0:
+        return None
+    rec = getattr(ctx, "gn_rec", None)
+    if rec is None or rec.numel() < need:
+        assert not torch.cuda.is_current_stream_capturing(), "GroupNorm record buffer must exist before a graph capture"
+        rec = ctx.gn_rec = torch.empty(need, dtype=torch.float32, device="cuda")
+    return rec
 
 
 class Conv3dTemporal(nn.Module):
@@ -637,8 +665,14 @@ class ResnetBlock2D(nn.Module):
         h = ops.groupnorm(a0, self.norm1.weight, self.norm1.bias, ctx.stats, rpg, x1=a1, groups=g, eps=self.norm1.eps,
                           silu=True)
         tv = ctx.temb_all[:, self._temb_col:self._temb_col + self.out_channels]
-        h = self.conv1.tokens(h, H, W, rowvec=tv, rowvec_div=ctx.F * HW)
-        h = ops.groupnorm(h, self.norm2.weight, self.norm2.bias, ctx.stats, rpg, groups=g, eps=self.norm2.eps, silu=True)
+        rec = _gn_records(ctx, Ts, rpg, g)
+        if rec is not None and self.conv1.tokens_gn_floats(h, H, W, rpg, g, rowvec=tv, rowvec_div=ctx.F * HW) > 0:
+            # conv1's epilogue writes norm2's statistics: no partial pass over its output
+            h = self.conv1.tokens(h, H, W, rowvec=tv, rowvec_div=ctx.F * HW, gn=(rec, rpg, g))
+            h = ops.groupnorm_from_stats(h, self.norm2.weight, self.norm2.bias, rec, rpg, groups=g, eps=self.norm2.eps, silu=True)
+        else:
+            h = self.conv1.tokens(h, H, W, rowvec=tv, rowvec_div=ctx.F * HW)
+            h = ops.groupnorm(h, self.norm2.weight, self.norm2.bias, ctx.stats, rpg, groups=g, eps=self.norm2.eps, silu=True)
         if self.conv_shortcut is not None:
             res = self.conv_shortcut.tokens(x0, H, W, x1=x1)
         else:
@@ -669,12 +703,27 @@ class TemporalConvLayer(nn.Module):
     def _run(self, ctx, x, HW, shard):
         h = x
         seqs = (self.conv1, self.conv2, self.conv3, self.conv4)
+        rpg = ctx.F * HW
+        rec = None   # records of h, written by the conv that produced it (ANYV2V_GN_EPILOGUE=1: conv i -> norm i + 1)
         for i, seq in enumerate(seqs):
             gn, conv = seq[0], seq[-1]
-            h = ops.groupnorm(h, gn.weight, gn.bias, ctx.stats, ctx.F * HW, groups=gn.num_groups, eps=gn.eps, silu=True,
-                              shard=shard)
-            h = ops.gemm(h, conv._w, bias=conv.bias, mode=MODE_TEMPORAL, temporal=(ctx.F, HW),
-                         residual=x if i == 3 else None)
+            if rec is not None:
+                h = ops.groupnorm_from_stats(h, gn.weight, gn.bias, rec, rpg, groups=gn.num_groups, eps=gn.eps, silu=True)
+            else:
+                h = ops.groupnorm(h, gn.weight, gn.bias, ctx.stats, rpg, groups=gn.num_groups, eps=gn.eps, silu=True,
+                                  shard=shard)
+            rec = None
+            if i < 3 and shard is None:
+                g_next = seqs[i + 1][0].num_groups
+                rec = _gn_records(ctx, h.shape[0], rpg, g_next)
+                if rec is not None and ops.gemm_gn_stats_floats(h, conv._w, bias=conv.bias, mode=MODE_TEMPORAL, temporal=(ctx.F, HW),
+                                                                rows_per_group=rpg, groups=g_next) == 0:
+                    rec = None
+            if rec is not None:
+                h = ops.gemm(h, conv._w, bias=conv.bias, mode=MODE_TEMPORAL, temporal=(ctx.F, HW), gn=(rec, rpg, g_next))
+            else:
+                h = ops.gemm(h, conv._w, bias=conv.bias, mode=MODE_TEMPORAL, temporal=(ctx.F, HW),
+                             residual=x if i == 3 else None)
         return h
 
 
@@ -945,6 +994,10 @@ class I2VGenXLUNet(nn.Module):
         HW = H * W
         T = B * F * HW
         ctx.stats = torch.empty(ops.gn_scratch_floats(B * F, 1, cfg.norm_num_groups), dtype=torch.float32, device=dev)
+        if ops.GN_EPILOGUE and fp is None:   # GroupNorm records of the largest launch of this engine (every level, 4-D and 5-D norms)
+            g = cfg.norm_num_groups
+            need = max(ops.gn_stats_floats(T, HW, g), ops.gn_stats_floats(T, F * HW, g))
+            ctx.gn_rec = torch.empty(need, dtype=torch.float32, device=dev) if need > 0 else None
         ctx.t_buf = torch.zeros(B, dtype=torch.float32, device=dev)
         boc0, cd = cfg.block_out_channels[0], cfg.cross_attention_dim
         # fps embedding

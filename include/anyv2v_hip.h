@@ -89,9 +89,33 @@ typedef struct AnyV2VGemmDesc {
     const float* ln_c1;
     float ln_eps;
     int32_t reserved0;
+    /* GroupNorm statistics from the epilogue (ABI 105; NULL / 0 = off).  With gn_stats != NULL the launch also writes partial
+     * GroupNorm statistics of the STORED fp16 output (after bias, rowvec, activation, residual and rounding) for the consumer
+     * GroupNorm(gn_groups) over statistics groups of gn_rows_per_group consecutive rows: one record of 3 floats per (16 consecutive
+     * rows, channel group),
+     *     gn_stats[((m / 16) * gn_groups + g) * 3 + {0, 1, 2}] = (K, sum(x - K), sum((x - K)^2)),   K = C[16 (m / 16)][g * N / gn_groups]
+     * over the record's 16 x (N / gn_groups) values -- each record about its own first element, summed in an order that depends only
+     * on the position inside the record (not on the tile, the kernel family or the batch hint; no atomics), so a [negative, editing]
+     * launch writes bit for bit the records the three-branch launch writes for those rows.  gn_stats_floats: capacity of gn_stats, at
+     * least anyv2v_gemm_gn_stats_floats(d).  A launch whose plan cannot emit statistics fails with ANYV2V_EINVAL -- ask first. */
+    float* gn_stats;
+    int64_t gn_stats_floats;
+    int32_t gn_rows_per_group;
+    int32_t gn_groups;
 } AnyV2VGemmDesc;
 
 int anyv2v_gemm_f16(const AnyV2VGemmDesc* d, void* stream);
+/* Floats of gn_stats the launch described by `d` would write (3 * (M / 16) * gn_groups), or 0 when the plan this descriptor gets
+ * cannot emit statistics: split-K plans, the naive kernel, the weight-stationary / LayerNorm-fold kernel, GEGLU / fp32-out
+ * epilogues, the off-by-default kernels flags bits 17 / 21 / 26-28 select, N not a multiple of 160, N / gn_groups not a divisor of
+ * 40 (a channel group must not straddle a 160-column wave tile), M or gn_rows_per_group not a multiple of 16.  Decides exactly as
+ * anyv2v_gemm_f16 will (same flags, workspace, alignment and batch hint; gn_stats and C may still be NULL), launches nothing. */
+int64_t anyv2v_gemm_gn_stats_floats(const AnyV2VGemmDesc* d);
+/* Launches that emitted statistics since the counter was last reset (reset != 0: return the count, then zero it).  Host-side,
+ * counted at enqueue time, before the launch status is known (a graph replay does not count; a launch the runtime rejects
+ * does).  One process-global integer, NOT thread-safe, like the batch hint.  For tests: a forced path must not pass because it
+ * fell back. */
+int64_t anyv2v_gemm_gn_launches(int32_t reset);
 
 /* ---- fused feed-forward ----------------------------------------------------------------------
  * Y = GEGLU(X W1^T + b1) W2^T + b2 (+ R): the FeedForward of BasicTransformerBlock (diffusers-0.26.3 `FeedForward(dim,
@@ -131,6 +155,16 @@ int64_t anyv2v_groupnorm_scratch_floats(int32_t M, int32_t rows_per_group, int32
 int anyv2v_groupnorm_f16(const void* X0, const void* X1, int32_t C0, int32_t C1, void* Y, const void* gamma,
                          const void* beta, float* stats, int32_t M, int32_t rows_per_group, int32_t G, float eps,
                          int32_t silu, void* stream);
+/* The same from the records a producing anyv2v_gemm_f16 launch wrote (AnyV2VGemmDesc.gn_stats): normalise + affine (+ SiLU), no
+ * partial pass over X.  sizes = {M, C, rows_per_group, G, capacity of stats in floats}; single source (the concat form stays on
+ * anyv2v_groupnorm_f16); rows_per_group a multiple of 16.  `stats` holds anyv2v_groupnorm_stats_floats(M, rows_per_group, G)
+ * floats: the 3 * (M / 16) * G the GEMM writes, then room in which statistics groups of more than 256 records (the 5-D norms) are
+ * first folded in runs (one more small launch).  Records are moved to one pivot per (statistics group, channel group), the first
+ * record's, exactly:  s += s_i + n_i d,  q += q_i + 2 d s_i + n_i d^2,  d = K_i - K,  in a fixed order that is the same in every
+ * block and depends on rows_per_group only: two runs are bit-equal, and so are a batch-hinted launch and the launch it stands for. */
+int64_t anyv2v_groupnorm_stats_floats(int32_t M, int32_t rows_per_group, int32_t G);
+int anyv2v_groupnorm_apply_stats_f16(const void* X, void* Y, const void* gamma, const void* beta, float* stats,
+                                     const int32_t* sizes, float eps, int32_t silu, void* stream);
 
 /* Sharded 5-D GroupNorm, for a clip whose frames / pixels are split over `shards` ranks (the 128-frame mode,
  * gradio_demo.py:129-131; every rank holds the same local shape).  The statistics are sums about one pivot per
@@ -295,8 +329,11 @@ const char* anyv2v_last_error(void);
  * descriptor (new fields are appended with 0 = "off").  101: AnyV2VGemmDesc grew ln_c1 / ln_eps / reserved0 (round 3), flags
  * bits 13-16 select the persistent kernel's tile order (round 4).  102: anyv2v_ff_geglu_f16.  103: anyv2v_guided_step_f16, anyv2v_guided_step_noise_f16.
  * 104: GroupNorm sums about a pivot; pivoted sharded entry points anyv2v_groupnorm_pivot_f16 / _partial_pivot_f16 /
- * _apply_pivot_f16 (the earlier pair is unchanged). */
-#define ANYV2V_ABI_VERSION 104
+ * _apply_pivot_f16 (the earlier pair is unchanged).  105: AnyV2VGemmDesc grew gn_stats / gn_stats_floats / gn_rows_per_group /
+ * gn_groups (GroupNorm statistics from the GEMM epilogue), anyv2v_gemm_gn_stats_floats, anyv2v_gemm_gn_launches,
+ * anyv2v_groupnorm_stats_floats, anyv2v_groupnorm_apply_stats_f16; nothing earlier changed (a 104 caller that zero-initialises its descriptors, as required,
+ * must still be recompiled against this header because the structure grew). */
+#define ANYV2V_ABI_VERSION 105
 int anyv2v_version(void);
 /* MFMA / LDS layout self-test used by the gpu test-suite (returns 0 when the layouts the kernels assume hold) */
 int anyv2v_selftest(void* scratch, int64_t scratch_bytes, void* stream);
