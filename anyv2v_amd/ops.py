@@ -414,12 +414,14 @@ def tokens_to_ncfhw(x: torch.Tensor, B: int, Cc: int, F: int, H: int, W: int, co
     return out
 
 
-def adaptive_avgpool(x: torch.Tensor, N: int, Hi: int, Wi: int, Ho: int, Wo: int):
+def adaptive_avgpool(x: torch.Tensor, N: int, Hi: int, Wi: int, Ho: int, Wo: int, out=None):
     lib = _lib.load()
     _rowmajor(x, "X")
     assert x.is_contiguous()
     Cc = x.shape[1]
-    out = torch.empty((N * Ho * Wo, Cc), dtype=torch.float16, device=x.device)
+    if out is None:
+        out = torch.empty((N * Ho * Wo, Cc), dtype=torch.float16, device=x.device)
+    assert out.is_contiguous() and out.dtype == torch.float16 and tuple(out.shape) == (N * Ho * Wo, Cc)
     _lib.check(lib.anyv2v_adaptive_avgpool_f16(_p(x), _p(out), N, Hi, Wi, Ho, Wo, Cc, _stream()), "anyv2v_adaptive_avgpool_f16")
     return out
 

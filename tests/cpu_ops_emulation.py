@@ -179,7 +179,11 @@ def timestep_embedding(t_f32, dim, out=None):
     half = dim // 2
     fr = torch.exp(-math.log(10000.0) * torch.arange(half, dtype=torch.float32) / half)
     arg = t_f32.float()[:, None] * fr[None]
-    return _h(torch.cat([arg.cos(), arg.sin()], -1))
+    y = _h(torch.cat([arg.cos(), arg.sin()], -1))
+    if out is not None:
+        out.copy_(y)
+        return out
+    return y
 
 
 def ncfhw_to_tokens(x, out, col0=0):
@@ -196,10 +200,14 @@ def tokens_to_ncfhw(x, B, Cc, Fr, H, W, col0=0, out=None):
     return y
 
 
-def adaptive_avgpool(x, N, Hi, Wi, Ho, Wo):
+def adaptive_avgpool(x, N, Hi, Wi, Ho, Wo, out=None):
     C = x.shape[1]
     y = F.adaptive_avg_pool2d(x.float().view(N, Hi, Wi, C).permute(0, 3, 1, 2), (Ho, Wo))
-    return _h(y.permute(0, 2, 3, 1).reshape(N * Ho * Wo, C))
+    y = _h(y.permute(0, 2, 3, 1).reshape(N * Ho * Wo, C))
+    if out is not None:
+        out.copy_(y)
+        return out
+    return y
 
 
 def copy_cols(x, xcol0, y, ycol0, ncols):

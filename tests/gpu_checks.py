@@ -857,6 +857,140 @@ def _guard_intact(buf, M, guard):
     return bool((buf[:pad] == bits).all() and (buf[pad + M:] == bits).all())
 
 
+POISON16 = 0x7E5A       # fp16 NaN, the pattern of ``_guarded``
+POISON32 = 0x7FC5A5A5   # fp32 NaN
+
+
+def _framed(M, C, dtype=torch.float16, rows=64, cols=8, bits=None, device=None, aligned=True):
+    """``(buf, view, frame)``: ``view`` is an [M, C] window of one larger tensor ``buf`` (integer dtype of the same width) whose
+    every element outside the window holds the NaN bit pattern ``bits``: ``rows`` guard rows above and below, ``cols`` guard
+    columns on the left and at least as many on the right (the leading dimension is rounded up to a multiple of 8 elements).
+    With ``aligned`` the row pitch and the left guard are multiples of 16 bytes, so ``view`` starts 16-byte aligned and keeps
+    ``ld % 8 == 0``: a launch on it gets the plan the launch on a fresh contiguous tensor gets."""
+    item = torch.empty(0, dtype=dtype).element_size()
+    assert item in (2, 4), dtype
+    idt = torch.int16 if item == 2 else torch.int32
+    if bits is None:
+        bits = POISON16 if item == 2 else POISON32
+    ld = (2 * cols + C + 7) // 8 * 8
+    if aligned:
+        assert (cols * item) % 16 == 0 and (rows * ld * item) % 16 == 0
+    buf = torch.full((M + 2 * rows, ld), bits, dtype=idt, device=DEV if device is None else device)
+    return buf, buf.view(dtype)[rows:rows + M, cols:cols + C], (rows, cols, M, C, bits)
+
+
+def _frame_intact(buf, frame):
+    """Exact bit compare of everything outside the window (the four bands: above, below, left, right)."""
+    rows, cols, M, C, bits = frame
+    mid = buf[rows:rows + M]
+    return bool((buf[:rows] == bits).all() and (buf[rows + M:] == bits).all() and (mid[:, :cols] == bits).all()
+                and (mid[:, cols + C:] == bits).all())
+
+
+def _framed_like(t, flat=False, rows=64, cols=8, device=None, aligned=True):
+    """``t`` copied into a frame: a 2-D matrix into an [M, C] window (strided, for operands addressed with a leading dimension); with
+    ``flat`` or any other rank the elements stay contiguous, with ``rows`` x row pitch poison elements before and after (weights, 1-D
+    operands such as bias / gamma / ``ln_c1``, NCFHW latents)."""
+    device = t.device if device is None else device
+    if t.dim() == 2 and not flat:
+        buf, view, frame = _framed(t.shape[0], t.shape[1], t.dtype, rows, cols, device=device, aligned=aligned)
+        view.copy_(t)
+        return buf, view, frame
+    buf, view, frame = _framed(1, t.numel(), t.dtype, rows=1, cols=64, device=device)
+    view.copy_(t.reshape(1, -1))
+    return buf, view[0].view(t.shape), frame
+
+
+def _ld8(t):
+    """``t`` as a window of a zero matrix whose leading dimension is a multiple of 8 (what ``_framed`` gives the framed twin)."""
+    if t is None or t.dim() != 2 or t.shape[1] % 8 == 0:
+        return t
+    wide = torch.zeros(t.shape[0], (t.shape[1] + 7) // 8 * 8, dtype=t.dtype, device=t.device)
+    wide[:, :t.shape[1]] = t
+    return wide[:, :t.shape[1]]
+
+
+class _PlainOperands:
+    """Operands of the plain launch of an edge row: fresh tensors (ragged widths padded to ``ld % 8 == 0``)."""
+    framed = False
+
+    def inp(self, t, flat=False):
+        return t if (t is None or flat) else _ld8(t)
+
+    def out(self, M, C, dtype=torch.float16, init=None, cols=8):
+        ld = (C + 7) // 8 * 8 + (0 if cols % 8 == 0 else 16)
+        off = 0 if cols % 8 == 0 else cols
+        y = torch.zeros(M, ld, dtype=dtype, device=DEV)[:, off:off + C]
+        if init is not None:
+            y.copy_(init)
+        return y
+
+    def out_flat(self, shape, dtype=torch.float16):
+        return torch.zeros(shape, dtype=dtype, device=DEV)
+
+    def inout(self, t):
+        return t.clone()
+
+    def intact(self):
+        return True
+
+
+class _FramedOperands:
+    """Operands of the framed launch: every input and output inside a poisoned frame; ``intact()`` checks the frames of the outputs."""
+    framed = True
+
+    def __init__(self):
+        self.outs = []
+
+    def inp(self, t, flat=False):
+        return None if t is None else _framed_like(t, flat)[1]
+
+    def out(self, M, C, dtype=torch.float16, init=None, cols=8):
+        buf, view, frame = _framed(M, C, dtype, cols=cols, aligned=cols % 8 == 0)
+        self.outs.append((buf, frame))
+        if init is not None:
+            view.copy_(init)
+        return view
+
+    def out_flat(self, shape, dtype=torch.float16):
+        n = 1
+        for s in shape:
+            n *= s
+        buf, view, frame = _framed(1, n, dtype, rows=1, cols=64)
+        self.outs.append((buf, frame))
+        return view[0].view(shape)
+
+    def inout(self, t):
+        buf, view, frame = _framed_like(t, flat=not (t.dim() == 2))
+        self.outs.append((buf, frame))
+        return view
+
+    def intact(self):
+        return all(_frame_intact(buf, frame) for buf, frame in self.outs)
+
+
+def _edge_rows(name, run, ref, tol=KTOL):
+    """The three rows of one edge case.  ``run(f)`` launches with the operands ``f`` hands out (``f.inp`` / ``f.out`` / ...) and returns
+    the result; it runs once on plain tensors and once with every operand framed.  Rows: framed result vs ``ref`` (a tensor or a
+    function of the result) at ``tol``; framed == plain, bit for bit (the plan depends on shapes, flags and alignment only: a difference
+    means poison reached a stored value); the frames of the framed outputs intact."""
+    yp = run(_PlainOperands())
+    fr = _FramedOperands()
+    yf = run(fr)
+    torch.cuda.synchronize()
+    want = ref(yf) if callable(ref) else ref
+    same = bool(torch.equal(yf, yp))
+    intact = fr.intact()
+    return [_res(name + ": framed vs reference", yf, want, tol),
+            dict(name=name + ": framed == plain, bit for bit", err=0.0 if same else float((yf.float() - yp.float()).abs().nan_to_num(nan=float("inf")).max()),
+                 tol=0.0, ok=same),
+            dict(name=name + ": frames of the outputs intact", err=0.0 if intact else 1.0, tol=0.0, ok=intact)]
+
+
+def _skip_row(name, why):
+    return dict(name=f"{name}: SKIPPED ({why})", err=0.0, l2=0.0, tol=0.0, ok=True, skipped=True)
+
+
 def check_groupnorm_plan_edges():
     """The launch plan's edges: rows_per_group that is not a multiple of the rows per block or of the chunk size, the 256-chunk
     cap, the same tensor under ``batch_hint(3, 2)`` (another chunk count: within KTOL and bit-reproducible call to call),
@@ -2961,9 +3095,617 @@ def check_attention_bias_and_rotary_windows():
     return out
 
 
+# ------------------------------------------------------------------------------------------------ buffer edges: framed operands
+# Every case below runs twice with the same flags: on plain tensors and with ALL operands inside poisoned frames (``_edge_rows``).
+# The kernels read past the logical edge of an operand on purpose (clamped rows, W rows past N, key tails) and mask; the frames make
+# what they read there NaN and what they may not write checkable.  Every framed operand lies inside one allocation.
+def _gemm_edge(name, a0, w, ref, *, a1=None, bias=None, rowvec=None, rowvec_div=0, residual=None, act=0, M=None, ln=None, c_cols=8, **kw):
+    Mout = a0.shape[0] if M is None else M
+    n_out = w.shape[0] // 2 if act == ops.ACT_GEGLU else w.shape[0]
+    cdt = torch.float32 if act == ops.ACT_F32OUT else torch.float16
+
+    def run(f):
+        lnf = None if ln is None else (f.inp(ln[0], flat=True), ln[1])
+        return ops.gemm(f.inp(a0), f.inp(w, flat=True), a1=f.inp(a1), bias=f.inp(bias), rowvec=f.inp(rowvec), rowvec_div=rowvec_div,
+                        residual=f.inp(residual), act=act, out=f.out(Mout, n_out, cdt, cols=c_cols), M=M, ln=lnf, **kw)
+    return _edge_rows(name, run, ref)
+
+
+def _geglu_case(M, K, inner, seed=0):
+    a = rnd(M, K, seed=seed + 1)
+    wfull, bfull = rnd(2 * inner, K, scale=1 / math.sqrt(K), seed=seed + 2), rnd(2 * inner, scale=0.1, seed=seed + 3)
+    wp, bp = _geglu_pack(wfull, bfull, inner)
+    proj = a.float() @ wfull.float().t() + bfull.float()
+    return a, wp, bp, proj[:, :inner] * F.gelu(proj[:, inner:])
+
+
+def _conv_edge_cases(n, ci, co, H, W, c1=0, what=("s1", "s2", "up", "asym", "two")):
+    """(tag, a0, w packed, gemm kwargs, reference tokens) of the small conv geometry: stride 1 + bias + temb + residual, stride 2,
+    folded nearest x2 upsample, asymmetric padding (stride 2, pad right / bottom only), two sources."""
+    x, w, b = rnd(n, ci, H, W, seed=11), rnd(co, ci, 3, 3, scale=1 / math.sqrt(9 * ci), seed=12), rnd(co, seed=13)
+    xt, wp = _to_tokens(x), _pack_conv(w)
+    cases = []
+    if "s1" in what:
+        temb, res = rnd(n, co, seed=14), rnd(n * H * W, co, seed=15)
+        ref = F.conv2d(x.float(), w.float(), b.float(), padding=1) + temb.float()[:, :, None, None]
+        cases.append(("s1 +bias+temb+res", xt, wp, dict(bias=b, rowvec=temb, rowvec_div=H * W, residual=res, mode=ops.MODE_CONV2D,
+                                                        conv=(H, W, H, W, 1, 0)), _to_tokens(ref) + res.float()))
+    if "s1res" in what:   # (the persistent families take bias + residual, not temb + residual)
+        res = rnd(n * H * W, co, seed=15)
+        ref = F.conv2d(x.float(), w.float(), b.float(), padding=1)
+        cases.append(("s1 +bias+res", xt, wp, dict(bias=b, residual=res, mode=ops.MODE_CONV2D, conv=(H, W, H, W, 1, 0)),
+                      _to_tokens(ref) + res.float()))
+    if "s2" in what:
+        Ho, Wo = H // 2, W // 2
+        cases.append(("stride 2", xt, wp, dict(bias=b, mode=ops.MODE_CONV2D, conv=(H, W, Ho, Wo, 2, 0), M=n * Ho * Wo),
+                      _to_tokens(F.conv2d(x.float(), w.float(), b.float(), stride=2, padding=1))))
+    if "up" in what:
+        ref = F.conv2d(F.interpolate(x.float(), scale_factor=2.0, mode="nearest"), w.float(), b.float(), padding=1)
+        cases.append(("upsample x2", xt, wp, dict(bias=b, mode=ops.MODE_CONV2D, conv=(H, W, 2 * H, 2 * W, 1, 1), M=n * 4 * H * W), _to_tokens(ref)))
+    if "asym" in what:
+        ref = F.conv2d(F.pad(x.float(), (0, 1, 0, 1)), w.float(), b.float(), stride=2)
+        Ho, Wo = ref.shape[2:]
+        cases.append(("asym pad, stride 2", xt, wp, dict(bias=b, mode=ops.MODE_CONV2D, conv=(H, W, Ho, Wo, 2, 0, 1), M=n * Ho * Wo), _to_tokens(ref)))
+    if "two" in what:
+        c1 = c1 or 128
+        x1 = rnd(n, c1, H, W, seed=16)
+        w2 = rnd(co, ci + c1, 3, 3, scale=1 / math.sqrt(9 * (ci + c1)), seed=17)
+        ref = F.conv2d(torch.cat([x, x1], 1).float(), w2.float(), padding=1)
+        cases.append(("two-source", xt, _pack_conv(w2), dict(a1=_to_tokens(x1), mode=ops.MODE_CONV2D, conv=(H, W, H, W, 1, 0)), _to_tokens(ref)))
+    return cases
+
+
+def _temporal_edge_case(B, Fr, HW, C, co):
+    xt = rnd(B * Fr * HW, C, seed=21)
+    wt, bt, rt = rnd(co, C, 3, scale=1 / math.sqrt(3 * C), seed=22), rnd(co, seed=23), rnd(B * Fr * HW, co, seed=24)
+    ref = F.conv1d(xt.float().view(B, Fr, HW, C).permute(0, 2, 3, 1).reshape(B * HW, C, Fr), wt.float(), bt.float(), padding=1)
+    ref = ref.view(B, HW, co, Fr).permute(0, 3, 1, 2).reshape(B * Fr * HW, co) + rt.float()
+    return (f"temporal B{B} F{Fr} HW{HW} {C}->{co} +res", xt, wt.permute(0, 2, 1).reshape(co, 3 * C).contiguous(),
+            dict(bias=bt, residual=rt, mode=ops.MODE_TEMPORAL, temporal=(Fr, HW)), ref)
+
+
+def check_edges_gemm_tile(variants=("reg", "glds", "naive")):
+    """The 128-row tile kernel (flags bit2 | bit4: no persistent kernel, no split-K), register- and LDS-DMA-staged, and the naive kernel:
+    ragged M (1 / 130 / 257 rows), N % 8 = 4 (the narrowest vector epilogue), 128- / 160-column tiles plus 8, one / two K-tiles, with
+    bias + rowvec + residual; two sources; GEGLU; fp32 output; one 8-byte-misaligned C view (falls back to the naive kernel)."""
+    out = []
+    saved, saved_glds = ops.GEMM_FLAGS, ops.USE_GLDS
+    try:
+        ops.GEMM_FLAGS = saved | 4 | 16
+        for var in variants:
+            ops.USE_GLDS = var == "glds"
+            naive = var == "naive"
+            for M in (1, 130, 257):
+                for N in (4, 12, 136, 168, 320):
+                    for K in (64, 128):
+                        a, w = rnd(M, K, seed=M + N + K), rnd(N, K, scale=1 / math.sqrt(K), seed=M + N + K + 1)
+                        bias, res, rv = rnd(N, seed=N), rnd(M, N, seed=M + 7 * N), rnd((M + 49) // 50, N, seed=M + 9 * N)
+                        out += _gemm_edge(f"edge gemm[{var}] M{M} N{N} K{K} +bias+rowvec+res", a, w, _gemm_ref(a, w, bias, rv, 50, res),
+                                          bias=bias, rowvec=rv, rowvec_div=50, residual=res, naive=naive)
+            a0, a1, w = rnd(130, 128, seed=1), rnd(130, 64, seed=2), rnd(320, 192, scale=0.1, seed=3)
+            out += _gemm_edge(f"edge gemm[{var}] two-source 128 + 64", a0, w, _gemm_ref(torch.cat([a0, a1], 1), w), a1=a1, naive=naive)
+            a, wp, bp, ref = _geglu_case(130, 128, 128)
+            out += _gemm_edge(f"edge gemm[{var}] GEGLU N256", a, wp, ref, bias=bp, act=ops.ACT_GEGLU, naive=naive)
+            a, w, bias = rnd(130, 64, seed=4), rnd(12, 64, scale=0.125, seed=5), rnd(12, seed=6)
+            out += _gemm_edge(f"edge gemm[{var}] fp32 out N12", a, w, _gemm_ref(a, w, bias), bias=bias, act=ops.ACT_F32OUT, naive=naive)
+        ops.USE_GLDS = True
+        a, w, bias, res = rnd(130, 128, seed=7), rnd(136, 128, scale=0.09, seed=8), rnd(136, seed=9), rnd(130, 136, seed=10)
+        out += _gemm_edge("edge gemm: C view 8 bytes off a 16-byte boundary (naive fallback)", a, w, _gemm_ref(a, w, bias, residual=res),
+                          bias=bias, residual=res, c_cols=12)
+    finally:
+        ops.GEMM_FLAGS, ops.USE_GLDS = saved, saved_glds
+    return out
+
+
+def check_edges_conv(variants=("reg", "glds", "naive")):
+    """Convolutions on the small geometry (3 images of 12 x 10, 64 -> 128 channels) and the temporal conv (2 x 5 frames x 24 px) with
+    residual: the taps of the first image's first row and of the last image's last row point at the frame."""
+    out = []
+    saved, saved_glds = ops.GEMM_FLAGS, ops.USE_GLDS
+    try:
+        ops.GEMM_FLAGS = saved | 4 | 16
+        for var in variants:
+            ops.USE_GLDS = var == "glds"
+            for (tag, a, w, kw, ref) in _conv_edge_cases(3, 64, 128, 12, 10) + [_temporal_edge_case(2, 5, 24, 64, 64)]:
+                out += _gemm_edge(f"edge conv3x3[{var}] {tag}" if "temporal" not in tag else f"edge conv[{var}] {tag}", a, w, ref,
+                                  naive=var == "naive", **kw)
+    finally:
+        ops.GEMM_FLAGS, ops.USE_GLDS = saved, saved_glds
+    return out
+
+
+def _nk(kw, K):
+    mode = kw.get("mode", ops.MODE_LINEAR)
+    return (1 if mode == ops.MODE_LINEAR else (9 if mode == ops.MODE_CONV2D else 3)) * (K // 64)
+
+
+def _sw_eligible(N, kw, K):
+    """Host mirror of the one-wave-per-SIMD kernel's shape test for the cases below (act none; ld % 8 = 0 by construction)."""
+    return N % 320 == 0 and not (kw.get("residual") is not None and kw.get("rowvec") is not None) and _nk(kw, K) >= 2
+
+
+def _sk_blocks(M, N, kw, K):
+    """... and of the forced stream-K form: 0 = the launch has fewer than 8 (tile, K-tile) units and stays on another kernel."""
+    units = ((M + 191) // 192) * (N // 320) * _nk(kw, K)
+    return (min(units // 4, 256) if units >= 8 else 0) if units < 1024 else 256
+
+
+PERSISTENT_FAMILIES = (("persistent 192x320", 8), ("ping-pong 192", (1 << 17) | (1 << 19)), ("ping-pong 256", (1 << 17) | (1 << 20)),
+                       ("one-wave-per-SIMD", 1 << 21), ("stream-K", 1 << 27))
+
+
+def _persistent_cases():
+    cases = []
+    for (M, N, K) in [(197, 320, 128), (261, 320, 128), (197, 640, 192)]:
+        a, w = rnd(M, K, seed=M + N), rnd(N, K, scale=1 / math.sqrt(K), seed=M + N + 1)
+        bias, res = rnd(N, seed=N + 2), rnd(M, N, seed=M + 3)
+        cases.append((f"M{M} N{N} K{K} +bias+res", a, w, dict(bias=bias, residual=res), _gemm_ref(a, w, bias, residual=res)))
+    cases += _conv_edge_cases(3, 64, 320, 16, 16, what=("s1res",))
+    cases.append(_temporal_edge_case(2, 5, 24, 64, 320))
+    return cases
+
+
+def check_edges_gemm_persistent():
+    """The persistent 192 x 320 kernel (flags bit3), the ping-pong kernel (bit17 with bit19 / bit20), the one-wave-per-SIMD kernel (bit21) and
+    its stream-K form (bit27) at row counts that are not multiples of their tiles; the stream-K rows run with the workspace NaN-filled
+    and zero-filled (bit-equal: no partial tile is summed from a slot the launch did not write).  A case a kernel is not eligible for
+    is skipped by name."""
+    out = []
+    saved, saved_glds = ops.GEMM_FLAGS, ops.USE_GLDS
+    try:
+        ops.USE_GLDS = True
+        for fam, bits in PERSISTENT_FAMILIES:
+            ops.GEMM_FLAGS = (saved & ~4) | bits
+            for (tag, a, w, kw, ref) in _persistent_cases():
+                name = f"edge gemm[{fam}] {tag}"
+                M, N, K = kw.get("M", a.shape[0]), w.shape[0], a.shape[1]
+                if bits in (1 << 21, 1 << 27) and not _sw_eligible(N, kw, K):
+                    out.append(_skip_row(name, "shape not eligible for the one-wave-per-SIMD kernel"))
+                    continue
+                if bits == 1 << 27:
+                    if _sk_blocks(M, N, kw, K) == 0:
+                        out.append(_skip_row(name, "fewer than 8 (tile, K-tile) units: no stream-K form"))
+                        continue
+                    out += _workspace_rows(name, a, w, ref, kw)
+                else:
+                    out += _gemm_edge(name, a, w, ref, **kw)
+    finally:
+        ops.GEMM_FLAGS, ops.USE_GLDS = saved, saved_glds
+    return out
+
+
+def _workspace_rows(name, a, w, ref, kw):
+    """Edge rows of a launch that sums fp32 partial tiles from ``ops._workspace``: the scratch NaN-filled, then zero-filled (a launch may
+    only read slots it wrote itself, so the two results are bit-equal).  The workspace is scratch: nothing is restored."""
+    ws = ops._workspace(DEV)
+    ws.fill_(float("nan"))
+    rows = _gemm_edge(name + " [workspace NaN-filled]", a, w, ref, **kw)
+    ws.fill_(float("nan"))
+    y_nan = ops.gemm(a, w, **kw)
+    ws.zero_()
+    y_zero = ops.gemm(a, w, **kw)
+    torch.cuda.synchronize()
+    same = bool(torch.equal(y_nan, y_zero))
+    rows.append(dict(name=name + ": NaN-filled workspace == zero-filled workspace, bit for bit", err=0.0 if same else 1.0, tol=0.0, ok=same))
+    rows += [r for r in _gemm_edge(name + " [workspace zero-filled]", a, w, ref, **kw)]
+    return rows
+
+
+def check_edges_splitk():
+    """The two 8x8-level conv cases of ``check_gemm_splitk`` (M = 3072: split-K on the 128-row kernel and on the persistent kernel) with
+    every operand framed and the fp32 workspace NaN- / zero-filled."""
+    out = []
+    saved_glds = ops.USE_GLDS
+    try:
+        ops.USE_GLDS = True
+        H = W = 8
+        for (n, ci, co, tag) in [(48, 256, 320, "split-K"), (48, 640, 1280, "persistent split-K")]:
+            x, w, b = rnd(n, ci, H, W), rnd(co, ci, 3, 3, scale=1 / math.sqrt(9 * ci)), rnd(co)
+            temb, res = rnd(3, co), rnd(n * H * W, co)
+            kw = dict(bias=b, rowvec=temb, rowvec_div=16 * H * W, residual=res, mode=ops.MODE_CONV2D, conv=(H, W, H, W, 1, 0))
+            ref = F.conv2d(x.float(), w.float(), b.float(), padding=1) + temb.float().repeat_interleave(16, 0)[:, :, None, None]
+            out += _workspace_rows(f"edge conv3x3[{tag}] {ci}->{co} @8x8 M3072", _to_tokens(x), _pack_conv(w), _to_tokens(ref) + res.float(), kw)
+    finally:
+        ops.USE_GLDS = saved_glds
+    return out
+
+
+def check_edges_conv_lds_patch():
+    """The LDS-patch 3x3 convolution (flags bit28) at row counts that are not multiples of its 192-row tile: the patch rows above the
+    first image and below the last one come from the frame."""
+    out = []
+    saved, saved_glds = ops.GEMM_FLAGS, ops.USE_GLDS
+    try:
+        ops.USE_GLDS = True
+        ops.GEMM_FLAGS = saved | (1 << 28)
+        for (n, H) in [(1, 16), (3, 16), (1, 32)]:
+            for (tag, a, w, kw, ref) in _conv_edge_cases(n, 64, 320, H, H, what=("s1res",)):
+                out += _gemm_edge(f"edge conv3x3[LDS patch] {n} x {H}x{H} 64->320 {tag}", a, w, ref, **kw)
+        out.append(_skip_row("edge conv[LDS patch] temporal", "the LDS-patch kernel takes 3x3 stride-1 convolutions only"))
+    finally:
+        ops.GEMM_FLAGS, ops.USE_GLDS = saved, saved_glds
+    return out
+
+
+def check_edges_gemm_ws():
+    """The weight-stationary kernel (flags bit10): ragged strips (row guards, clamped look-ahead), K = 320 and 512, residual, GEGLU, and
+    the LayerNorm fold with ``ln_c1`` framed."""
+    out = []
+    saved, saved_glds = ops.GEMM_FLAGS, ops.USE_GLDS
+    try:
+        ops.USE_GLDS = True
+        ops.GEMM_FLAGS = saved | 1024
+        for (M, N, K, res) in [(100, 160, 320, False), (2049, 320, 320, True), (100, 64, 512, False), (100, 512, 512, True)]:
+            name = f"edge gemm[ws] M{M} N{N} K{K} res={res}"
+            if K == 512 and N != 512:
+                out.append(_skip_row(name, "at K = 512 the weight-stationary kernel takes N = 512 (or GEGLU) only"))
+                continue
+            a, w, bias = rnd(M, K, seed=M), rnd(N, K, scale=1 / math.sqrt(K), seed=N), rnd(N, seed=K)
+            r = rnd(M, N, seed=M + N) if res else None
+            out += _gemm_edge(name, a, w, _gemm_ref(a, w, bias, residual=r), bias=bias, residual=r)
+        a, wp, bp, ref = _geglu_case(777, 320, 160)
+        out += _gemm_edge("edge gemm[ws] GEGLU M777 inner160", a, wp, ref, bias=bp, act=ops.ACT_GEGLU)
+        M, K, N, eps = 100, 320, 160, 1e-5
+        x = (rnd(M, K, seed=31).float() * 1.5 + 2.0).half()
+        gamma, beta = (1.0 + 0.3 * rnd(K, seed=32).float()).half(), (0.2 * rnd(K, seed=33).float()).half()
+        w, b = rnd(N, K, scale=1 / math.sqrt(K), seed=34), rnd(N, scale=0.1, seed=35)
+        ref = F.layer_norm(x.float(), (K,), gamma.float(), beta.float(), eps) @ w.float().t() + b.float()
+        wq, bq, c1 = ops.ln_fold(w, b, gamma, beta)
+        out += _gemm_edge("edge gemm[ws+LN] M100 K320 N160", x, wq, ref, bias=bq, ln=(c1, eps))
+    finally:
+        ops.GEMM_FLAGS, ops.USE_GLDS = saved, saved_glds
+    return out
+
+
+def check_edges_ff_fused():
+    """The fused feed-forward kernel with X, W1, b1, W2, b2, R and Y framed: one strip and a ragged tail."""
+    out = []
+    C, H = 320, 1280
+    w1, b1 = rnd(2 * H, C, scale=1 / math.sqrt(C)), rnd(2 * H, scale=0.1)
+    w2, b2 = rnd(C, H, scale=1 / math.sqrt(H)), rnd(C, scale=0.1)
+    w1p, b1p = _geglu_pack(w1, b1, H)
+    w2s = ops.ff_pack_w2(w2)
+    for M in (32, 167):
+        x, r = rnd(M, C, seed=M), rnd(M, C, seed=M + 1)
+        proj = x.float() @ w1.float().t() + b1.float()
+        hid = (proj[:, :H] * F.gelu(proj[:, H:])).half().float()
+        ref = (hid @ w2.float().t() + b2.float()).half().float() + r.float()
+
+        def run(f):
+            return ops.ff_geglu(f.inp(x), f.inp(w1p, flat=True), f.inp(b1p), f.inp(w2s, flat=True), f.inp(b2), residual=f.inp(r),
+                                out=f.out(M, C))
+        out += _edge_rows(f"edge ff_fused M{M} +res", run, ref)
+    return out
+
+
+# ---- attention
+def _attn_rows_of(batch, S, inner, strides):
+    outer, inner_s, seq = strides
+    i = torch.arange(batch, device=DEV)
+    return ((i // inner) * outer + (i % inner) * inner_s)[:, None] + torch.arange(S, device=DEV)[None] * seq   # [batch, S]
+
+
+def _attn_ref(q2, k2, v2, *, batch, heads, Sq, Sk, inner, q_strides, kv_strides, kv_div=1, qk_mod=0, d=64, scale=None, causal=False,
+              bias=None, only=None):
+    """fp32 attention on token matrices with the entry point's addressing (include/anyv2v_hip.h): ``(rows, ref)`` -- the output rows
+    of the batch elements ``only`` (default: all) and their [len(rows), heads * d] reference."""
+    C = heads * d
+    i = torch.arange(batch, device=DEV) if only is None else torch.tensor(only, device=DEV)
+    iq = i % qk_mod if qk_mod else i
+    rq, ro = _attn_rows_of(batch, Sq, inner, q_strides), _attn_rows_of(batch, Sq, inner, q_strides)
+    rkv = _attn_rows_of(batch, Sk, inner, kv_strides)
+    sp = lambda x, rows, S: x[rows.reshape(-1)].float().view(len(i), S, heads, d).transpose(1, 2)
+    q, k, v = sp(q2, rq[iq], Sq), sp(k2, rkv[iq // kv_div], Sk), sp(v2, rkv[i // kv_div], Sk)
+    scale = d ** -0.5 if scale is None else scale
+    if bias is not None:
+        ref = F.scaled_dot_product_attention(q, k, v, attn_mask=bias[None].float(), scale=scale)
+    else:
+        ref = F.scaled_dot_product_attention(q, k, v, is_causal=causal, scale=scale)
+    return ro[i].reshape(-1), ref.transpose(1, 2).reshape(-1, C)
+
+
+def _attn_operand(f, t):
+    """A Q / K / V source matrix for the launch: plain, or inside a buffer with 16 more (poisoned) columns and poisoned frame rows."""
+    if not f.framed:
+        return t
+    M, Wd = t.shape
+    buf = torch.full((M + 128, Wd + 16), POISON16, dtype=torch.int16, device=DEV)
+    view = buf.view(torch.float16)[64:64 + M, :Wd]
+    view.copy_(t)
+    return view
+
+
+def _attn_edge(name, *, batch, heads, Sq, Sk, d=64, inner=1, q_strides=None, kv_strides=None, kv_div=1, qk_mod=0, causal=False,
+               bias=None, naive=False, seed=0, tol=KTOL):
+    """One attention edge case.  Self-attention shapes read Q / K / V from one fused matrix [rows, 3 C]; the others Q from [rows, C] and
+    K / V from [kv rows, 2 C].  O is a framed [rows, C] window (8 guard columns each side, guard rows)."""
+    C = heads * d
+    q_strides = (Sq, 0, 1) if q_strides is None else q_strides
+    kv_strides = (Sk, 0, 1) if kv_strides is None else kv_strides
+    Mq = int(_attn_rows_of(batch, Sq, inner, q_strides).max()) + 1
+    Mk = int(_attn_rows_of((batch + kv_div - 1) // kv_div, Sk, inner, kv_strides).max()) + 1
+    fused = Mq == Mk and kv_div == 1 and q_strides == kv_strides
+    if fused:
+        qkv = rnd(Mq, 3 * C, seed=seed + 1)
+        srcs = lambda f: (lambda t: (t[:, :C], t[:, C:2 * C], t[:, 2 * C:]))(_attn_operand(f, qkv))
+        q2, k2, v2 = qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:]
+    else:
+        qm, kv = rnd(Mq, C, seed=seed + 1), rnd(Mk, 2 * C, seed=seed + 2)
+        srcs = lambda f: (lambda a, b: (a, b[:, :C], b[:, C:]))(_attn_operand(f, qm), _attn_operand(f, kv))
+        q2, k2, v2 = qm, kv[:, :C], kv[:, C:]
+    kw = dict(batch=batch, heads=heads, Sq=Sq, Sk=Sk, inner=inner, q_strides=q_strides, kv_strides=kv_strides, kv_div=kv_div, qk_mod=qk_mod)
+    rows, ref = _attn_ref(q2, k2, v2, d=d, causal=causal, bias=bias, **kw)
+    want = torch.zeros(Mq, C, device=DEV)
+    want[rows] = ref
+    extra = {} if d == 64 and not causal and bias is None else dict(scale=d ** -0.5, head_dim=d, causal=causal)
+
+    def run(f):
+        q, k, v = srcs(f)
+        o = f.out(Mq, C, init=torch.zeros(Mq, C, dtype=torch.float16, device=DEV))
+        return ops.attention(q, k, v, o, naive=naive, bias=None if bias is None else f.inp(bias, flat=True), **kw, **extra)
+    return _edge_rows(name, run, want, tol)
+
+
+def check_edges_attention():
+    """The flash kernel (4-wave blocks): ragged query blocks and key tails, whole masked steps, shared K / V (kv_div), the PnP
+    shared-softmax kernel and its aliasing form (flag bit3), the temporal layout through the short one-wave kernel (F <= 16) and the
+    flash kernel (F = 40)."""
+    out = []
+    for (b, h, Sq, Sk) in [(2, 2, 130, 145), (2, 1, 20, 3), (1, 1, 33, 63)]:
+        out += _attn_edge(f"edge attn[flash] b{b} h{h} Sq{Sq} Sk{Sk}", batch=b, heads=h, Sq=Sq, Sk=Sk, seed=Sq)
+    out += _attn_edge("edge attn[flash] b4 h1 Sq256 Sk145 kv_div2", batch=4, heads=1, Sq=256, Sk=145, kv_div=2, seed=5)
+    for flag in (0, 8):
+        saved, ops.ATTN_FLAGS = ops.ATTN_FLAGS, ops.ATTN_FLAGS | flag
+        try:
+            out += _attn_edge("edge attn PnP b3 h1 S130 " + ("shared-softmax kernel" if not flag else "aliasing form (flag bit3)"),
+                              batch=3, heads=1, Sq=130, Sk=130, qk_mod=1, seed=6)
+        finally:
+            ops.ATTN_FLAGS = saved
+    B_, HW, h = 3, 20, 2
+    for Fr in (8, 16, 40):
+        for inj in (False, True):
+            st = (Fr * HW, 1, HW)
+            out += _attn_edge(f"edge attn temporal F{Fr} inject={inj}", batch=B_ * HW, heads=h, Sq=Fr, Sk=Fr, inner=HW, q_strides=st,
+                              kv_strides=st, qk_mod=HW if inj else 0, seed=Fr)
+    return out
+
+
+def check_edges_attention_8wave():
+    """8-wave (256-query) blocks of the flash kernel: b29 h4 S2100 gives 1044 blocks, a ragged last block (52 queries) and a ragged last
+    key tile.  Framed against plain (bit-equal), framed against the 4-wave form (flag bit2, 1e-6), fp32 SDPA on two (batch, head) pairs."""
+    out = []
+    b, h, S = 29, 4, 2100
+    C = 64 * h
+    qkv = rnd(b * S, 3 * C, seed=2100)
+    kw = dict(batch=b, heads=h, Sq=S, Sk=S, inner=1, q_strides=(S, 0, 1), kv_strides=(S, 0, 1))
+    name = f"edge attn[flash, 8-wave blocks] b{b} h{h} S{S}"
+
+    def launch(f):
+        t = _attn_operand(f, qkv)
+        return ops.attention(t[:, :C], t[:, C:2 * C], t[:, 2 * C:], f.out(b * S, C), **kw)
+    yp = launch(_PlainOperands())
+    fr = _FramedOperands()
+    yf = launch(fr)
+    saved, ops.ATTN_FLAGS = ops.ATTN_FLAGS, ops.ATTN_FLAGS | 4
+    try:
+        y4 = launch(_FramedOperands())
+    finally:
+        ops.ATTN_FLAGS = saved
+    torch.cuda.synchronize()
+    for (i, hh) in [(0, 0), (28, 3)]:
+        q, k, v = (qkv[i * S:(i + 1) * S, j * C + 64 * hh:j * C + 64 * hh + 64][None, None] for j in range(3))
+        out.append(_res(f"{name}: framed, element {i} head {hh} vs fp32 SDPA", yf[i * S:(i + 1) * S, 64 * hh:64 * hh + 64], _sdpa(q, k, v)[0, 0], KTOL))
+    out.append(_res(f"{name}: framed == 4-wave blocks (flag bit2), framed", yf, y4.float(), 1e-6))
+    same, intact = bool(torch.equal(yf, yp)), fr.intact()
+    out.append(dict(name=f"{name}: framed == plain, bit for bit", err=0.0 if same else 1.0, tol=0.0, ok=same))
+    out.append(dict(name=f"{name}: frames of the outputs intact", err=0.0 if intact else 1.0, tol=0.0, ok=intact))
+    return out
+
+
+def check_edges_attention_small():
+    """``anyv2v_attention_small_f16``: the whole-sequence MFMA kernel, the 96-key loop kernel, the one-thread-per-query kernel (head_dim 4),
+    and the bias entry point on its MFMA (Sk <= 96) and generic (Sk = 130) kernels with the fp32 bias framed."""
+    out = []
+    for (B, h, S, d, causal) in [(3, 8, 24, 40, False), (3, 16, 77, 64, True), (2, 4, 90, 56, False), (2, 8, 77, 160, False)]:
+        out += _attn_edge(f"edge attention[small mfma] B{B} h{h} S{S} d{d} causal={causal}", batch=B, heads=h, Sq=S, Sk=S, d=d, causal=causal, seed=S + d)
+    for (B, h, S, d, causal) in [(2, 3, 289, 24, False), (1, 2, 401, 56, True)]:
+        out += _attn_edge(f"edge attention[small loop] B{B} h{h} S{S} d{d} causal={causal}", batch=B, heads=h, Sq=S, Sk=S, d=d, causal=causal, seed=S + d)
+    for (B, h, Sq, Sk, d) in [(2, 3, 20, 24, 40), (2, 2, 33, 130, 40)]:
+        bias = torch.randn(h, Sq, Sk, generator=torch.Generator().manual_seed(Sk)).to(DEV)
+        out += _attn_edge(f"edge attention + score bias B{B} h{h} Sq{Sq} Sk{Sk} d{d}", batch=B, heads=h, Sq=Sq, Sk=Sk, d=d, bias=bias, seed=Sk)
+    B_, Fr, HW, h, d = 2, 6, 10, 2, 4
+    st = (Fr * HW, 1, HW)
+    out += _attn_edge("edge attention one thread per query, head_dim 4 (temporal layout)", batch=B_ * HW, heads=h, Sq=Fr, Sk=Fr, d=d, inner=HW,
+                      q_strides=st, kv_strides=st, seed=4)
+    return out
+
+
+# ---- elementwise, layout and step kernels
+GRID_CAP_N = 4096 * 256 + 12345   # past the 4096-block x 256-thread grid cap of silu / add / ddim_step / guided_step: the grid-stride loop iterates
+EDGE_NS = (GRID_CAP_N, 1, 7, 8, 9)
+
+
+def _h(x):   # one fp16 rounding point of a kernel that computes in fp32
+    return x.half().float()
+
+
+def _guided_ref(e, x, coef, b_txt, b_unc, b_img, g_txt, g_img, pred, noise=None, sigma=0.0):
+    """The guided step with the kernel's documented rounding points: every guidance operation in fp32 rounded to fp16, the step itself
+    exact (float64)."""
+    n = x.numel()
+    E = e.reshape(-1, n).float()
+    ee = E[b_txt]
+    if b_unc >= 0:
+        eu = E[b_unc]
+        if b_img >= 0:
+            ei = E[b_img]
+            ee = _h(_h(eu + _h(g_img * _h(ei - eu))) + _h(g_txt * _h(ee - ei)))
+        else:
+            ee = _h(eu + _h(g_txt * _h(ee - eu)))
+    sa_t, sb_t, c0, c1 = (float(torch.tensor(c, dtype=torch.float32)) for c in coef)
+    ee, xx = ee.double(), x.reshape(-1).double()
+    if pred == 0:
+        x0, eps = sa_t * xx - sb_t * ee, sa_t * ee + sb_t * xx
+    elif pred == 1:
+        x0, eps = (xx - sb_t * ee) / sa_t, ee
+    else:
+        x0, eps = ee, (xx - sa_t * ee) / sb_t
+    y = c0 * x0 + c1 * eps
+    if noise is not None:
+        y = y + float(torch.tensor(sigma, dtype=torch.float32)) * noise.reshape(-1).double()
+    return y
+
+
+GUIDANCE_FORMS = (("no guidance", dict(b_txt=1)), ("text only", dict(b_unc=0, b_txt=2, g_txt=7.5)),
+                  ("image + text", dict(b_unc=2, b_img=0, b_txt=1, g_txt=7.5, g_img=1.5)))
+
+
+def check_edges_elementwise():
+    """silu / add / ddim_step / guided_step past the grid cap (the grid-stride loop iterates) and at 1 / 7 / 8 / 9 elements; add on operands
+    2 bytes off alignment (scalar path); every guidance form x prediction type of guided_step, Y aliasing X, the noise entry point."""
+    out = []
+    coef = (0.8, 0.6, 0.9, math.sqrt(1 - 0.81))
+    for n in EDGE_NS:
+        x, y2 = rnd(n, scale=2.0, seed=n % 1000 + 1), rnd(n, seed=n % 1000 + 2)
+        out += _edge_rows(f"edge silu n{n}", lambda f: ops.silu(f.inp(x), out=f.out_flat((n,))), F.silu(x.double()), 2e-3)
+        out += _edge_rows(f"edge add n{n}", lambda f: ops.add(f.inp(x), f.inp(y2), out=f.out_flat((n,))), x.double() + y2.double(), 2e-3)
+        sa, sb, pa, pb = coef
+        ref = pa * (sa * y2.double() - sb * x.double()) + pb * (sa * x.double() + sb * y2.double())
+        out += _edge_rows(f"edge ddim_step n{n}", lambda f: ops.ddim_step(f.inp(x), f.inp(y2), sa, sb, pa, pb, out=f.out_flat((n,))), ref, 3e-3)
+        e = rnd(3, n, seed=n % 1000 + 3)
+        gk = GUIDANCE_FORMS[2][1]
+        refg = _guided_ref(e, y2, coef, gk["b_txt"], gk["b_unc"], gk["b_img"], gk["g_txt"], gk["g_img"], 0)
+        out += _edge_rows(f"edge guided_step n{n} image + text, v-prediction",
+                          lambda f: ops.guided_step(f.inp(e, flat=True), f.inp(y2), coef, out=f.out_flat((n,)), **gk), refg, KTOL)
+    # add: every operand 2 bytes past a 16-byte boundary -> the alignment test picks the scalar path
+    n = 1000
+    a, b = rnd(n + 1, seed=71), rnd(n + 1, seed=72)
+
+    def run_add(f):
+        o = f.out_flat((n + 1,))
+        ops.add(f.inp(a)[1:], f.inp(b)[1:], out=o[1:])
+        return o[1:]
+    out += _edge_rows("edge add, operands 2 bytes off a 16-byte boundary (scalar path)", run_add, a[1:].double() + b[1:].double(), 2e-3)
+    n = 777
+    e, x = rnd(3, n, seed=81), rnd(n, seed=82)
+    nz = rnd(n, seed=83)
+    for form, gk in GUIDANCE_FORMS:
+        for pred in (0, 1, 2):
+            args = (gk["b_txt"], gk.get("b_unc", -1), gk.get("b_img", -1), gk.get("g_txt", 1.0), gk.get("g_img", 1.0), pred)
+            out += _edge_rows(f"edge guided_step {form}, prediction {pred}",
+                              lambda f: ops.guided_step(f.inp(e, flat=True), f.inp(x), coef, prediction=pred, out=f.out_flat((n,)), **gk),
+                              _guided_ref(e, x, coef, *args), KTOL)
+            out += _edge_rows(f"edge guided_step {form}, prediction {pred}, Y aliasing X",
+                              lambda f: (lambda xx: ops.guided_step(f.inp(e, flat=True), xx, coef, prediction=pred, out=xx, **gk))(f.inout(x)),
+                              _guided_ref(e, x, coef, *args), KTOL)
+            for sigma, tag in ((0.0, "sigma 0"), (0.3, "sigma 0.3")):
+                out += _edge_rows(f"edge guided_step_noise {form}, prediction {pred}, {tag}",
+                                  lambda f: ops.guided_step(f.inp(e, flat=True), f.inp(x), coef, prediction=pred, out=f.out_flat((n,)),
+                                                            noise=f.inp(nz), sigma=sigma, **gk),
+                                  _guided_ref(e, x, coef, *args, noise=nz, sigma=sigma), KTOL)
+    # fused CFG + DDIM step without CFG (b_unc < 0), the v tokens a 4-column window of a wider matrix (ldv > C)
+    Fr, H, W = 3, 4, 5
+    vt, latx = rnd(3 * Fr * H * W, 4, seed=91), rnd(1, 4, Fr, H, W, seed=92)
+    cf = torch.tensor(coef, dtype=torch.float32, device=DEV)
+    v = vt.double().view(3, Fr, H * W, 4).permute(0, 3, 1, 2).reshape(3, 4, Fr, H, W)[1]
+    c = [float(t) for t in cf]
+    xx = latx.double()[0]
+    ref = c[2] * (c[0] * xx - c[1] * v) + c[3] * (c[0] * v + c[1] * xx)
+    out += _edge_rows("edge cfg_ddim_step without CFG (b_unc < 0), ldv > C",
+                      lambda f: ops.cfg_ddim_step(f.inp(vt), -1, 1, 9.0, f.inp(cf), f.inp(latx), f.out_flat(tuple(latx.shape)))[0], ref, KTOL)
+    return out
+
+
+def _window_rows(name, run, window, want, exact=True, tol=0.0):
+    """Edge rows of a kernel that writes a column window of a wider destination: ``run(f)`` returns (destination, its prefill); the
+    window must equal ``want`` and every other column of the destination its prefill, on top of the three usual rows."""
+    rows = []
+    res = {}
+
+    def run2(f):
+        y, pre = run(f)
+        res[f.framed] = (y, pre)
+        return y
+    rows += _edge_rows(name, run2, lambda yf: torch.cat([res[True][1][:, :window[0]].float(), want.float().to(DEV), res[True][1][:, window[1]:].float()], 1), tol)
+    y, pre = res[True]
+    keep = bool(torch.equal(y[:, :window[0]], pre[:, :window[0]]) and torch.equal(y[:, window[1]:], pre[:, window[1]:]))
+    rows.append(dict(name=name + ": columns outside the destination window unchanged", err=0.0 if keep else 1.0, tol=0.0, ok=keep))
+    return rows
+
+
+def check_edges_layout():
+    """copy_cols / gather_rows past their grid caps and on odd windows, the NCFHW <-> token layouts on a column window of a framed token
+    matrix, adaptive_avgpool with non-divisible sizes."""
+    out = []
+    M = 8192 * 256 // 320 + 77
+    for (xc, yc, C) in [(0, 0, 1), (3, 5, 13), (320, 640, 320)]:
+        x, pre = rnd(M, xc + C + 3, seed=C), rnd(M, yc + C + 5, seed=C + 1)
+        out += _window_rows(f"edge copy_cols M{M} x[:, {xc}:{xc + C}] -> y[:, {yc}:{yc + C}]",
+                            lambda f: (ops.copy_cols(f.inp(x), xc, f.out(M, pre.shape[1], init=pre), yc, C), pre), (yc, yc + C), x[:, xc:xc + C])
+    Mg = 8192 * 256 + 77                      # one 16-byte chunk per row: past the 8192-block cap
+    src = rnd(300, 16, seed=7)
+    idx = torch.randint(0, 300, (Mg,), generator=torch.Generator().manual_seed(8)).to(torch.int32)
+    idx[:4] = torch.tensor([0, 299, 299, 0])
+    idx[-3:] = torch.tensor([299, 0, 0])
+    idx = idx.to(DEV)
+    pre = torch.zeros(Mg, 16, dtype=torch.float16, device=DEV)
+    out += _window_rows(f"edge gather_rows M{Mg} (repeated indices, first / last source row)",
+                        lambda f: (ops.gather_rows(f.inp(src), 8, idx, f.out(Mg, 16, init=pre), 8, 8), pre), (8, 16), src[idx.long(), 8:16])
+    B, Fr, H, W = 2, 3, 5, 6
+    for C in (4, 9):
+        lat = rnd(B, C, Fr, H, W, seed=C)
+        pre = rnd(B * Fr * H * W, 16, seed=C + 1)
+        tok_ref = lat.permute(0, 2, 3, 4, 1).reshape(-1, C)
+        out += _window_rows(f"edge ncfhw_to_tokens C{C} -> tokens[:, 4:{4 + C}]",
+                            lambda f: (ops.ncfhw_to_tokens(f.inp(lat), f.out(pre.shape[0], 16, init=pre), col0=4), pre), (4, 4 + C), tok_ref)
+        tok = pre.clone()
+        tok[:, 4:4 + C] = tok_ref
+        out += _edge_rows(f"edge tokens_to_ncfhw C{C} <- tokens[:, 4:{4 + C}]",
+                          lambda f: ops.tokens_to_ncfhw(f.inp(tok), B, C, Fr, H, W, col0=4, out=f.out_flat((B, C, Fr, H, W))), lat, 0.0)
+    N_, C = 2, 5
+    for (Hi, Wi, Ho, Wo) in [(10, 7, 4, 3), (5, 5, 8, 8), (3, 9, 1, 1)]:
+        xp = rnd(N_ * Hi * Wi, C, seed=Hi * Wi)
+        ref = F.adaptive_avg_pool2d(xp.double().view(N_, Hi, Wi, C).permute(0, 3, 1, 2), (Ho, Wo)).permute(0, 2, 3, 1).reshape(-1, C)
+        out += _edge_rows(f"edge adaptive_avgpool {Hi}x{Wi} -> {Ho}x{Wo}",
+                          lambda f: ops.adaptive_avgpool(f.inp(xp, flat=True), N_, Hi, Wi, Ho, Wo, out=f.out_flat((N_ * Ho * Wo, C))), ref, 2e-3)
+    return out
+
+
+def check_edges_softmax_timestep():
+    """softmax_rows over 1 / 255 / 257 / 8192 columns with lds, ldp > cols (poisoned padding), logits with |scale s| up to 1e4 and one
+    all-equal row, against float64 and with rows summing to 1 within 2e-3; timestep_embedding at dim 2 / 320 / 1280 for t = 0, 1, 999."""
+    out = []
+    for cols in (1, 255, 257, 8192):
+        g = torch.Generator().manual_seed(cols)
+        s = (torch.randn(4, cols, generator=g) * 3.0).to(DEV)
+        s[2] = 1.25                                       # one all-equal row
+        for scale, tag in ((0.044194173824159216, "scale 512^-0.5"), (1e4 / float(s.abs().max()), "|scale s| up to 1e4")):
+            ref = torch.softmax(scale * s.double(), 1)
+            name = f"edge softmax_rows cols {cols}, {tag}"
+            got = {}
+
+            def run(f):
+                got[f.framed] = ops.softmax_rows(f.inp(s), scale, out=f.out(4, cols))
+                return got[f.framed]
+            out += _edge_rows(name, run, ref, KTOL)
+            dev = float((got[True].double().sum(1) - 1.0).abs().max())
+            out.append(dict(name=name + ": rows sum to 1", err=dev, tol=2e-3, ok=dev <= 2e-3))
+    t = torch.tensor([0.0, 1.0, 999.0], device=DEV)
+    for dim in (2, 320, 1280):
+        half = dim // 2
+        arg = t.double()[:, None] * torch.exp(-math.log(10000.0) * torch.arange(half, device=DEV).double() / half)[None]
+        out += _edge_rows(f"edge timestep_embedding dim {dim}, t = 0, 1, 999",
+                          lambda f: ops.timestep_embedding(f.inp(t), dim, out=f.out_flat((3, dim))), torch.cat([arg.cos(), arg.sin()], -1), 2e-3)
+    return out
+
+
+EDGE_CHECKS = [check_edges_gemm_tile, check_edges_conv, check_edges_gemm_persistent, check_edges_splitk, check_edges_conv_lds_patch,
+               check_edges_gemm_ws, check_edges_ff_fused, check_edges_attention, check_edges_attention_8wave, check_edges_attention_small,
+               check_edges_elementwise, check_edges_layout, check_edges_softmax_timestep]
+
 ALL_KERNEL_CHECKS = [check_selftest, check_gemm, check_gemm_big, check_gemm_ws, check_gemm_ws_ln, check_gemm_splitk, check_conv, check_norms, check_attention,
                      check_attention_small_mfma, check_attention_bias_and_rotary_windows, check_gelu_all_inputs, check_elementwise,
-                     check_full_size_properties, check_vae_kernels]
+                     check_full_size_properties, check_vae_kernels] + EDGE_CHECKS
 
 
 def check_frame_parallel(Fr=4, hw=16, tol=4e-3):
