@@ -36,6 +36,33 @@ class GemmDesc(C.Structure):
         ("gn_stats", C.c_void_p), ("gn_stats_floats", C.c_int64), ("gn_rows_per_group", C.c_int32), ("gn_groups", C.c_int32),
     ]
 
+# AnyV2VGemmDesc.flags: the ANYV2V_GEMM_* constants of include/anyv2v_hip.h, which says what each bit does (*_SHIFT: first bit
+# of a multi-bit field).  tests/test_gemm_plan_host.py holds the two lists together.
+ANYV2V_GEMM_NAIVE = 1 << 0
+ANYV2V_GEMM_LDS_DMA = 1 << 1
+ANYV2V_GEMM_NO_BIG = 1 << 2
+ANYV2V_GEMM_FORCE_BIG = 1 << 3
+ANYV2V_GEMM_NO_SPLITK = 1 << 4
+ANYV2V_GEMM_PROBE_TRACE = 1 << 5
+ANYV2V_GEMM_PROBE_KO_SHIFT = 6
+ANYV2V_GEMM_NO_WS = 1 << 9
+ANYV2V_GEMM_FORCE_WS = 1 << 10
+ANYV2V_GEMM_NF4 = 1 << 11
+ANYV2V_GEMM_NF5 = 1 << 12
+ANYV2V_GEMM_RASTER_SHIFT = 13
+ANYV2V_GEMM_RASTER_NFAST = 1 << 16
+ANYV2V_GEMM_PP = 1 << 17
+ANYV2V_GEMM_NO_PP = 1 << 18
+ANYV2V_GEMM_PP_192 = 1 << 19
+ANYV2V_GEMM_PP_256 = 1 << 20
+ANYV2V_GEMM_SW = 1 << 21
+ANYV2V_GEMM_NO_SW = 1 << 22
+ANYV2V_GEMM_PROBE_SW_KO_SHIFT = 23
+ANYV2V_GEMM_STREAMK = 1 << 26
+ANYV2V_GEMM_FORCE_STREAMK = 1 << 27
+ANYV2V_GEMM_SWH = 1 << 28
+ANYV2V_GEMM_PROBE_KORDER_SHIFT = 29
+
 
 class FFDesc(C.Structure):
     _fields_ = [

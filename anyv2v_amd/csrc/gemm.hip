@@ -1171,6 +1171,7 @@ __global__ void gemm_splitk_reduce_kernel(const GemmK p) {
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// Host side: anyv2v_gemm_f16 plans (gemm_plan.cpp decides everything), fills the kernel arguments, launches what the plan says.
 static const half_t* zero_line() {
     static const half_t* z = nullptr;
     if (z == nullptr) {
@@ -1180,313 +1181,87 @@ static const half_t* zero_line() {
     return z;
 }
 
-// K-tiles (of 64) from which the ping-pong kernel would be taken by default.  Measured (profiles/r04_gemm_pp_ab_v1_*.txt, interleaved A/B
-// on the edit step's launches): its K loop is 2-6 % faster than gemm_big_kernel's from K = 5760 on (conv 960->320 @64x64 898 -> 845 us,
-// 1.21 -> 1.29 PF), equal at K = 2880, and its tile switch costs more (residual launches 10-30 % slower; temporal convolutions,
-// FF-down slower) -- the R slots, not the M slots, set the slot time (9 LDS-DMA issues per wave and K-tile).  The launches it wins sum
-// to 0.25 ms of the 106 ms step pair (+ 0.08 ms on the inversion step's one-round launches, M = 65536 with 256-row tiles: conv 960->320
-// 322 -> 298 us, r04_gemm_pp_ab_v1_b1_*.txt), so it stays OFF by default (flags bit17 selects it: tests, A/B); a second form with the next
-// tile's start-up hoisted in front of the tile-switch barrier was slower throughout (r04_gemm_pp_ab_v2_*.txt, not kept).
-constexpr int AV_PP_MIN_KTILES = 1 << 30;
-
-// GroupNorm records from the epilogue (AnyV2VGemmDesc.gn_stats): shapes the record layout covers, whatever the plan.
-static bool gn_shape_ok(const AnyV2VGemmDesc* d) {
-    if (d->gn_groups <= 0 || d->gn_rows_per_group <= 0 || d->N % 160 != 0 || d->N % d->gn_groups != 0) return false;
-    const int cg = d->N / d->gn_groups;
-    return 40 % cg == 0 && d->M % 16 == 0 && d->gn_rows_per_group % 16 == 0 && d->M % d->gn_rows_per_group == 0 &&
-           (d->act == ACT_NONE || d->act == ACT_SILU || d->act == ACT_GELU);
-}
 static int64_t g_gn_launches = 0;   // launches that emitted records (anyv2v_gemm_gn_launches); host-side, like the batch hint
 
-// gn_query != nullptr: plan only -- *gn_query = 1 when the launch this descriptor gets can emit GroupNorm records, nothing is
-// enqueued.  One function plans for the query and for the launch, so the two cannot disagree.
-#define AV_GN_DECLINE(what)                                                                                              \
-    do {                                                                                                                 \
-        if (gn_query != nullptr) return ANYV2V_OK;                                                                       \
-        AV_CHECK(d->gn_stats == nullptr, "gemm: gn_stats set, but this launch runs on " what                            \
-                                         ", which writes no GroupNorm statistics (ask anyv2v_gemm_gn_stats_floats first)"); \
-    } while (0)
+static void launch_splitk_reduce(const GemmK& k, hipStream_t s) {
+    const long long blocks = ((long long)k.M * (k.N / 8) + 255) / 256;   // (grid-stride loop: at most 2048 blocks)
+    hipLaunchKernelGGL(gemm_splitk_reduce_kernel, dim3((unsigned)(blocks < 2048 ? blocks : 2048)), dim3(256), 0, s, k);
+}
+
+// One arm per kernel family: it only picks the template instantiation.  Tiles, grid, split-K factor and tile order are in k / plan.
+#define AV_GO(kernel, threads) hipLaunchKernelGGL((kernel), grid, dim3(threads), 0, s, k)
 template <int MODE>
-static int dispatch(GemmK& k, const AnyV2VGemmDesc* d, bool fast, hipStream_t s, int* gn_query) {
-    const bool geglu = d->act == ACT_GEGLU;
-    const bool gn = gn_query != nullptr || d->gn_stats != nullptr;
-    if (!fast) {
-        AV_GN_DECLINE("the naive kernel");
-        const int Nout = geglu ? d->N / 2 : d->N;
-        const long long total = (long long)d->M * Nout;
-        hipLaunchKernelGGL(gemm_naive_kernel<MODE>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, k);
+static int launch(GemmK& k, const AnyV2VGemmDesc* d, const GemmPlan& plan, hipStream_t s) {
+    const bool geglu = d->act == ACT_GEGLU, res = d->R != nullptr, gn = k.gn_stats != nullptr;
+    const bool glds = (d->flags & ANYV2V_GEMM_LDS_DMA) != 0;
+    const dim3 grid((unsigned)plan.grid);
+    switch (plan.family) {
+    case GEMM_WS:
+    case GEMM_WS_LN: return av_gemm_ws_launch(k, d, plan, s);
+    case GEMM_SW: return av_gemm_sw_launch(k, d, plan, s);
+    case GEMM_SW_STREAMK: return av_gemm_sw_sk_launch(k, d, plan, s);
+    case GEMM_SWH: return av_gemm_swh_launch(k, d, plan, s);
+    case GEMM_NAIVE:
+        AV_GO(gemm_naive_kernel<MODE>, 256);
         return av_launch_status("gemm_naive");
-    }
-    const bool glds = (d->flags & 2) != 0;
-    // Stream-K form of the one-wave-per-SIMD kernel (gemm_sw.hip): flags bit26 allows it where av_gemm_sw_sk_blocks says it pays,
-    // bit27 forces it; never for a batch-hinted launch (its K ranges depend on the launch's own tile count, i.e. they fix the
-    // arithmetic, and a hinted launch has to reproduce the arithmetic of the launch it stands for).
-    if (glds && (d->flags & ((1 << 26) | (1 << 27))) && !(d->flags & (1 << 22)) && av_gemm_sw_eligible(d) && av_hint_rows(d->M) == d->M &&
-        d->workspace != nullptr) {
-        const int blocks = av_gemm_sw_sk_blocks(d, (d->flags & (1 << 27)) != 0);
-        if (blocks > 0 && av_gemm_sw_sk_workspace(blocks) <= (size_t)d->workspace_bytes) {
-            AV_GN_DECLINE("the stream-K kernel");
-            return av_gemm_sw_sk_launch(k, d, blocks, s);
-        }
-    }
-    // 3x3 convolution with LDS reuse of the A operand across the dx taps (gemm_swh.hip): flags bit28 takes it where eligible.
-    if (glds && (d->flags & (1 << 28)) && !(d->flags & (1 << 22)) && av_gemm_swh_eligible(d)) {
-        AV_GN_DECLINE("the LDS-patch convolution kernel");
-        return av_gemm_swh_launch(k, d, s);
-    }
-    // One-wave-per-SIMD persistent kernel (gemm_sw.hip): flags bit21 takes it wherever the shape allows, bit22 forbids it.
-    if (glds && (d->flags & (1 << 21)) && !(d->flags & (1 << 22)) && av_gemm_sw_eligible(d)) {
-        AV_GN_DECLINE("the one-wave-per-SIMD kernel");
-        return av_gemm_sw_launch(k, d, s);
-    }
-    // 128-row kernel tile width: 160 columns (NF = 5) where N allows it, except where 128-column tiles (NF = 4) quantise better onto
-    // the 256 CUs x 2 resident blocks -- more CUs busy when there is less than one tile per CU, or the same number of rounds with
-    // 20 % smaller tiles (flags bit11 / bit12 force NF = 4 / 5: A/B in tools/gemm_nf_ab.py).  Same arithmetic per output either way.
-    // The width does not touch the arithmetic, so a launch picks it on its OWN rows; the split-K factor of a batch-hinted launch is
-    // the reference launch's, i.e. planned with the width the reference launch picks (nf_ref below).
-    const int nk_all = k.taps * (k.nt0 + k.nt1);
-    auto choose_nf = [&](int rows) -> int {
-        int nf_ = geglu ? 4 : (d->N % 160 == 0 ? 5 : 4);
-        if (!geglu && nf_ == 5 && d->N % 128 == 0) {
-            const int mt = (rows + 127) / 128;
-            const int t5 = mt * (d->N / 160), t4 = mt * (d->N / 128);
-            // (not where the launch would be split along K: the split factor is derived from the tile count, and 7 x 80 tiles spill
-            //  into a second round where 7 x 64 do not -- B = 1 8x8-level convolutions: 45 -> 59 us, profiles/r03_gemm_nf_ab.txt)
-            const bool would_split = t4 < 384 && ((t4 <= 128 && nk_all >= 32) || nk_all >= 72);
-            const bool prefer4 = !would_split && ((t4 <= 256) || (t5 > 256 && (t5 + 511) / 512 == (t4 + 511) / 512));
-            if (((d->flags & 2048) || prefer4) && !(d->flags & 4096)) nf_ = 4;
-        }
-        return nf_;
-    };
-    const int nf = choose_nf(d->M);
-    const int nf_ref = choose_nf(av_hint_rows(d->M));
-    const int tilesN_small = (d->N + nf * 32 - 1) / (nf * 32);
-    constexpr int BMB = 192;
-    const bool big_ok = glds && !(d->flags & 4) && d->N % 320 == 0 && (!geglu || MODE == MODE_LINEAR) && (geglu || d->act == ACT_NONE);
-    // Launch plan as a function of the row count: kernel family (persistent 192 x 320 tiles / 128-row tiles) and split-K factor.
-    //  * persistent kernel: taken when its tiles fill the 256 CUs for a whole number of rounds well enough (>= 75 %), or when
-    //    forced (flags bit3);
-    //  * launches that cannot fill the CUs but have a long K loop (8x8-level convs / FF-down of the 3-clip batch, M = 3072): split K
-    //    so that (tiles x splits) is one nearly full round of 256 work items; the ordered reduce pass finishes them.  Measured
-    //    (profiles/r01_gemm_split_ab.txt): 1.2-1.4x over the 128-row kernel's split path from 80 K-tiles on with >= 224 work items;
-    //    slower below 72 K-tiles or with a 3/4-full round (M = 1024), which stay on the 128-row kernel;
-    //  * 128-row kernel split-K for launches that cannot fill the chip (512 block slots) and have a long K loop (with 20 K-tiles the
-    //    second pass costs more than the idle CUs; with 60 it pays only when fewer than a quarter of the block slots would be busy;
-    //    from ~72 K-tiles on it always pays).
-    // (the workspace test uses the PLANNED row count as well: a batch-hinted launch must reproduce the decision of the launch it
-    //  stands for -- its own, smaller partial tiles could fit where the reference launch's do not, and the two would then split
-    //  differently: seen at 16 f x 256^2, tests/test_gpu_parity.py::test_two_branch_steps_bit_equal_at_a_mid_size_full_width)
-    // (the split-K rules below see at most the 64 MiB the workspace had when they were tuned: a larger buffer -- the stream-K form
-    //  wants 126 MB -- must not change which launches split, i.e. their arithmetic)
-    const size_t split_ws_bytes = (size_t)d->workspace_bytes < ((size_t)64 << 20) ? (size_t)d->workspace_bytes : ((size_t)64 << 20);
-    struct Plan { int big, splits; };
-    auto plan = [&](int rows, int nf_rows) -> Plan {
-        const bool ws_ok = d->workspace != nullptr && d->N % 8 == 0;
-        if (big_ok) {
-            const int tb = ((rows + BMB - 1) / BMB) * (d->N / 320);
-            const int rounds = (tb + 255) / 256;
-            const bool fills = tb >= 224 && tb * 4 >= rounds * 256 * 3;
-            if (!fills && !geglu && !(d->flags & (16 | 8)) && ws_ok && tb <= 128 && nk_all >= 72) {
-                int sp = 256 / tb;
-                if (sp > 8) sp = 8;
-                if (sp > nk_all / 12) sp = nk_all / 12;
-                if (sp >= 2 && tb * sp >= 224 && (size_t)sp * rows * d->N * sizeof(float) <= split_ws_bytes) return {1, sp};
-            }
-            if (fills || (d->flags & 8)) return {1, 1};
-        }
-        const int tm = ((rows + 127) / 128) * ((d->N + nf_rows * 32 - 1) / (nf_rows * 32));
-        const bool split_pays = (tm <= 128 && nk_all >= 32) || nk_all >= 72;
-        if (glds && !geglu && d->act != ACT_F32OUT && !(d->flags & 16) && ws_ok && tm < 384 && split_pays) {
-            int sp = (512 + tm - 1) / tm;
-            if (sp > 8) sp = 8;
-            if (sp > nk_all / 8) sp = nk_all / 8;
-            if (sp >= 2 && (size_t)sp * rows * d->N * sizeof(float) <= split_ws_bytes) return {0, sp};
-        }
-        return {0, 1};
-    };
-    // Batch hint (anyv2v_set_batch_hint): what fixes the ARITHMETIC is the split-K factor (fp32 partial tiles summed afterwards);
-    // the two kernel families accumulate every output element in the same order (tests/gpu_checks.py asserts it bit for bit).  A
-    // hinted launch therefore takes the split factor of the launch it stands for and is otherwise planned on its own row count.
-    Plan use = plan(d->M, nf);
-    if (av_hint_rows(d->M) != d->M) {
-        const Plan ref = plan(av_hint_rows(d->M), nf_ref);
-        if (ref.splits > 1)
-            use = ref;
-        else if (use.splits > 1)
-            use = Plan{0, 1};
-    }
-    // Ping-pong kernel (gemm_pp_kernel): flags bit17 takes it wherever the shape allows, bit18 forbids it, bit19 / bit20 force its
-    // 192- / 256-row tile (default: the taller tile unless it quantises worse onto the 256 CUs).  Not split along K (the launches
-    // that want that are too small for it), so a batch-hinted launch may only take it when its reference launch is unsplit too.
-    if (big_ok && !geglu && use.splits == 1 && !(d->flags & (1 << 18)) &&
-        ((d->flags & (1 << 17)) || (use.big && nk_all >= AV_PP_MIN_KTILES))) {
-        auto eff = [&](int bm) {
-            const int tb = ((d->M + bm - 1) / bm) * (d->N / 320), r = (tb + 255) / 256;
-            return (double)tb / (r * 256.0);
-        };
-        AV_GN_DECLINE("the ping-pong kernel");
-        const int mf = (d->flags & (1 << 19)) ? 3 : ((d->flags & (1 << 20)) ? 4 : (eff(256) + 0.02 >= eff(192) ? 4 : 3));
-        const int tb = ((d->M + 64 * mf - 1) / (64 * mf)) * (d->N / 320);
-        const dim3 gridp(tb < 256 ? tb : 256);
-        k.tilesN = d->N / 320;
-#define AV_PP(MF_)                                                                                        \
-    do {                                                                                                  \
-        if (d->R != nullptr)                                                                              \
-            hipLaunchKernelGGL((gemm_pp_kernel<MF_, MODE, true>), gridp, dim3(512), 0, s, k);             \
-        else                                                                                              \
-            hipLaunchKernelGGL((gemm_pp_kernel<MF_, MODE, false>), gridp, dim3(512), 0, s, k);            \
-    } while (0)
-        if (mf == 4)
-            AV_PP(4);
-        else
-            AV_PP(3);
-#undef AV_PP
+    case GEMM_PP:
+        if (plan.pp_mf == 4 && res) AV_GO((gemm_pp_kernel<4, MODE, true>), 512);
+        else if (plan.pp_mf == 4) AV_GO((gemm_pp_kernel<4, MODE, false>), 512);
+        else if (res) AV_GO((gemm_pp_kernel<3, MODE, true>), 512);
+        else AV_GO((gemm_pp_kernel<3, MODE, false>), 512);
         return av_launch_status("gemm_pp");
-    }
-    // GroupNorm records: both tile kernels emit them in their unsplit, fp16-output, non-GEGLU forms (LDS-DMA staging); a split-K plan
-    // finishes in the reduce kernel, which has no tile to take them of.  Decided on `use`, i.e. under the batch hint, like the launch.
-    if (gn) {
-        if (use.splits > 1) AV_GN_DECLINE("a split-K plan");
-        if (geglu || d->act == ACT_F32OUT || !glds || !gn_shape_ok(d))
-            AV_GN_DECLINE("a GEGLU / fp32-output / register-staged launch or a shape the record layout does not cover (N %% 160 = 0, N / gn_groups "
-                          "dividing 40, M and gn_rows_per_group multiples of 16)");
-        if (gn_query != nullptr) {
-            *gn_query = 1;
-            return ANYV2V_OK;
-        }
-        AV_CHECK(d->gn_stats_floats >= (int64_t)3 * (d->M / 16) * d->gn_groups, "gemm: gn_stats holds %lld floats, the launch writes %lld",
-                 (long long)d->gn_stats_floats, (long long)3 * (d->M / 16) * d->gn_groups);
-        AV_CHECK((((uintptr_t)d->gn_stats) & 3) == 0, "gemm: gn_stats must be 4-byte aligned");
-        k.gn_stats = d->gn_stats;
-        k.gn_groups = d->gn_groups;
-        k.gn_cg = d->N / d->gn_groups;
-        ++g_gn_launches;
-    }
-    {   // ANYV2V_GEMM_LOG=1: one line per launch plan on stderr (diagnostics: which launches split, and how, under a batch hint)
-        static const bool log_on = getenv("ANYV2V_GEMM_LOG") != nullptr;
-        if (log_on)
-            fprintf(stderr, "gemm-plan mode %d M %d (hinted %d) N %d K %d act %d res %d big %d splits %d\n", MODE, d->M, av_hint_rows(d->M), d->N,
-                    k.Ktot, d->act, d->R != nullptr, use.big, use.splits);
-    }
-    if (use.big) {
-        const int tiles_big = ((d->M + BMB - 1) / BMB) * (d->N / 320);
-        k.tilesN = d->N / 320;
-        if (use.splits > 1) {
-            k.splits = use.splits;
-            k.partial = (float*)d->workspace;
-            const dim3 grid(tiles_big * use.splits < 256 ? tiles_big * use.splits : 256);
-            hipLaunchKernelGGL((gemm_big_kernel<3, false, MODE, false, true>), grid, dim3(512), 0, s, k);
-            const long long total = (long long)d->M * (d->N / 8);
-            long long blocks = (total + 255) / 256;
-            if (blocks > 2048) blocks = 2048;
-            hipLaunchKernelGGL(gemm_splitk_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, s, k);
+    case GEMM_BIG:
+        if (plan.splits > 1) {
+            AV_GO((gemm_big_kernel<3, false, MODE, false, true>), 512);
+            launch_splitk_reduce(k, s);
             return av_launch_status("gemm_big<split-K>");
-        }
-        const dim3 grid(tiles_big < 256 ? tiles_big : 256);
-        {   // tile order of wide-N launches (gemm_big_kernel): 8 x 4 super-tiles per XCD round when N has >= 8 tiles (the GEGLU
-            // up-projections at 640 / 1280 channels: 16 / 32 N-tiles).  flags bits 13-15: 0 auto, 1 classic order, 2..6 force
-            // rast_gm = 4, 8, 16, 32, 2; bit16: super-tiles N-fastest.  Same arithmetic per output element in every order.
-            const int code = (d->flags >> 13) & 7;
-            static const int gm_of[8] = {0, 0, 4, 8, 16, 32, 2, 0};
-            int gm = gm_of[code];
-            if (code == 0 && k.tilesN >= 8 && tiles_big >= 512) gm = 8;
-            const int tm_big = (d->M + BMB - 1) / BMB;
-            if (gm > 0 && grid.x == 256 && k.tilesN % (32 / gm) == 0) {
-                k.rast_gm = gm;
-                k.rast_gn = 32 / gm;
-                k.rast_sm = (tm_big + gm - 1) / gm;
-                k.rast_sn = k.tilesN / k.rast_gn;
-                k.rast_nfast = (d->flags >> 16) & 1;
-            }
         }
 #ifdef ANYV2V_EXPERIMENTS  // probe build only (make experiments): phase-timestamp instantiations, tools/gemm_big_trace.py
 #include "../../tools/experiments/gemm_dispatch_big_probe.inc"
 #endif
-        if (gn) {   // (never GEGLU: declined above)
-            if (d->R != nullptr)
-                hipLaunchKernelGGL((gemm_big_kernel<3, false, MODE, false, false, true, true>), grid, dim3(512), 0, s, k);
-            else
-                hipLaunchKernelGGL((gemm_big_kernel<3, false, MODE, false, false, false, true>), grid, dim3(512), 0, s, k);
+        if (gn) {   // (never GEGLU: the plan declines)
+            if (res) AV_GO((gemm_big_kernel<3, false, MODE, false, false, true, true>), 512);
+            else AV_GO((gemm_big_kernel<3, false, MODE, false, false, false, true>), 512);
             return av_launch_status("gemm_big<gn>");
         }
         if constexpr (MODE == MODE_LINEAR) {
-            if (geglu)
-                hipLaunchKernelGGL((gemm_big_kernel<3, true, MODE_LINEAR>), grid, dim3(512), 0, s, k);
-            else if (d->R != nullptr)
-                hipLaunchKernelGGL((gemm_big_kernel<3, false, MODE_LINEAR, false, false, true>), grid, dim3(512), 0, s, k);
-            else
-                hipLaunchKernelGGL((gemm_big_kernel<3, false, MODE_LINEAR>), grid, dim3(512), 0, s, k);
-        } else if (d->R != nullptr) {
-            hipLaunchKernelGGL((gemm_big_kernel<3, false, MODE, false, false, true>), grid, dim3(512), 0, s, k);
-        } else {
-            hipLaunchKernelGGL((gemm_big_kernel<3, false, MODE>), grid, dim3(512), 0, s, k);
+            if (geglu) {
+                AV_GO((gemm_big_kernel<3, true, MODE_LINEAR>), 512);
+                return av_launch_status("gemm_big");
+            }
         }
+        if (res) AV_GO((gemm_big_kernel<3, false, MODE, false, false, true>), 512);
+        else AV_GO((gemm_big_kernel<3, false, MODE>), 512);
         return av_launch_status("gemm_big");
-    }
-    // (with records: always the 160-column tile -- a channel group must not straddle the tile, and the width does not touch the
-    //  arithmetic; the plan above, split-K factor included, is the one the launch without records gets)
-    k.tilesN = gn ? d->N / 160 : tilesN_small;
-    const int tiles = ((d->M + 127) / 128) * k.tilesN;
-    const int nk = nk_all;
-    (void)nk;
-    if (use.splits > 1) {
-        k.splits = use.splits;
-        k.partial = (float*)d->workspace;
-    }
-    const dim3 grid(tiles * k.splits);
-#ifdef ANYV2V_EXPERIMENTS  // probe build only: phase timestamps (flag 32) / K-loop knock-outs (flags 64..448), tools/gemm_trace.py
+    default: {   // GEMM_MFMA128
+#ifdef ANYV2V_EXPERIMENTS  // probe build only: phase timestamps / K-loop knock-outs (ANYV2V_GEMM_PROBE_*), tools/gemm_trace.py
 #include "../../tools/experiments/gemm_dispatch_mfma_probe.inc"
 #endif
-#define AV_LAUNCH2(NF_, GEGLU_)                                                                          \
-    do {                                                                                                 \
-        if (glds)                                                                                   \
-            hipLaunchKernelGGL((gemm_mfma_kernel<NF_, true, GEGLU_, MODE>), grid, dim3(256), 0, s, k);   \
-        else                                                                                             \
-            hipLaunchKernelGGL((gemm_mfma_kernel<NF_, false, GEGLU_, MODE>), grid, dim3(256), 0, s, k);  \
-    } while (0)
-    if (gn)
-        hipLaunchKernelGGL((gemm_mfma_kernel<5, true, false, MODE, false, 0, true>), grid, dim3(256), 0, s, k);
-    else if (geglu)
-        AV_LAUNCH2(4, true);
-    else if (nf == 5)
-        AV_LAUNCH2(5, false);
-    else
-        AV_LAUNCH2(4, false);
-#undef AV_LAUNCH2
-    if (k.splits > 1) {
-        const long long total = (long long)d->M * (d->N / 8);
-        long long blocks = (total + 255) / 256;
-        if (blocks > 2048) blocks = 2048;
-        hipLaunchKernelGGL(gemm_splitk_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, s, k);
+        if (gn) AV_GO((gemm_mfma_kernel<5, true, false, MODE, false, 0, true>), 256);
+        else if (geglu && glds) AV_GO((gemm_mfma_kernel<4, true, true, MODE>), 256);
+        else if (geglu) AV_GO((gemm_mfma_kernel<4, false, true, MODE>), 256);
+        else if (plan.nf == 5 && glds) AV_GO((gemm_mfma_kernel<5, true, false, MODE>), 256);
+        else if (plan.nf == 5) AV_GO((gemm_mfma_kernel<5, false, false, MODE>), 256);
+        else if (glds) AV_GO((gemm_mfma_kernel<4, true, false, MODE>), 256);
+        else AV_GO((gemm_mfma_kernel<4, false, false, MODE>), 256);
+        if (plan.splits > 1) launch_splitk_reduce(k, s);
+        return av_launch_status("gemm_mfma");
     }
-    return av_launch_status("gemm_mfma");
+    }
 }
+#undef AV_GO
 
-static int gemm_impl(const AnyV2VGemmDesc* d, void* stream, int* gn_query) {
+extern "C" int anyv2v_gemm_f16(const AnyV2VGemmDesc* d, void* stream) {
     AV_CHECK(d != nullptr, "gemm: null descriptor");
-    AV_CHECK(d->A0 && d->W && (d->C || gn_query != nullptr), "gemm: null A0/W/C");
-    AV_CHECK(d->M > 0 && d->N > 0 && d->C0 > 0 && d->C1 >= 0, "gemm: bad M/N/C0/C1 (%d %d %d %d)", d->M, d->N, d->C0, d->C1);
-    AV_CHECK(d->mode >= 0 && d->mode <= 2, "gemm: bad mode %d", d->mode);
-    AV_CHECK(d->act >= 0 && d->act <= 4, "gemm: bad act %d", d->act);
-    AV_CHECK(d->act != ACT_F32OUT || (d->rowvec == nullptr && d->R == nullptr && d->N % 4 == 0 && d->ldc % 4 == 0),
-             "gemm: fp32 output supports bias only and needs N, ldc multiples of 4");
-    AV_CHECK(d->asym == 0 || d->asym == 1, "gemm: asym must be 0 or 1");
-    AV_CHECK(d->C1 == 0 || d->A1 != nullptr, "gemm: C1 > 0 but A1 is null");
-    AV_CHECK(d->rowvec == nullptr || d->rowvec_div > 0, "gemm: rowvec needs rowvec_div > 0");
-    if (d->mode == MODE_CONV2D) {
-        AV_CHECK(d->Hi > 0 && d->Wi > 0 && d->Ho > 0 && d->Wo > 0 && (d->stride == 1 || d->stride == 2),
-                 "gemm: bad conv geometry");
-        AV_CHECK(d->M % (d->Ho * d->Wo) == 0, "gemm: M not a multiple of Ho*Wo");
-        AV_CHECK(d->up == 0 || d->up == 1, "gemm: up must be 0 or 1");
-    }
-    if (d->mode == MODE_TEMPORAL) {
-        AV_CHECK(d->F > 0 && d->HW > 0 && d->M % (d->F * d->HW) == 0, "gemm: bad temporal geometry");
-    }
-    if (d->act == ACT_GEGLU) {
-        AV_CHECK(d->N % 32 == 0, "gemm: GEGLU needs N %% 32 == 0");
-        AV_CHECK(d->rowvec == nullptr, "gemm: GEGLU with rowvec unsupported");
-    }
-    GemmK k;
+    AV_CHECK(d->A0 && d->W && d->C, "gemm: null A0/W/C");
+    const int hinted = av_hint_rows(d->M);
+    const GemmPlan plan = av_gemm_plan(*d, hinted);
+    // (in front of the plan's own status and over its text: a LayerNorm-fold launch with gn_stats set hears about gn_stats first)
+    AV_CHECK(d->gn_stats == nullptr || plan.gn_decline == nullptr,
+             "gemm: gn_stats set, but this launch runs on %s, which writes no GroupNorm statistics (ask anyv2v_gemm_gn_stats_floats first)",
+             plan.gn_decline);
+    if (plan.status != ANYV2V_OK) return plan.status;
+    GemmK k = {};   // (trace, gn_* and what the plan leaves 0 stay off)
     k.A0 = (const half_t*)d->A0;
     k.A1 = d->C1 > 0 ? (const half_t*)d->A1 : (const half_t*)d->A0;
     k.W = (const half_t*)d->W;
@@ -1502,56 +1277,36 @@ static int gemm_impl(const AnyV2VGemmDesc* d, void* stream, int* gn_query) {
     k.mode = d->mode; k.Hi = d->Hi; k.Wi = d->Wi; k.Ho = d->Ho; k.Wo = d->Wo; k.stride = d->stride; k.up = d->up;
     k.F = d->F; k.HW = d->HW; k.act = d->act;
     k.pad_lo = d->asym ? 0 : 1;
-    k.taps = d->mode == MODE_LINEAR ? 1 : (d->mode == MODE_CONV2D ? 9 : 3);
-    k.Ktot = k.taps * (d->C0 + d->C1);
-    k.nt0 = d->C0 / 64;
-    k.nt1 = d->C1 / 64;
-    k.tilesN = 1;
-    k.splits = 1;
-    k.partial = nullptr;
-    k.trace = nullptr;
-    k.ln_c1 = nullptr;
-    k.ln_eps = 0.f;
-    k.rast_gm = k.rast_gn = k.rast_sm = k.rast_sn = k.rast_nfast = 0;
-    k.gn_stats = nullptr;
-    k.gn_groups = k.gn_cg = 0;
-    k.vec_epi = (((uintptr_t)d->bias & 7) == 0) && (((uintptr_t)d->rowvec & 7) == 0) && (d->ldrv % 4 == 0) && (d->N % 4 == 0);
+    k.taps = plan.taps; k.Ktot = k.taps * (d->C0 + d->C1); k.nt0 = d->C0 / 64; k.nt1 = d->C1 / 64;
+    k.tilesN = plan.tilesN; k.vec_epi = plan.vec_epi; k.splits = plan.splits;
+    if (plan.splits > 1 || plan.family == GEMM_SW_STREAMK) k.partial = (float*)d->workspace;
+    if (plan.family == GEMM_WS_LN) k.ln_c1 = d->ln_c1, k.ln_eps = d->ln_eps;
+    k.rast_gm = plan.rast_gm; k.rast_gn = plan.rast_gn; k.rast_sm = plan.rast_sm; k.rast_sn = plan.rast_sn; k.rast_nfast = plan.rast_nfast;
+    if (d->gn_stats != nullptr) {   // (plan.gn_records holds: checked above)
+        AV_CHECK(d->gn_stats_floats >= (int64_t)3 * (d->M / 16) * d->gn_groups, "gemm: gn_stats holds %lld floats, the launch writes %lld",
+                 (long long)d->gn_stats_floats, (long long)3 * (d->M / 16) * d->gn_groups);
+        AV_CHECK((((uintptr_t)d->gn_stats) & 3) == 0, "gemm: gn_stats must be 4-byte aligned");
+        k.gn_stats = d->gn_stats;
+        k.gn_groups = d->gn_groups;
+        k.gn_cg = d->N / d->gn_groups;
+        ++g_gn_launches;
+    }
+    // ANYV2V_GEMM_LOG=1: one line per launch plan on stderr (diagnostics: which launches split, and how, under a batch hint)
+    static const bool log_on = getenv("ANYV2V_GEMM_LOG") != nullptr;
+    if (log_on)
+        fprintf(stderr, "gemm-plan mode %d M %d (hinted %d) N %d K %d act %d res %d big %d splits %d kernel %s nf %d grid %d\n", d->mode, d->M,
+                hinted, d->N, k.Ktot, d->act, d->R != nullptr, plan.family == GEMM_BIG, plan.splits, av_gemm_family_name(plan.family),
+                plan.nf, plan.grid);
     hipStream_t s = (hipStream_t)stream;
-
-    const bool geglu = d->act == ACT_GEGLU;
-    const bool fast = !(d->flags & 1) && d->C0 % 64 == 0 && d->C1 % 64 == 0 && d->lda0 % 8 == 0 &&
-                      (d->C1 == 0 || d->lda1 % 8 == 0) && d->ldc % 8 == 0 && av_aligned16(d->A0) &&
-                      (d->C1 == 0 || av_aligned16(d->A1)) && av_aligned16(d->W) && av_aligned16(d->C) &&
-                      (d->R == nullptr || (d->ldr % 8 == 0 && av_aligned16(d->R))) && (!geglu || d->N % 128 == 0) &&
-                      k.vec_epi;
-    // K = 320 Linear layers with many rows (the 64x64 level): weight-stationary streaming kernel (gemm_ws.hip).
-    // flags bit9 (512): never, bit10 (1024): whenever the shape allows (tests; small M leaves most waves idle)
-    if (d->ln_c1 != nullptr) {   // LayerNorm folded into the GEMM: only the weight-stationary kernel implements it
-        AV_GN_DECLINE("the LayerNorm-fold kernel");
-        if (!(fast && (d->flags & 2) && !(d->flags & 1) && av_gemm_ws_eligible(d) && (((uintptr_t)d->ln_c1) & 15) == 0)) {
-            anyv2v_set_error("gemm: ln_c1 (LayerNorm fold) needs mode 0, C0 = 320 (N %% 160 = 0) or C0 = 512 with GEGLU (N %% 128 = 0), no "
-                             "residual / rowvec, 16-byte aligned operands -- got C0 %d N %d act %d", d->C0, d->N, d->act);
-            return ANYV2V_EUNSUPPORTED;
-        }
-        return av_gemm_ws_launch(k, d, s);
-    }
-    if (fast && (d->flags & 2) && !(d->flags & (512 | 4 | 1)) && av_gemm_ws_eligible(d) &&
-        (av_hint_rows(d->M) >= 32768 || (d->flags & 1024))) {
-        AV_GN_DECLINE("the weight-stationary kernel");
-        return av_gemm_ws_launch(k, d, s);
-    }
-    if (d->mode == MODE_CONV2D) return dispatch<MODE_CONV2D>(k, d, fast, s, gn_query);
-    if (d->mode == MODE_TEMPORAL) return dispatch<MODE_TEMPORAL>(k, d, fast, s, gn_query);
-    return dispatch<MODE_LINEAR>(k, d, fast, s, gn_query);
+    if (d->mode == MODE_CONV2D) return launch<MODE_CONV2D>(k, d, plan, s);
+    if (d->mode == MODE_TEMPORAL) return launch<MODE_TEMPORAL>(k, d, plan, s);
+    return launch<MODE_LINEAR>(k, d, plan, s);
 }
-#undef AV_GN_DECLINE
-
-extern "C" int anyv2v_gemm_f16(const AnyV2VGemmDesc* d, void* stream) { return gemm_impl(d, stream, nullptr); }
 
 extern "C" int64_t anyv2v_gemm_gn_stats_floats(const AnyV2VGemmDesc* d) {
-    int can = 0;
-    if (d == nullptr || gemm_impl(d, nullptr, &can) != ANYV2V_OK || !can) return 0;
-    return (int64_t)3 * (d->M / 16) * d->gn_groups;
+    if (d == nullptr) return 0;
+    const GemmPlan plan = av_gemm_plan(*d, av_hint_rows(d->M));   // plans only: touches no device
+    return plan.status == ANYV2V_OK && plan.gn_records ? (int64_t)3 * (d->M / 16) * d->gn_groups : 0;
 }
 
 extern "C" int64_t anyv2v_gemm_gn_launches(int32_t reset) {

@@ -1,10 +1,7 @@
 // Definitions shared by the GEMM translation units (gemm.hip, gemm_ws.hip): kernel argument block, gather addressing.
 #pragma once
 #include "common.h"
-
-enum { MODE_LINEAR = 0, MODE_CONV2D = 1, MODE_TEMPORAL = 2 };
-enum { ACT_NONE = 0, ACT_SILU = 1, ACT_GELU = 2, ACT_GEGLU = 3, ACT_F32OUT = 4 };
-
+#include "gemm_plan.h"   // MODE_*, ACT_*, GemmPlan
 
 struct GemmK {
     const half_t* A0;
@@ -22,7 +19,7 @@ struct GemmK {
     int vec_epi;  // bias / rowvec may be read as 8-byte vectors
     int splits;   // split-K factor (128-row kernel only): each split writes an fp32 partial tile, reduced afterwards
     float* partial;  // [splits][M][N] fp32 workspace
-    long long* trace;  // debug (flags bit5): 32 timestamps per block, see tools/gemm_trace.py
+    long long* trace;  // debug (ANYV2V_GEMM_PROBE_TRACE): 32 timestamps per block, see tools/gemm_trace.py
     const float* ln_c1;  // LayerNorm fold (gemm_ws.hip): column sums of the gamma-scaled weights, or nullptr
     float ln_eps;
     // persistent kernel, rastered tile order (0 = classic): an XCD round covers rast_gm x rast_gn output tiles; rast_sm x rast_sn
@@ -137,7 +134,8 @@ __device__ __forceinline__ void gn_slab_records(const half_t* slab, int ld, int 
     }
 }
 
-// ---- weight-stationary kernel (gemm_ws.hip): launch plan + host entry points used by gemm.hip's dispatch ----
+// ---- launchers of the kernels outside gemm.hip: k filled by anyv2v_gemm_f16 from the descriptor and the plan (tiles, grid, raster) ----
+// weight-stationary kernel (gemm_ws.hip): how (slab, row range) are dealt to the 256 blocks
 struct WsPlan {
     int S;        // 160-column W slabs (= blocks per row range)
     int px;       // row ranges per XCD (px * S <= 32 blocks of the 32 CUs of an XCD)
@@ -145,17 +143,9 @@ struct WsPlan {
     int spr;      // strips per row range
     int trace_waves;  // probe build: waves of a block that work (8; 4 / 1 = one wave per SIMD / per CU), tools/gemm_ws_trace.py
 };
-bool av_gemm_ws_eligible(const AnyV2VGemmDesc* d);
-int av_gemm_ws_launch(const GemmK& k, const AnyV2VGemmDesc* d, hipStream_t s);
-
-// ---- one-wave-per-SIMD persistent kernel (gemm_sw.hip): 192 x 320 tiles, 4 waves, direct 16-byte stores ----
-bool av_gemm_sw_eligible(const AnyV2VGemmDesc* d);
-int av_gemm_sw_launch(GemmK& k, const AnyV2VGemmDesc* d, hipStream_t s);
-// stream-K form (flags bit26 allows it, bit27 forces it): blocks to launch (0 = do not take it), its workspace need, the launch
-int av_gemm_sw_sk_blocks(const AnyV2VGemmDesc* d, bool force);
-size_t av_gemm_sw_sk_workspace(int blocks);
-int av_gemm_sw_sk_launch(GemmK& k, const AnyV2VGemmDesc* d, int blocks, hipStream_t s);
-
-// ---- 3x3 convolution with the A operand reused from LDS across the dx taps (gemm_swh.hip): flags bit28 takes it where eligible ----
-bool av_gemm_swh_eligible(const AnyV2VGemmDesc* d);
-int av_gemm_swh_launch(GemmK& k, const AnyV2VGemmDesc* d, hipStream_t s);
+int av_gemm_ws_launch(const GemmK& k, const AnyV2VGemmDesc* d, const GemmPlan& plan, hipStream_t s);
+// one-wave-per-SIMD persistent kernel (gemm_sw.hip): 192 x 320 tiles, 4 waves, direct 16-byte stores; its stream-K form
+int av_gemm_sw_launch(const GemmK& k, const AnyV2VGemmDesc* d, const GemmPlan& plan, hipStream_t s);
+int av_gemm_sw_sk_launch(const GemmK& k, const AnyV2VGemmDesc* d, const GemmPlan& plan, hipStream_t s);
+// 3x3 convolution with the A operand reused from LDS across the dx taps (gemm_swh.hip)
+int av_gemm_swh_launch(const GemmK& k, const AnyV2VGemmDesc* d, const GemmPlan& plan, hipStream_t s);

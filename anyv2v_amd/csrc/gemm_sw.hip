@@ -684,30 +684,25 @@ __global__ __launch_bounds__(256) void gemm_sw_fixup_kernel(const GemmK p, int G
 }
 
 // ---------------------------------------------------------------------------------------------------------
-bool av_gemm_sw_eligible(const AnyV2VGemmDesc* d) {
-    const bool geglu = d->act == ACT_GEGLU;
-    const int nk = (d->mode == MODE_LINEAR ? 1 : (d->mode == MODE_CONV2D ? 9 : 3)) * ((d->C0 + d->C1) / 64);
-    return d->N % 320 == 0 && (geglu ? d->mode == MODE_LINEAR && d->R == nullptr && d->rowvec == nullptr : d->act == ACT_NONE) &&
-           !(d->R != nullptr && d->rowvec != nullptr) && nk >= 2 && d->ldc % 8 == 0 && (d->R == nullptr || d->ldr % 8 == 0) &&
-           (d->rowvec == nullptr || d->ldrv % 8 == 0);
-}
+// host side (eligibility, tiles, grid and tile order: gemm_plan.cpp)
+static_assert(SW_BM == AV_GEMM_BM && SW_BN == AV_GEMM_BN, "the plan counts tiles of this size");
 
-template <int MODE>
+template <int MODE, bool SK>
 static void sw_launch_mode(const GemmK& k, const AnyV2VGemmDesc* d, dim3 grid, hipStream_t s) {
     if constexpr (MODE == MODE_LINEAR) {
         if (d->act == ACT_GEGLU) {
-            hipLaunchKernelGGL((gemm_sw_kernel<MODE_LINEAR, 2>), grid, dim3(256), 0, s, k);
+            hipLaunchKernelGGL((gemm_sw_kernel<MODE_LINEAR, 2, 0, SK>), grid, dim3(256), 0, s, k);
             return;
         }
     }
 #ifdef ANYV2V_EXPERIMENTS
-    if constexpr (MODE == MODE_CONV2D) {
-        const int ko = (d->flags >> 23) & 15;
+    if constexpr (MODE == MODE_CONV2D && !SK) {
+        const int ko = (d->flags >> ANYV2V_GEMM_PROBE_SW_KO_SHIFT) & 15;
         if (ko == 7 && d->R == nullptr) { hipLaunchKernelGGL((gemm_sw_kernel<MODE, 0, 7>), grid, dim3(256), 0, s, k); return; }
         if (ko == 8 && d->R == nullptr) { hipLaunchKernelGGL((gemm_sw_kernel<MODE, 0, 8>), grid, dim3(256), 0, s, k); return; }
     }
-    if constexpr (MODE == MODE_LINEAR) {
-        const int ko = (d->flags >> 23) & 7;
+    if constexpr (MODE == MODE_LINEAR && !SK) {
+        const int ko = (d->flags >> ANYV2V_GEMM_PROBE_SW_KO_SHIFT) & 7;
         if (ko == 1) { hipLaunchKernelGGL((gemm_sw_kernel<MODE, 0, 1>), grid, dim3(256), 0, s, k); return; }
         if (ko == 2) { hipLaunchKernelGGL((gemm_sw_kernel<MODE, 0, 2>), grid, dim3(256), 0, s, k); return; }
         if (ko == 3) { hipLaunchKernelGGL((gemm_sw_kernel<MODE, 0, 3>), grid, dim3(256), 0, s, k); return; }
@@ -717,90 +712,39 @@ static void sw_launch_mode(const GemmK& k, const AnyV2VGemmDesc* d, dim3 grid, h
     }
 #endif
     if (d->R != nullptr)
-        hipLaunchKernelGGL((gemm_sw_kernel<MODE, 1>), grid, dim3(256), 0, s, k);
+        hipLaunchKernelGGL((gemm_sw_kernel<MODE, 1, 0, SK>), grid, dim3(256), 0, s, k);
     else
-        hipLaunchKernelGGL((gemm_sw_kernel<MODE, 0>), grid, dim3(256), 0, s, k);
+        hipLaunchKernelGGL((gemm_sw_kernel<MODE, 0, 0, SK>), grid, dim3(256), 0, s, k);
+}
+template <bool SK>
+static void sw_launch_any(const GemmK& k, const AnyV2VGemmDesc* d, dim3 grid, hipStream_t s) {
+    if (d->mode == MODE_CONV2D)
+        sw_launch_mode<MODE_CONV2D, SK>(k, d, grid, s);
+    else if (d->mode == MODE_TEMPORAL)
+        sw_launch_mode<MODE_TEMPORAL, SK>(k, d, grid, s);
+    else
+        sw_launch_mode<MODE_LINEAR, SK>(k, d, grid, s);
 }
 
-// k: filled by anyv2v_gemm_f16 (tilesN / raster fields set here)
-int av_gemm_sw_launch(GemmK& k, const AnyV2VGemmDesc* d, hipStream_t s) {
-    const int tiles = ((d->M + SW_BM - 1) / SW_BM) * (d->N / 320);
-    k.tilesN = d->N / 320;
-    int gmax = 256;
+int av_gemm_sw_launch(const GemmK& k_in, const AnyV2VGemmDesc* d, const GemmPlan& plan, hipStream_t s) {
+    GemmK k = k_in;
+    dim3 grid((unsigned)plan.grid);
 #ifdef ANYV2V_EXPERIMENTS   // probe (tools/gemm_sw_grid_probe.py): fewer persistent blocks = fewer CUs share the L2 / fabric
-    if (const char* e = getenv("ANYV2V_SW_GRID")) gmax = atoi(e) > 0 ? atoi(e) : 256;
-#endif
-    const dim3 grid(tiles < gmax ? tiles : gmax);
-    {   // tile order of wide-N launches: as gemm_big_kernel's dispatch (flags bits 13-16)
-        const int code = (d->flags >> 13) & 7;
-        static const int gm_of[8] = {0, 0, 4, 8, 16, 32, 2, 0};
-        int gm = gm_of[code];
-        if (code == 0 && k.tilesN >= 8 && tiles >= 512) gm = 8;
-        const int tm = (d->M + SW_BM - 1) / SW_BM;
-        if (gm > 0 && grid.x == 256 && k.tilesN % (32 / gm) == 0) {
-            k.rast_gm = gm;
-            k.rast_gn = 32 / gm;
-            k.rast_sm = (tm + gm - 1) / gm;
-            k.rast_sn = k.tilesN / k.rast_gn;
-            k.rast_nfast = (d->flags >> 16) & 1;
-        }
+    if (const char* e = getenv("ANYV2V_SW_GRID")) {
+        if (atoi(e) > 0) grid.x = plan.tiles < atoi(e) ? plan.tiles : atoi(e);
+        if (grid.x != 256) k.rast_gm = k.rast_gn = k.rast_sm = k.rast_sn = k.rast_nfast = 0;   // (the tile order needs 256 blocks)
     }
-    if (d->mode == MODE_CONV2D)
-        sw_launch_mode<MODE_CONV2D>(k, d, grid, s);
-    else if (d->mode == MODE_TEMPORAL)
-        sw_launch_mode<MODE_TEMPORAL>(k, d, grid, s);
-    else
-        sw_launch_mode<MODE_LINEAR>(k, d, grid, s);
+#endif
+    sw_launch_any<false>(k, d, grid, s);
     return av_launch_status("gemm_sw");
 }
 
-// ---- stream-K form -------------------------------------------------------------------------------------
-// Workspace: two fp32 slabs of 192 x 320 per block of the main launch.
-size_t av_gemm_sw_sk_workspace(int blocks) { return (size_t)2 * blocks * SW_BM * SW_BN * sizeof(float); }
-
-// Blocks the stream-K form would use, or 0 when it should not be taken: the launch's (tile, K-tile) units are dealt evenly to
-// min(256, units / 4) blocks.  It pays where whole tiles quantise badly onto 256 CUs (tiles / (rounds x 256) below ~0.9) and every
-// block still gets a few K-tiles.
-int av_gemm_sw_sk_blocks(const AnyV2VGemmDesc* d, bool force) {
-    const int tiles = ((d->M + SW_BM - 1) / SW_BM) * (d->N / 320);
-    const int nk = (d->mode == MODE_LINEAR ? 1 : (d->mode == MODE_CONV2D ? 9 : 3)) * ((d->C0 + d->C1) / 64);
-    const long long U = (long long)tiles * nk;
-    if (U < 256 * 4 || U > (1ll << 22)) return force && U >= 8 ? (int)(U / 4 < 256 ? U / 4 : 256) : 0;
-    if (force) return 256;
-    const int rounds = (tiles + 255) / 256;
-    const double eff = (double)tiles / (rounds * 256.0);
-    return eff < 0.9 ? 256 : 0;
-}
-
-template <int MODE>
-static void sw_sk_launch_mode(const GemmK& k, const AnyV2VGemmDesc* d, dim3 grid, hipStream_t s) {
-    if constexpr (MODE == MODE_LINEAR) {
-        if (d->act == ACT_GEGLU) {
-            hipLaunchKernelGGL((gemm_sw_kernel<MODE_LINEAR, 2, 0, true>), grid, dim3(256), 0, s, k);
-            return;
-        }
-    }
-    if (d->R != nullptr)
-        hipLaunchKernelGGL((gemm_sw_kernel<MODE, 1, 0, true>), grid, dim3(256), 0, s, k);
-    else
-        hipLaunchKernelGGL((gemm_sw_kernel<MODE, 0, 0, true>), grid, dim3(256), 0, s, k);
-}
-
-int av_gemm_sw_sk_launch(GemmK& k, const AnyV2VGemmDesc* d, int blocks, hipStream_t s) {
-    const int tiles = ((d->M + SW_BM - 1) / SW_BM) * (d->N / 320);
-    const int nk = k.taps * (k.nt0 + k.nt1);
-    k.tilesN = d->N / 320;
-    k.partial = (float*)d->workspace;
-    const dim3 grid(blocks);
-    if (d->mode == MODE_CONV2D)
-        sw_sk_launch_mode<MODE_CONV2D>(k, d, grid, s);
-    else if (d->mode == MODE_TEMPORAL)
-        sw_sk_launch_mode<MODE_TEMPORAL>(k, d, grid, s);
-    else
-        sw_sk_launch_mode<MODE_LINEAR>(k, d, grid, s);
+// stream-K form (blocks and workspace need: gemm_plan.cpp): the main launch, then the fix-up of the tiles a range boundary cut
+int av_gemm_sw_sk_launch(const GemmK& k, const AnyV2VGemmDesc* d, const GemmPlan& plan, hipStream_t s) {
+    sw_launch_any<true>(k, d, dim3((unsigned)plan.sk_blocks), s);
     if (d->act == ACT_GEGLU)
-        hipLaunchKernelGGL((gemm_sw_fixup_kernel<true>), dim3(tiles), dim3(256), 0, s, k, blocks, nk);
+        hipLaunchKernelGGL((gemm_sw_fixup_kernel<true>), dim3(plan.tiles), dim3(256), 0, s, k, plan.sk_blocks, plan.nk);
     else
-        hipLaunchKernelGGL((gemm_sw_fixup_kernel<false>), dim3(tiles), dim3(256), 0, s, k, blocks, nk);
+        hipLaunchKernelGGL((gemm_sw_fixup_kernel<false>), dim3(plan.tiles), dim3(256), 0, s, k, plan.sk_blocks, plan.nk);
     return av_launch_status("gemm_sw<stream-K>");
 }

@@ -375,12 +375,8 @@ __global__ __launch_bounds__(256, 1) void gemm_swh_kernel(const GemmK p) {
 }
 
 // ---------------------------------------------------------------------------------------------------------
-bool av_gemm_swh_eligible(const AnyV2VGemmDesc* d) {
-    return d->mode == MODE_CONV2D && d->stride == 1 && d->up == 0 && d->asym == 0 && d->Hi == d->Ho && d->Wi == d->Wo &&
-           (d->Wi == 16 || d->Wi == 32 || d->Wi == 64) && d->N % 320 == 0 && d->act == ACT_NONE && d->C0 % 64 == 0 && d->C1 % 64 == 0 &&
-           !(d->R != nullptr && d->rowvec != nullptr) && d->ldc % 8 == 0 && (d->R == nullptr || d->ldr % 8 == 0) &&
-           (d->rowvec == nullptr || d->ldrv % 8 == 0) && (long long)d->M * 1 < (1ll << 31);
-}
+// host side (eligibility, tiles and grid: gemm_plan.cpp)
+static_assert(SWH_BM == AV_GEMM_BM && SWH_BN == AV_GEMM_BN, "the plan counts tiles of this size");
 
 template <int WI>
 static void swh_launch_w(const GemmK& k, const AnyV2VGemmDesc* d, dim3 grid, hipStream_t s) {
@@ -390,10 +386,8 @@ static void swh_launch_w(const GemmK& k, const AnyV2VGemmDesc* d, dim3 grid, hip
         hipLaunchKernelGGL((gemm_swh_kernel<WI, 0>), grid, dim3(256), 0, s, k);
 }
 
-int av_gemm_swh_launch(GemmK& k, const AnyV2VGemmDesc* d, hipStream_t s) {
-    const int tiles = ((d->M + SWH_BM - 1) / SWH_BM) * (d->N / 320);
-    k.tilesN = d->N / 320;
-    const dim3 grid(tiles < 256 ? tiles : 256);
+int av_gemm_swh_launch(const GemmK& k, const AnyV2VGemmDesc* d, const GemmPlan& plan, hipStream_t s) {
+    const dim3 grid((unsigned)plan.grid);
     if (d->Wi == 64)
         swh_launch_w<64>(k, d, grid, s);
     else if (d->Wi == 32)

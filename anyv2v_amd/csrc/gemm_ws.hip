@@ -296,37 +296,21 @@ __global__ __launch_bounds__(512) void gemm_ws_kernel(const GemmK p, const WsPla
     }
 }
 
-// host side: can this launch run on the weight-stationary kernel, and how are (slab, row range) dealt to the 256 blocks
-static int ws_slab_cols(const AnyV2VGemmDesc* d) {   // 0 = shape not covered
-    if (d->C0 == 320) return 160;
-    // K = 512 (transformer_in): GEGLU with 128-column slabs (1291 -> 834 us at 196608 rows); plain launches would need 64-column
-    // slabs (128 + their epilogue slabs exceed LDS), which only pays for N = 512 (x 1.07-1.16; QKV N = 1536: x 0.87-0.96, left to
-    // the tile kernels) -- profiles/r03_gemm_ws_ab.txt
-    if (d->C0 == 512) return d->act == ACT_GEGLU ? 128 : (d->N == 512 ? 64 : 0);
-    return 0;
-}
-
-bool av_gemm_ws_eligible(const AnyV2VGemmDesc* d) {
-    const int ns = ws_slab_cols(d);
-    if (d->ln_c1 != nullptr && (d->R != nullptr || (d->C0 == 512 && d->act != ACT_GEGLU))) return false;
-    return d->mode == MODE_LINEAR && ns > 0 && d->C1 == 0 && d->N % ns == 0 && d->N / ns <= 32 &&
-           (d->act == ACT_NONE || (d->act == ACT_GEGLU && d->R == nullptr)) && d->rowvec == nullptr && d->M > 0;
-}
-
-int av_gemm_ws_launch(const GemmK& k_in, const AnyV2VGemmDesc* d, hipStream_t s) {
+// host side (eligibility and slab width: gemm_plan.cpp): how (slab, row range) are dealt to the 256 blocks
+int av_gemm_ws_launch(const GemmK& k_in, const AnyV2VGemmDesc* d, const GemmPlan& gp, hipStream_t s) {
     GemmK k = k_in;
     WsPlan plan;
-    const int ns = ws_slab_cols(d);
-    plan.S = d->N / ns;
+    plan.S = gp.tilesN;
     plan.px = 32 / plan.S;
     plan.nstrips = (d->M + WS_RW - 1) / WS_RW;
     const int nranges = 8 * plan.px;
     plan.spr = (plan.nstrips + nranges - 1) / nranges;
-    plan.trace_waves = (d->flags & 8192) ? 4 : ((d->flags & 16384) ? 1 : 8);
+    // (probe build: bits 13 / 14, the two low bits of the raster field this kernel has no use for, leave 4 / 1 waves working)
+    plan.trace_waves = (d->flags & (1 << ANYV2V_GEMM_RASTER_SHIFT)) ? 4 : ((d->flags & (2 << ANYV2V_GEMM_RASTER_SHIFT)) ? 1 : 8);
     const bool geglu = d->act == ACT_GEGLU, res = d->R != nullptr;
-#define WS_GO(K, NS, G, RS, R, Q, E, T) hipLaunchKernelGGL((gemm_ws_kernel<K, NS, G, RS, R, Q, E, T>), dim3(256), dim3(512), 0, s, k, plan)
-#ifdef ANYV2V_EXPERIMENTS  // probe build only: per-strip phase timestamps (flags bit5), tools/gemm_ws_trace.py
-    if ((d->flags & 32) && d->C0 == 320 && d->workspace != nullptr && (size_t)256 * 2 * 16 * sizeof(long long) <= (size_t)d->workspace_bytes) {
+#define WS_GO(K, NS, G, RS, R, Q, E, T) hipLaunchKernelGGL((gemm_ws_kernel<K, NS, G, RS, R, Q, E, T>), dim3(gp.grid), dim3(512), 0, s, k, plan)
+#ifdef ANYV2V_EXPERIMENTS  // probe build only: per-strip phase timestamps, tools/gemm_ws_trace.py
+    if ((d->flags & ANYV2V_GEMM_PROBE_TRACE) && d->C0 == 320 && d->workspace != nullptr && (size_t)256 * 2 * 16 * sizeof(long long) <= (size_t)d->workspace_bytes) {
         k.trace = (long long*)d->workspace;
         if (geglu) WS_GO(320, 160, true, false, 5, 8, false, true);
         else if (res) WS_GO(320, 160, false, true, 10, 4, false, true);
@@ -336,10 +320,8 @@ int av_gemm_ws_launch(const GemmK& k_in, const AnyV2VGemmDesc* d, hipStream_t s)
 #endif
     // (A/B in profiles/r03_gemm_ws_ab.txt: ring depth 5 vs 10, weight look-ahead 3 vs 7, residual requested first vs after the
     //  K loop -- all within 3 % except: pairs matter for QKV at 196608 rows, the late residual request for the +residual launches)
-    if (d->ln_c1 != nullptr) {   // LayerNorm folded in (QKV / to_q / GEGLU-up of the transformer blocks)
-        k.ln_c1 = d->ln_c1;
-        k.ln_eps = d->ln_eps;
-#define WS_GO_LN(K, NS, G, R, Q) hipLaunchKernelGGL((gemm_ws_kernel<K, NS, G, false, R, Q, false, false, true>), dim3(256), dim3(512), 0, s, k, plan)
+    if (gp.family == GEMM_WS_LN) {   // LayerNorm folded in (QKV / to_q / GEGLU-up of the transformer blocks)
+#define WS_GO_LN(K, NS, G, R, Q) hipLaunchKernelGGL((gemm_ws_kernel<K, NS, G, false, R, Q, false, false, true>), dim3(gp.grid), dim3(512), 0, s, k, plan)
         if (d->C0 == 320) {
             if (geglu) WS_GO_LN(320, 160, true, 5, 4);
             else WS_GO_LN(320, 160, false, 10, 4);

@@ -16,7 +16,7 @@ ACT_NONE, ACT_SILU, ACT_GELU, ACT_GEGLU, ACT_F32OUT = 0, 1, 2, 3, 4
 # global knobs (tests flip them to cross-check kernel variants)
 FORCE_NAIVE = False   # route GEMM / attention through the reference-grade kernels
 ATTN_FLAGS = int(os.environ.get("ANYV2V_ATTN_FLAGS", "0"))  # bit1 (2): no short kernel; bit3 (8): PnP launches as per-branch aliasing (no shared-softmax kernel)
-GEMM_FLAGS = int(os.environ.get("ANYV2V_GEMM_FLAGS", "0"))  # bit2 (4): no persistent 192x320 kernel; bit3 (8): force it; bit4 (16): no split-K
+GEMM_FLAGS = int(os.environ.get("ANYV2V_GEMM_FLAGS", "0"))  # an integer of _lib.ANYV2V_GEMM_* bits (include/anyv2v_hip.h), e.g. 4: NO_BIG, 16: NO_SPLITK
 USE_GLDS = os.environ.get("ANYV2V_GLDS", "1") == "1"   # LDS-DMA (global_load_lds) staging variant of the GEMM
 
 
@@ -134,7 +134,8 @@ def gemm(a0: torch.Tensor, w: torch.Tensor, *, a1: Optional[torch.Tensor] = None
     elif mode == MODE_TEMPORAL:
         d.F, d.HW = temporal
     d.act = act
-    d.flags = (1 if (naive or FORCE_NAIVE) else 0) | (2 if USE_GLDS else 0) | GEMM_FLAGS
+    d.flags = ((_lib.ANYV2V_GEMM_NAIVE if (naive or FORCE_NAIVE) else 0) | (_lib.ANYV2V_GEMM_LDS_DMA if USE_GLDS else 0)
+               | GEMM_FLAGS)
     if ln is not None:
         c1, eps = ln
         assert c1.dtype == torch.float32 and c1.is_cuda and c1.numel() >= N and c1.is_contiguous()
@@ -236,7 +237,7 @@ def ln_gemm_supported(M: int, K: int, N: int, act: int = ACT_NONE, hinted: bool 
     """Shapes for which ``gemm(..., ln=...)`` runs (the weight-stationary kernel, gemm_ws.hip) AND pays: the 64x64 level's row
     counts.  Mirrors the library's own check; everything else runs ``layernorm`` + ``gemm``.  ``hinted=False``: ``M`` is already a
     canonical row count (one branch's rows) and is compared as it is, whatever batch hint is in force."""
-    if FORCE_NAIVE or not USE_GLDS or (GEMM_FLAGS & (512 | 4)) or (M * _HINT[0] // _HINT[1] if hinted else M) < 32768:
+    if FORCE_NAIVE or not USE_GLDS or (GEMM_FLAGS & (_lib.ANYV2V_GEMM_NO_WS | _lib.ANYV2V_GEMM_NO_BIG)) or (M * _HINT[0] // _HINT[1] if hinted else M) < 32768:
         return False
     if K == 320:
         return N % 160 == 0 and N // 160 <= 32

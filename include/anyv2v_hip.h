@@ -45,6 +45,32 @@ extern "C" {
  *                logits of the VAE mid-block's single 512-wide head;
  *           + R[m, n] (residual, pnp_utils.py:124); store fp16.
  */
+/* AnyV2VGemmDesc.flags.  All but LDS_DMA are A/B switches and test hooks, off by default; unnamed bits are ignored. */
+#define ANYV2V_GEMM_NAIVE (1 << 0)         /* Run the naive reference kernel. */
+#define ANYV2V_GEMM_LDS_DMA (1 << 1)       /* Stage operands by LDS-DMA; only the 128-row and naive kernels run without it. */
+#define ANYV2V_GEMM_NO_BIG (1 << 2)        /* Never take the persistent 192x320 kernel, nor the weight-stationary one. */
+#define ANYV2V_GEMM_FORCE_BIG (1 << 3)     /* Take the persistent kernel whenever the shape allows. */
+#define ANYV2V_GEMM_NO_SPLITK (1 << 4)     /* Never split along K. */
+#define ANYV2V_GEMM_PROBE_TRACE (1 << 5)   /* Probe build: phase timestamps; ignored by the product library. */
+#define ANYV2V_GEMM_PROBE_KO_SHIFT 6       /* Bits 6-8, probe build: K-loop knock-outs; ignored by the product library. */
+#define ANYV2V_GEMM_NO_WS (1 << 9)         /* Never take the weight-stationary kernel. */
+#define ANYV2V_GEMM_FORCE_WS (1 << 10)     /* Take it wherever it is implemented, also below its M >= 32768 threshold. */
+#define ANYV2V_GEMM_NF4 (1 << 11)          /* 128-column tiles in the 128-row kernel whatever the fill heuristic says. */
+#define ANYV2V_GEMM_NF5 (1 << 12)          /* 160-column tiles likewise. */
+#define ANYV2V_GEMM_RASTER_SHIFT 13        /* Bits 13-15, persistent kernels' tile order: 0 auto, 1 classic, 2..6 super-tiles of
+                                              4 / 8 / 16 / 32 / 2 M-tiles per XCD round; same bits in every order. */
+#define ANYV2V_GEMM_RASTER_NFAST (1 << 16) /* Walk the super-tiles N-fastest. */
+#define ANYV2V_GEMM_PP (1 << 17)           /* Take the ping-pong kernel wherever the shape allows (N % 320 = 0, no GEGLU). */
+#define ANYV2V_GEMM_NO_PP (1 << 18)        /* Never take it. */
+#define ANYV2V_GEMM_PP_192 (1 << 19)       /* Its 192-row tile. */
+#define ANYV2V_GEMM_PP_256 (1 << 20)       /* Its 256-row tile. */
+#define ANYV2V_GEMM_SW (1 << 21)           /* Take the one-wave-per-SIMD kernel wherever the shape allows (N % 320 = 0, K >= 128). */
+#define ANYV2V_GEMM_NO_SW (1 << 22)        /* Never take it, its stream-K form or the LDS-patch kernel. */
+#define ANYV2V_GEMM_PROBE_SW_KO_SHIFT 23   /* Bits 23-25, probe build: its knock-outs / K orders; ignored by the product library. */
+#define ANYV2V_GEMM_STREAMK (1 << 26)      /* Allow the stream-K form where it pays (un-hinted, 126 MB workspace; another summation order). */
+#define ANYV2V_GEMM_FORCE_STREAMK (1 << 27) /* Take it wherever it can run. */
+#define ANYV2V_GEMM_SWH (1 << 28)          /* 3x3 stride-1 "same" convolutions at width 16 / 32 / 64 on the LDS-patch kernel (another order). */
+#define ANYV2V_GEMM_PROBE_KORDER_SHIFT 29  /* Bits 29-30, probe patches: K order of the persistent kernel; ignored by the product library. */
 typedef struct AnyV2VGemmDesc {
     const void* A0;
     const void* A1;      /* may be NULL when C1 == 0 */
@@ -61,22 +87,7 @@ typedef struct AnyV2VGemmDesc {
     int32_t asym;                       /* mode 1: 0 = pad 1 on every side, 1 = pad only right / bottom */
     int32_t F, HW;                      /* mode 2: frames per clip, pixels per frame */
     int32_t act;
-    int32_t flags;       /* bit0: force the naive reference kernel; bit1: LDS-DMA staging; bit2: never use the
-                            persistent 192x320 kernel (nor the weight-stationary one); bit3: always use it when the shape
-                            allows; bit4: no split-K; bit9 (512): never use the weight-stationary K = 320 kernel; bit10 (1024):
-                            use it whenever the shape allows (mode 0, C0 = 320 with N % 160 = 0 or C0 = 512 with N % 64 = 0 (GEGLU: 128), C1 = 0, act 0 | 3, no rowvec), also
-                            below its M >= 32768 threshold; bit11 (2048) / bit12 (4096): 128-column / 160-column tiles in the
-                            128-row kernel regardless of the fill heuristic; bits 13-15: tile order of the persistent kernel on
-                            wide-N launches (0 auto, 1 classic N-fastest, 2..6 super-tiles of 4 / 8 / 16 / 32 / 2 M-tiles per XCD
-                            round), bit16: super-tiles walked N-fastest -- every order gives bit-identical results; bit17: take the
-                            ping-pong persistent kernel wherever the shape allows (N % 320 = 0, no GEGLU), bit18: never take it,
-                            bit19 / bit20: its 192- / 256-row tile (bit-identical to the other tile kernels); round 6, all OFF by
-                            default (A/B switches and tests): bit21: take the one-wave-per-SIMD persistent kernel (gemm_sw.hip:
-                            N % 320 = 0, >= 2 K-tiles; bit-identical to the other tile kernels), bit22: never take any of the round-6
-                            kernels, bit26 / bit27: allow / force its stream-K form (un-hinted launches, needs a workspace of 126 MB;
-                            a different fp32 summation order), bit28: 3x3 stride-1 "same" convolutions at image width 16 / 32 / 64 on
-                            the LDS-patch kernel (gemm_swh.hip: K order (dy, slice, dx), a different summation order).  All other
-                            bits are ignored by the product library. */
+    int32_t flags;       /* ANYV2V_GEMM_* above */
     void* workspace;     /* optional fp32 scratch for split-K partial tiles (small-M, long-K launches) or NULL */
     int64_t workspace_bytes;
     /* LayerNorm folded into the projection that consumes it (BasicTransformerBlock.norm1/2/3 -> attn.to_q/k/v / ff.net[0].proj,
@@ -109,7 +120,9 @@ int anyv2v_gemm_f16(const AnyV2VGemmDesc* d, void* stream);
  * cannot emit statistics: split-K plans, the naive kernel, the weight-stationary / LayerNorm-fold kernel, GEGLU / fp32-out
  * epilogues, the off-by-default kernels flags bits 17 / 21 / 26-28 select, N not a multiple of 160, N / gn_groups not a divisor of
  * 40 (a channel group must not straddle a 160-column wave tile), M or gn_rows_per_group not a multiple of 16.  Decides exactly as
- * anyv2v_gemm_f16 will (same flags, workspace, alignment and batch hint; gn_stats and C may still be NULL), launches nothing. */
+ * anyv2v_gemm_f16 will (same flags, workspace, alignment and batch hint; gn_stats and C may still be NULL), launches nothing and
+ * touches no device.  A descriptor the launch would reject (ANYV2V_EINVAL / ANYV2V_EUNSUPPORTED) answers 0 and leaves the launch's
+ * text in anyv2v_last_error(). */
 int64_t anyv2v_gemm_gn_stats_floats(const AnyV2VGemmDesc* d);
 /* Launches that emitted statistics since the counter was last reset (reset != 0: return the count, then zero it).  Host-side,
  * counted at enqueue time, before the launch status is known (a graph replay does not count; a launch the runtime rejects

@@ -1,7 +1,7 @@
-// Probe build only (-DANYV2V_EXPERIMENTS, `make -C anyv2v_amd/csrc experiments`): included from gemm.hip's dispatch<MODE>() in front of
+// Probe build only (-DANYV2V_EXPERIMENTS, `make -C anyv2v_amd/csrc experiments`): included from gemm.hip's launch<MODE>() in front of
 // the persistent-kernel launch.  Flag bit5 + a workspace: the TRACE instantiation writes 32 s_memtime stamps per block
 // (tools/gemm_big_trace.py).  The product library contains none of these instantiations.
-            if ((d->flags & 32) && d->workspace != nullptr && (size_t)grid.x * 32 * sizeof(long long) <= (size_t)d->workspace_bytes) {
+            if ((d->flags & ANYV2V_GEMM_PROBE_TRACE) && d->workspace != nullptr && (size_t)grid.x * 32 * sizeof(long long) <= (size_t)d->workspace_bytes) {
                 k.trace = (long long*)d->workspace;  // debug: phase timestamps of each block's first tile
                 if constexpr (MODE == MODE_LINEAR) {
                     if (geglu)
