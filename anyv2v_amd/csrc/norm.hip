@@ -118,7 +118,9 @@ __global__ void gn_partial_kernel(const half_t* __restrict__ X0, const half_t* _
 // kernel: no index division, no per-element group stepping, no gamma / beta reloads) and walks the rows of its block
 // with U row loads in flight (the previous one-vector-per-iteration grid-stride form had 32 KiB in flight per CU and
 // stopped at 3.6 TB/s read + write).
-__device__ __forceinline__ float gn_silu(float x) {  // x * sigmoid(x) on raw v_exp / v_rcp (1 ulp; the output is fp16)
+// x * sigmoid(x) on raw v_exp / v_rcp.  The output is fp16: over all 63 488 finite fp16 inputs it is at most 1 fp16 ulp from the exact
+// result rounded once, on a handful of inputs, in every apply kernel (tests/gpu_checks.py::check_silu_all_inputs).
+__device__ __forceinline__ float gn_silu(float x) {
     return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * x));
 }
 

@@ -492,6 +492,19 @@ def check_gemm_splitk():
         y_one = ops.gemm(xt, wp, **kw)
         out.append(_res("conv3x3[split-K] vs unsplit kernel", ys[0], y_one.float(), 2e-3))
         ops.GEMM_FLAGS = saved
+        # the same launch with an activation: gemm_splitk_reduce_kernel applies it to the summed partial tiles (+ bias + temb) and
+        # rounds to fp16 before the residual add (the reference adds in fp32: inside KTOL).  An activation keeps the launch off the
+        # persistent kernel, the 128-row kernel splits it 4 ways (tests/test_gemm_plan_host.py: splitk_conv_silu / _gelu).
+        pre = _to_tokens(F.conv2d(x.float(), w.float(), b.float(), padding=1) + temb.float().repeat_interleave(16, 0)[:, :, None, None])
+        for act, tag in ((ops.ACT_SILU, "SiLU"), (ops.ACT_GELU, "GELU")):
+            ref_act = (F.silu(pre) if act == ops.ACT_SILU else F.gelu(pre)) + res.float()
+            ya = [ops.gemm(xt, wp, act=act, **kw) for _ in range(3)]
+            out.append(_res(f"conv3x3[split-K] + {tag} vs torch", ya[0], ref_act, KTOL))
+            same = bool(torch.equal(ya[0], ya[1]) and torch.equal(ya[0], ya[2]))
+            out.append(dict(name=f"conv3x3[split-K] + {tag} bit-reproducible over three runs", err=0.0 if same else 1.0, l2=0.0, tol=0.0, ok=same))
+            ops.GEMM_FLAGS = saved | 16
+            out.append(_res(f"conv3x3[split-K] + {tag} vs unsplit kernel", ya[0], ops.gemm(xt, wp, act=act, **kw).float(), 2e-3))
+            ops.GEMM_FLAGS = saved
         # same level, N = 1280: split-K work items of the persistent 192x320 kernel (16 x 4 tiles x 4 splits = one round);
         # M = 3000 is not a multiple of 192 (row guards), compared with the 128-row kernel's split path (flag bit2) too
         n, ci, co = 48, 640, 1280
@@ -1510,31 +1523,88 @@ def check_clip():
         out.append(_res(f"clip vision [{tag}] image_embeds", vis.image_embeds(px), ref, 8e-3))
     return out
 
-# ------------------------------------------------------------------------------------------------ erf-GELU, every fp16 input
+# ------------------------------------------------------------------------------------------------ activations, every fp16 input
+def _fp16_key(h):
+    """Monotone integer key of an fp16 value (-0 and +0 share key 0): a difference of two keys counts fp16 steps."""
+    i = h.view(torch.int16).to(torch.int32)
+    return torch.where(i < 0, -(i & 0x7FFF), i)
+
+
+def _fp16_ulps(y, exact16):
+    """Distance of ``y`` from the correctly rounded result ``exact16`` in fp16 steps (broadcasts)."""
+    return (_fp16_key(y) - _fp16_key(exact16)).abs()
+
+
+def _finite_fp16():
+    bits = torch.arange(0, 65536, dtype=torch.int32, device=DEV).to(torch.int16)
+    x = bits.view(torch.float16)
+    return x[torch.isfinite(x)]                           # 63 488 values
+
+
+def _round_once_fp16(exact64):
+    """float64 -> fp16 in ONE rounding (numpy converts the bits directly; torch's ``.to(float16)`` goes through fp32 and rounds twice:
+    2 of the 63 488 exact SiLU values land on the other side of an fp16 tie that way)."""
+    import numpy as np
+    return torch.from_numpy(exact64.cpu().numpy().astype(np.float16)).to(exact64.device)
+
+
+def _ulp_row(out, what, tag, y, exact16, digits=2):
+    """The activation gate: every element of ``y`` at most 1 fp16 step from ``exact16`` (broadcast), fewer than 1 % of them off at all."""
+    d = _fp16_ulps(y, exact16)
+    frac = float((d > 0).double().mean())
+    worst = int(d.max())
+    out.append(dict(name=f"{what} over all {exact16.shape[0]} finite fp16 inputs, {tag}: {100 * frac:.{digits}f} % differ, worst {worst} ulp",
+                    err=float(worst), tol=1.0, ok=worst <= 1 and frac < 0.01))
+
+
+# The activation launches below: each value reaches the activation as the fp32 number equal to the fp16 input.
+#  * row-vector form: A = 0 (every product and every partial tile is an exact +0), the values in ``rowvec`` with rowvec_div = 1,
+#    M x N of them per launch;
+#  * column form (GEGLU takes no rowvec): a[:, 0] = x, w[:, 0] = 1 on the gate rows, the value half = 1 through the bias.
+# Families (pinned on the CPU by tests/test_gemm_plan_host.py, rows act_*): 496 x 128 x 64 -> 128-row kernel, unsplit; 64 x 1024 x 2048
+# -> 128-row kernel, 4 splits (8 tiles, 32 K-tiles), the activation in gemm_splitk_reduce_kernel.
+_ACT_TILE_SHAPE = (496, 128, 64)
+_ACT_SPLIT_SHAPE = (64, 1024, 2048)
+
+
+def _act_rowvec_gemm(x, shape, act, naive=False):
+    M, N, K = shape
+    n = x.numel()
+    rv = torch.zeros(M * N, dtype=torch.float16, device=DEV)
+    rv[:n] = x
+    a = torch.zeros(M, K, dtype=torch.float16, device=DEV)
+    w = torch.ones(N, K, dtype=torch.float16, device=DEV)
+    return ops.gemm(a, w, rowvec=rv.view(M, N), rowvec_div=1, act=act, naive=naive).reshape(-1)[:n]
+
+
+def _act_geglu_gemm(x, N, K, naive=False):
+    """[n, N / 2] outputs, every column = 1 * gelu(x).  Packed layout: groups of [16 value | 16 gate] columns."""
+    a = torch.zeros(x.numel(), K, dtype=torch.float16, device=DEV)
+    a[:, 0] = x
+    w = torch.zeros(N, K, dtype=torch.float16, device=DEV)
+    b = torch.zeros(N, dtype=torch.float16, device=DEV)
+    for g in range(N // 32):
+        w[g * 32 + 16:g * 32 + 32, 0] = 1.0
+        b[g * 32:g * 32 + 16] = 1.0
+    return ops.gemm(a, w, bias=b, act=ops.ACT_GEGLU, naive=naive)
+
+
 def check_gelu_all_inputs():
     """The GEMM epilogues' erf-GELU (``av_gelu`` in csrc/common.h: max(x,0) - |x| q with the Abramowitz-Stegun 7.1.26 tail) on
     EVERY finite fp16 input, through the GELU and the GEGLU epilogue of the tile kernel and the GEGLU epilogue of the
     weight-stationary one: at most 1 ulp from the correctly rounded exact GELU (float64 erf), and that on < 1 % of the inputs
-    (the reference's activation is ``F.gelu`` with the exact erf, diffusers GEGLU; VERDICT r2 #4: no change of semantics)."""
+    (the reference's activation is ``F.gelu`` with the exact erf, diffusers GEGLU; VERDICT r2 #4: no change of semantics).
+    The same gate on every other place that evaluates ``av_gelu``: the naive kernel (GELU, GEGLU), the split-K reduce kernel, the
+    GEGLU epilogues of the persistent kernel, of the one-wave-per-SIMD kernel and of its stream-K form (main kernel and fix-up
+    kernel), and the fused feed-forward kernel -- all output columns of those launches, not one."""
     out = []
-    bits = torch.arange(0, 65536, dtype=torch.int32, device=DEV).to(torch.int16)
-    x = bits.view(torch.float16)
-    x = x[torch.isfinite(x)]                              # 63 488 values
+    x = _finite_fp16()
     n = x.numel()
     exact = (0.5 * x.double() * (1.0 + torch.erf(x.double() / math.sqrt(2.0))))
-
-    def ulps(y):   # distance in fp16 steps from the correctly rounded result (monotone integer key of an fp16 value)
-        def key(h):
-            i = h.view(torch.int16).to(torch.int32)
-            return torch.where(i < 0, -(i & 0x7FFF), i)
-        return (key(y) - key(exact.to(torch.float16))).abs()
+    exact16 = exact.to(torch.float16)
 
     def report(tag, y):
-        d = ulps(y)
-        frac = float((d > 0).float().mean())
-        worst = int(d.max())
-        out.append(dict(name=f"erf-GELU over all {n} finite fp16 inputs, {tag}: {100 * frac:.2f} % differ, worst {worst} ulp",
-                        err=float(worst), tol=1.0, ok=worst <= 1 and frac < 0.01))
+        _ulp_row(out, "erf-GELU", tag, y, exact16 if y.dim() == 1 else exact16[:, None])
 
     for K, M_pad in ((64, 0), (320, 32768)):   # K = 320 with >= 32768 rows: the weight-stationary kernel
         M = max(n, M_pad)
@@ -1553,6 +1623,160 @@ def check_gelu_all_inputs():
             b[g * 32:g * 32 + 16] = 1.0
         y = ops.gemm(a, w, bias=b, act=ops.ACT_GEGLU)
         report("GEGLU epilogue (%s)" % ("weight-stationary kernel" if K == 320 else "tile kernel"), y[:n, 3])
+    from anyv2v_amd import _lib
+    saved, saved_glds = ops.GEMM_FLAGS, ops.USE_GLDS
+    try:
+        ops.USE_GLDS = True   # (split-K and the persistent kernels exist in the LDS-DMA form only)
+        report("GELU (naive kernel)", _act_rowvec_gemm(x, _ACT_TILE_SHAPE, ops.ACT_GELU, naive=True))
+        report("GEGLU (naive kernel)", _act_geglu_gemm(x, 128, 64, naive=True))
+        report("GELU (split-K reduce kernel, 4 splits)", _act_rowvec_gemm(x, _ACT_SPLIT_SHAPE, ops.ACT_GELU))
+        # 63488 x 640 (320 outputs per row): 331 x 2 tiles of 192 x 320 on 256 blocks; the one-wave kernel needs two K-tiles; its
+        # stream-K form deals the 1324 (tile, K-tile) units to 256 blocks, so whole tiles (main kernel's epilogue) and cut tiles
+        # (fix-up kernel's) both occur
+        ops.GEMM_FLAGS = (saved & ~_lib.ANYV2V_GEMM_NO_BIG) | _lib.ANYV2V_GEMM_FORCE_BIG
+        report("GEGLU epilogue (persistent kernel, forced)", _act_geglu_gemm(x, 640, 64))
+        ops.GEMM_FLAGS = saved | _lib.ANYV2V_GEMM_SW
+        report("GEGLU epilogue (one-wave-per-SIMD kernel)", _act_geglu_gemm(x, 640, 128))
+        ops.GEMM_FLAGS = saved | _lib.ANYV2V_GEMM_FORCE_STREAMK
+        report("GEGLU epilogue (one-wave kernel, stream-K: main + fix-up kernels)", _act_geglu_gemm(x, 640, 128))
+    finally:
+        ops.GEMM_FLAGS, ops.USE_GLDS = saved, saved_glds
+    # fused feed-forward (C = 320, hidden = 1280), 320 values per row: gate unit j < 320 copies x[:, j] (an identity block in W1's
+    # gate half), every value unit is 1 through the bias, hidden units >= 320 are 1 * gelu(0) = 0; the down-projection is the 0/1
+    # matrix that copies hidden unit c to output c.  The kernel rounds the hidden value to fp16 once; 1 x that value + 0 is exact.
+    C, H = 320, 1280
+    M = (n + C - 1) // C
+    xp = torch.zeros(M * C, dtype=torch.float16, device=DEV)
+    xp[:n] = x
+    w1, b1 = torch.zeros(2 * H, C, dtype=torch.float16, device=DEV), torch.zeros(2 * H, dtype=torch.float16, device=DEV)
+    b1[:H] = 1.0
+    w1[H:H + C] = torch.eye(C, dtype=torch.float16, device=DEV)
+    w2 = torch.zeros(C, H, dtype=torch.float16, device=DEV)
+    w2[:, :C] = torch.eye(C, dtype=torch.float16, device=DEV)
+    w1p, b1p = _geglu_pack(w1, b1, H)
+    y = ops.ff_geglu(xp.view(M, C), w1p, b1p, ops.ff_pack_w2(w2), torch.zeros(C, dtype=torch.float16, device=DEV))
+    report("GEGLU (fused feed-forward kernel)", y.reshape(-1)[:n])
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ SiLU, every fp16 input
+def _gn_beta_launches(C, rows, x, const, run):
+    """The 63 488 values ``x`` through a GroupNorm kernel, C per launch: ``run(X, gamma, beta, out)`` with the constant input
+    ``const``, gamma = -0 and beta = the next C values.  (x - mean) rstd is an exact +0 (sums about a pivot taken from the data are
+    s = q = 0, so mean = the constant; sums about 0 need const = 0), times -0 is -0, and -0 + beta = beta for every beta, -0
+    included: the kernel's pre-activation is beta[c], bit for bit, in every row.  Returns (outputs [launches, rows, C], betas)."""
+    n = x.numel()
+    L = (n + C - 1) // C
+    betas = torch.zeros(L * C, dtype=torch.float16, device=DEV)
+    betas[:n] = x
+    betas = betas.view(L, C)
+    X = torch.full((rows, C), const, dtype=torch.float16, device=DEV)
+    gamma = torch.full((C,), -0.0, dtype=torch.float16, device=DEV)
+    ys = torch.empty(L, rows, C, dtype=torch.float16, device=DEV)
+    for i in range(L):
+        run(X, gamma, betas[i], ys[i])
+    return ys, betas
+
+
+def check_silu_all_inputs():
+    """SiLU on EVERY finite fp16 input through every kernel that computes it, against x / (1 + exp(-x)) in float64 rounded ONCE to
+    fp16: at most 1 ulp, on fewer than 1 % of the inputs (the erf-GELU gate).  4 855 of the exact results are fp16 subnormals (a
+    kernel that flushes them fails), 12 013 round to +-0 (the key treats -0 and +0 alike).  fp32 torch evaluations of the kernels'
+    formulas differ from the exact result on 1 to 3 inputs, by 1 ulp.
+
+    ``av_silu`` (csrc/common.h, x / (1 + __expf(-x))): the elementwise kernel; the 128-row GEMM kernel's epilogue with register and
+    with LDS-DMA staging; the naive kernel; the split-K reduce kernel.  ``gn_silu`` (norm.hip, x * v_rcp(1 + v_exp(-x log2 e))):
+    the apply kernel of the one-call GroupNorm in three launch plans (C = 320: 6 rows per block; C = 1280 and C = 2560: one row
+    per block, 160 / 320 threads; each with the 4-row unrolled loop and its tail), of the one-all-reduce sharded pair (sums about 0:
+    its input is 0, not 0.5), of the pivoted sharded path, and the apply-from-records kernel (records written by hand: pivot = the
+    constant, s = q = 0).  Every GroupNorm kernel also runs without SiLU: its output must be beta, bit for bit, which proves
+    that the values reach the activation intact."""
+    from anyv2v_amd import _lib
+    out = []
+    x = _finite_fp16()
+    n = x.numel()
+    x64 = x.double()
+    exact16 = _round_once_fp16(x64 / (1.0 + torch.exp(-x64)))
+
+    def report(tag, y):   # (three decimals: a correct kernel is off on a handful of inputs, 1 of 63 488 = 0.002 %)
+        _ulp_row(out, "SiLU", tag, y, exact16 if y.dim() == 1 else exact16[:, None], digits=3)
+
+    report("elementwise kernel", ops.silu(x.contiguous()))
+    saved_glds = ops.USE_GLDS
+    try:
+        for glds in (False, True):
+            ops.USE_GLDS = glds
+            report("GEMM epilogue (128-row kernel, %s staging)" % ("LDS-DMA" if glds else "register"),
+                   _act_rowvec_gemm(x, _ACT_TILE_SHAPE, ops.ACT_SILU))
+        report("GEMM epilogue (naive kernel)", _act_rowvec_gemm(x, _ACT_TILE_SHAPE, ops.ACT_SILU, naive=True))
+        report("split-K reduce kernel, 4 splits", _act_rowvec_gemm(x, _ACT_SPLIT_SHAPE, ops.ACT_SILU))
+    finally:
+        ops.USE_GLDS = saved_glds
+
+    lib = _lib.load()
+    G, eps, nsg = 32, 1e-5, 2
+
+    def one_call(silu, rpg, stats):
+        return lambda X, ga, be, y: ops.groupnorm(X, ga, be, stats, rpg, groups=G, eps=eps, silu=silu, out=y)
+
+    def pivoted(silu, rpg, stats):   # anyv2v_groupnorm_pivot_f16 / _partial_pivot_f16 / _apply_pivot_f16, one shard
+        return lambda X, ga, be, y: ops.groupnorm(X, ga, be, stats, rpg, groups=G, eps=eps, silu=silu, out=y, shard=(1, lambda t: t))
+
+    def one_all_reduce(silu, rpg, stats):   # anyv2v_groupnorm_partial_f16 / _apply_f16, one shard: sums about 0
+        def run(X, ga, be, y):
+            M, C = X.shape
+            _lib.check(lib.anyv2v_groupnorm_partial_f16(X.data_ptr(), None, C, 0, stats.data_ptr(), M, rpg, G, ops._stream()))
+            _lib.check(lib.anyv2v_groupnorm_apply_f16(X.data_ptr(), None, C, 0, y.data_ptr(), ga.data_ptr(), be.data_ptr(), stats.data_ptr(),
+                                                      M, rpg, G, eps, int(silu), 1, ops._stream()))
+        return run
+
+    def from_records(silu, rpg, stats):   # anyv2v_groupnorm_apply_stats_f16; hand-written records [16 rows][G][3] = (pivot 0.5, s 0, q 0)
+        rec = torch.zeros(ops.gn_stats_floats(nsg * rpg, rpg, G), dtype=torch.float32, device=DEV)
+        rec[:3 * (nsg * rpg // 16) * G].view(-1, 3)[:, 0] = 0.5
+        return lambda X, ga, be, y: ops.groupnorm_from_stats(X, ga, be, rec, rpg, groups=G, eps=eps, silu=silu, out=y)
+
+    # (kernel, C, rows per statistics group, constant input) x 2 statistics groups.  C = 320, 64 rows: 6 rows per block, 2 blocks of 32
+    # rows per group: every thread runs the 4-row unrolled loop once and then its tail.  One row per block at C >= 1280: 42 rows
+    # -> 6 blocks of 7 rows, unrolled loop + tail again.
+    sites = [("one-call GroupNorm, C 320 (6 rows per block)", one_call, 320, 64, 0.5),
+             ("one-call GroupNorm, C 1280 (1 row per block)", one_call, 1280, 42, 0.5),
+             ("one-call GroupNorm, C 2560 (320 threads)", one_call, 2560, 42, 0.5),
+             ("sharded GroupNorm, one all-reduce (groupnorm_apply_f16)", one_all_reduce, 320, 64, 0.0),
+             ("sharded GroupNorm, pivoted (groupnorm_apply_pivot_f16)", pivoted, 320, 64, 0.5),
+             ("GroupNorm from GEMM records (groupnorm_apply_stats_f16)", from_records, 320, 64, 0.5)]
+    for tag, make, C, rpg, const in sites:
+        rows = nsg * rpg
+        stats = torch.zeros(ops.gn_scratch_floats(rows, rpg, G), dtype=torch.float32, device=DEV)
+        ys, betas = _gn_beta_launches(C, rows, x, const, make(False, rpg, stats))
+        same = bool(torch.equal(ys.view(torch.int16), betas.view(torch.int16)[:, None, :].expand_as(ys)))
+        out.append(dict(name=f"{tag}, silu=0: every output row == beta, bit for bit ({ys.shape[0]} launches)", err=0.0 if same else 1.0,
+                        l2=0.0, tol=0.0, ok=same))
+        ys, _ = _gn_beta_launches(C, rows, x, const, make(True, rpg, stats))
+        L = ys.shape[0]
+        got = ys.permute(1, 0, 2).reshape(rows, L * C)[:, :n]   # [row, value]
+        report(f"{tag}, all {rows} rows", got.t())
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ timestep embedding, every timestep
+def check_timestep_embedding_all_timesteps():
+    """The sinusoidal embedding at t = 0 ... 999 in one launch, at every width the three model families pass (320: all released
+    configurations; 64: the mini I2VGen-XL and the SEINE toy UNet; 32: the ConsistI2V toy UNet) and at the edge widths 2 and 1280,
+    against float64 cos / sin(t exp(-ln 10000 f / half)).  Per element |got - ref| <= 2^-11 + |arg| 2^-21: the fp16 rounding of a value
+    in [-1, 1], plus 4 fp32 ulps on the argument for the kernel's fp32 expf and product (the same formula in fp32 torch on the CPU
+    uses 0.50 of the bound).  err = the worst ratio of error to bound."""
+    out = []
+    t = torch.arange(1000, device=DEV, dtype=torch.float32)
+    for dim in (320, 64, 32, 2, 1280):
+        half = dim // 2
+        arg = t.double()[:, None] * torch.exp(-math.log(10000.0) * torch.arange(half, device=DEV).double() / half)[None]
+        ref = torch.cat([arg.cos(), arg.sin()], -1)
+        bound = 2.0 ** -11 + torch.cat([arg, arg], -1).abs() * 2.0 ** -21
+        got = ops.timestep_embedding(t, dim)
+        finite = bool(torch.isfinite(got.float()).all())
+        ratio = float(((got.double() - ref).abs() / bound).max()) if finite else float("nan")
+        out.append(dict(name=f"timestep embedding dim {dim}, t = 0 ... 999: worst |error| / (2^-11 + |arg| 2^-21) = {ratio:.3f}", err=ratio, l2=0.0,
+                        tol=1.0, ok=finite and ratio <= 1.0))
     return out
 
 
@@ -3704,7 +3928,8 @@ EDGE_CHECKS = [check_edges_gemm_tile, check_edges_conv, check_edges_gemm_persist
                check_edges_elementwise, check_edges_layout, check_edges_softmax_timestep]
 
 ALL_KERNEL_CHECKS = [check_selftest, check_gemm, check_gemm_big, check_gemm_ws, check_gemm_ws_ln, check_gemm_splitk, check_conv, check_norms, check_attention,
-                     check_attention_small_mfma, check_attention_bias_and_rotary_windows, check_gelu_all_inputs, check_elementwise,
+                     check_attention_small_mfma, check_attention_bias_and_rotary_windows, check_gelu_all_inputs, check_silu_all_inputs,
+                     check_timestep_embedding_all_timesteps, check_elementwise,
                      check_full_size_properties, check_vae_kernels] + EDGE_CHECKS
 
 

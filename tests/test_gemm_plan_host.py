@@ -173,6 +173,39 @@ ROWS = [
     ("gn_m_rpg", f"{CONV64} M=196608 N=320 C0=320 gn_groups=32 gn_rpg=20480 flags=2", dict(gn_records=False, gn_decline=SHAPE)),
     ("gn_naive", f"{CONV64} M=196608 N=320 C0=320 {GN} flags=3", dict(grid=245760, family="naive", gn_records=False, gn_decline="the naive kernel")),
     ("gn_pp", f"{CONV64} M=196608 N=320 C0=320 {GN} flags={2 | 1 << 17}", dict(tiles=768, grid=256, family="pp", gn_records=False)),
+    # ---- the launches of the all-fp16-inputs activation checks (tests/gpu_checks.py: check_silu_all_inputs, check_gelu_all_inputs) and the
+    # split-K activation rows of check_gemm_splitk: a retune that moves one of them must not silently change the epilogue under test ----
+    # values in rowvec, 496 x 128 x 64, SiLU / GELU: N = 128 is no multiple of 320 (no persistent kernel) nor of 160 -> NF 4; tm = 4 x 1,
+    # nk = 1: no split.  The same with register staging (flags 0); bit0: the naive kernel, 496 x 128 / 256 blocks
+    ("act_tile_silu", "mode=0 M=496 N=128 C0=64 rowvec=1 act=1 flags=2", dict(family="mfma128", nf=4, splits=1, tilesN=1, tiles=4, grid=4)),
+    ("act_tile_silu_reg", "mode=0 M=496 N=128 C0=64 rowvec=1 act=1 flags=0", dict(family="mfma128", nf=4, splits=1, tilesN=1, tiles=4, grid=4)),
+    ("act_naive_silu", "mode=0 M=496 N=128 C0=64 rowvec=1 act=1 flags=3", dict(family="naive", splits=1, grid=248)),
+    ("act_naive_gelu", "mode=0 M=496 N=128 C0=64 rowvec=1 act=2 flags=3", dict(family="naive", splits=1, grid=248)),
+    # GEGLU on the naive kernel: one thread per OUTPUT, 63488 x 64 / 256 blocks
+    ("act_naive_geglu", "mode=0 M=63488 N=128 C0=64 bias=1 act=3 flags=3", dict(family="naive", splits=1, grid=15872)),
+    # 64 x 1024 x 2048: N = 1024 is no multiple of 320 / 160 -> 128-row kernel, NF 4, tm = 1 x 8 = 8 <= 128 with nk = 32 >= 32 pays:
+    # sp = min(ceil(512 / 8) = 64, 8, 32 / 8) = 4, 4 x 64 x 1024 x 4 B = 1 MiB fits -> the reduce kernel applies the activation
+    ("act_splitk_silu", "mode=0 M=64 N=1024 C0=2048 rowvec=1 act=1 flags=2",
+     dict(family="mfma128", nf=4, splits=4, tilesN=8, tiles=8, grid=32, gn_decline="a split-K plan")),
+    ("act_splitk_gelu", "mode=0 M=64 N=1024 C0=2048 rowvec=1 act=2 flags=2", dict(family="mfma128", nf=4, splits=4, tilesN=8, tiles=8, grid=32)),
+    # check_gemm_splitk's first case with an activation: SiLU / GELU keep it off the persistent kernel (big_ok: act 0); N = 320: NF 5
+    # (320 % 128 != 0), tm = 24 x 2 = 48, nk = 9 x 4 = 36 >= 32: sp = min(ceil(512 / 48) = 11, 8, 36 / 8) = 4; bit4: unsplit
+    ("splitk_conv_silu", f"{CONV8} M=3072 N=320 C0=256 bias=1 rowvec=1 rowvec_div=1024 R=1 act=1 flags=2",
+     dict(family="mfma128", nf=5, splits=4, tilesN=2, tiles=48, grid=192)),
+    ("splitk_conv_gelu", f"{CONV8} M=3072 N=320 C0=256 bias=1 rowvec=1 rowvec_div=1024 R=1 act=2 flags=2",
+     dict(family="mfma128", nf=5, splits=4, tilesN=2, tiles=48, grid=192)),
+    ("splitk_conv_silu_bit4", f"{CONV8} M=3072 N=320 C0=256 bias=1 rowvec=1 rowvec_div=1024 R=1 act=1 flags=18",
+     dict(family="mfma128", nf=5, splits=1, tilesN=2, tiles=48, grid=48)),
+    # GEGLU, 63488 x 640: bit3 (and tb = 331 x 2 = 662 on 3 rounds, 662 x 4 >= 3 x 256 x 3, fills anyway) -> persistent kernel, 2 N-tiles:
+    # classic order
+    ("act_big_geglu", "mode=0 M=63488 N=640 C0=64 bias=1 act=3 flags=10",
+     dict(family="big", splits=1, tilesN=2, tiles=662, grid=256, raster=[0, 0, 0, 0, 0])),
+    # bit21 with nk = 2 (the one-wave kernel needs >= 2 K-tiles; GEGLU Linear without residual / rowvec is eligible)
+    ("act_sw_geglu", f"mode=0 M=63488 N=640 C0=128 bias=1 act=3 flags={2 | 1 << 21}",
+     dict(family="sw", tilesN=2, tiles=662, grid=256, raster=[0, 0, 0, 0, 0])),
+    # bit27: U = 662 x 2 = 1324 units in [1024, 2^22] -> 256 blocks (5.2 units each: whole tiles and cut tiles), 125.8 MB <= 128 MiB
+    ("act_sk_geglu", f"mode=0 M=63488 N=640 C0=128 bias=1 act=3 flags={2 | 1 << 27}",
+     dict(family="sw_streamk", sk_blocks=256, grid=256, tiles=662, tilesN=2)),
     # ---- descriptor validation (gemm_impl's checks, same texts) ----
     ("bad_mode", "mode=3 M=128 N=320 C0=320 flags=2", dict(status=-1, message="gemm: bad mode 3")),
     ("bad_shape", "mode=0 M=0 N=320 C0=320 flags=2", dict(status=-1, message="gemm: bad M/N/C0/C1 (0 320 320 0)")),
