@@ -448,6 +448,28 @@ def gather_rows(x: torch.Tensor, xcol0: int, idx: torch.Tensor, y: torch.Tensor,
     return y
 
 
+def freeu(hidden: torch.Tensor, skip: torch.Tensor, n_img: int, H: int, W: int, b: float, s: float, out=None):
+    """FreeU on the pair an up block concatenates (``anyv2v_freeu_f16``, include/anyv2v_hip.h), token matrices [n_img H W, C]:
+    the first half of ``hidden``'s channels times ``b``; ``skip`` through the 2 x 2-box Fourier filter with scale ``s``, per
+    (image, channel) plane.  Out of place -> (hidden', skip'); ``out`` = (hidden', skip') to write into given matrices."""
+    lib = _lib.load()
+    _rowmajor(hidden, "hidden")
+    _rowmajor(skip, "skip")
+    rows = n_img * H * W
+    assert hidden.shape[0] == rows and skip.shape[0] == rows, f"freeu: {tuple(hidden.shape)} / {tuple(skip.shape)} rows, expected {rows}"
+    if out is None:
+        out = (torch.empty((rows, hidden.shape[1]), dtype=torch.float16, device=hidden.device),
+               torch.empty((rows, skip.shape[1]), dtype=torch.float16, device=skip.device))
+    ho, so = out
+    _rowmajor(ho, "hidden'")
+    _rowmajor(so, "skip'")
+    assert tuple(ho.shape) == tuple(hidden.shape) and tuple(so.shape) == tuple(skip.shape)
+    _lib.check(lib.anyv2v_freeu_f16(_p(hidden), hidden.stride(0), _p(ho), ho.stride(0), hidden.shape[1], float(b),
+                                    _p(skip), skip.stride(0), _p(so), so.stride(0), skip.shape[1], float(s), n_img, H, W, _stream()),
+               "anyv2v_freeu_f16")
+    return ho, so
+
+
 def rotary(x: torch.Tensor, col0: int, rot_dim: int, rows_per_pos: int, n_pos: int, theta: float = 10000.0, windows: int = 1,
            window_stride: int = 0):
     """In-place rotary position embedding of columns [col0 + w * window_stride, ... + rot_dim), w < windows (interleaved pairs);

@@ -409,11 +409,23 @@ class I2VGenXLPipeline:
         self._vae_tiling = False
 
     def enable_freeu(self, s1, s2, b1, b2):
-        """``:623-648`` (FreeU re-weights the decoder's skip / backbone features): not built -- AnyV2V never enables it."""
-        raise NotImplementedError("FreeU is not supported by the native UNet")
+        """``:623-648``: forwarded to the UNet (``I2VGenXLUNet.enable_freeu``: FreeU re-weights the decoder's backbone / skip features
+        in front of the concats of ``up_blocks[0]`` / ``[1]``).  The four numbers are part of the step engines' cache key, so HIP graphs
+        captured under another setting are not replayed, and the multi-edit source-feature cache is dropped: what it recorded depends
+        on them.  ConsistI2V / SEINE have no FreeU in the reference and none here."""
+        if self.unet is None or not hasattr(self.unet, "enable_freeu"):
+            raise NotImplementedError("enable_freeu needs a UNet: this pipeline has none loaded (or one without FreeU support)")
+        self.unet.enable_freeu(s1, s2, b1, b2)   # (refuses frame-parallel clips)
+        self._freeu_changed()
 
     def disable_freeu(self):
-        pass
+        if self.unet is not None and hasattr(self.unet, "disable_freeu"):
+            self.unet.disable_freeu()
+            self._freeu_changed()
+
+    def _freeu_changed(self):
+        if self.source_cache is not None:
+            self.source_cache.bind(None)   # recorded source features were computed under the other setting
 
     def encode_vae_video(self, video, device, height=576, width=1024):
         vae = self._need("vae")
@@ -496,7 +508,8 @@ class I2VGenXLPipeline:
             self.unet.pack()  # (weights loaded / moved since the last call: new packed tensors, engines of the old ones are stale)
         key = (tag, self.unet._pack_gen, tuple(sample.shape), str(sample.device), tuple(cond["encoder_hidden_states"].shape), kw.get("b_unc"),
                kw.get("b_cond"), float(kw.get("guidance")), tuple(kw.get("dup_slots")), bool(kw.get("shared_stem", False)),
-               _use_graphs(), pnp_utils.has_foreign_hooks(self.unet), id(self.unet), kw.get("lat_slots"))
+               _use_graphs(), pnp_utils.has_foreign_hooks(self.unet), id(self.unet), kw.get("lat_slots"),
+               getattr(self.unet, "freeu", None))   # (a captured graph holds the FreeU launches of the setting it was captured under)
         eng = self._engines.pop(key, None)
         if eng is None or not eng.rebind(sample, cond):
             eng = _StepEngine(self, sample, cond, **kw)
@@ -751,7 +764,7 @@ class I2VGenXLPipeline:
             fp_ = lambda x: (tuple(x.shape), float(x.float().sum()), float(x.float().abs().sum()))
             src = ("object", traj.serial) if isinstance(ddim_inv_latents_path, LatentTrajectory) else ("files", os.path.abspath(str(ddim_inv_latents_path)))
             cache.bind((src, tuple(ts), fp_(load_ddim_latents_at_t(ts[0], traj)), fp_(spe), fp_(sie), fp_(sil), int(target_fps),
-                        self.unet._pack_gen, id(self.unet), tuple(latents.shape)))
+                        self.unet._pack_gen, id(self.unet), tuple(latents.shape), getattr(self.unet, "freeu", None)))
             if not hasattr(eng, "site_bufs"):
                 # rows of ONE branch at the site's level: up_blocks[1] works at 1/16 of the 64x64 level's pixels, [2] at 1/4, [3] at 1/1
                 full = num_frames * (height // self.vae_scale_factor) * (width // self.vae_scale_factor)

@@ -20,6 +20,7 @@ The attribute paths the reference hooks rely on (``pnp_utils.py:20-27,130,239,34
 from __future__ import annotations
 
 import copy
+import math
 import os
 
 from dataclasses import dataclass
@@ -801,12 +802,15 @@ class UpBlock3D(nn.Module):
                 self.attentions.append(Transformer2DModel(heads, cfg.attention_head_dim, cout, cfg.cross_attention_dim, g))
                 self.temp_attentions.append(TransformerTemporalModel(heads, cfg.attention_head_dim, cout, g))
         self.upsamplers = nn.ModuleList([Upsample2D(cout)]) if add_upsample else None
+        self.freeu = None   # (b, s) of I2VGenXLUNet.enable_freeu on up_blocks[0] / [1]; None: off, nothing below runs
 
     def run(self, ctx, x, skips: List[torch.Tensor], H, W, out_hw=None):
         """``out_hw``: the size the upsampler has to deliver -- that of the skip connections the next block pops ([3P] diffusers
         ``forward_upsample_size``: a latent size that is not a multiple of 8 does not come back from three ceil-halvings by doubling)."""
         for i in range(len(self.resnets)):
             skip = skips.pop()
+            if self.freeu is not None:   # FreeU: backbone half times b, skip through the Fourier filter -- in front of the (folded) concat
+                x, skip = ops.freeu(x, skip, x.shape[0] // (H * W), H, W, *self.freeu)
             x = self.resnets[i].run(ctx, x, skip, H, W)  # torch.cat([x, skip], 1) folded into the kernels
             x = self.temp_convs[i].run(ctx, x, H, W)
             if self.has_cross_attention:
@@ -931,8 +935,34 @@ class I2VGenXLUNet(nn.Module):
     def set_frame_parallel(self, fp):
         """Shard ONE clip's frames over the ranks of ``fp`` (``anyv2v_amd.parallel.FrameParallel``; None = off).  Inputs
         and outputs of ``forward`` stay full-size and replicated; only the activations are sharded."""
+        if fp is not None and self.freeu is not None:
+            raise NotImplementedError("FreeU is enabled: frame-parallel clips do not support it (disable_freeu() first)")
         self.frame_parallel = fp
         self._ctx = _Ctx()
+
+    # ----------------------------------------------------------------------------------- FreeU
+    def enable_freeu(self, s1, s2, b1, b2):
+        """diffusers ``enable_freeu`` (arXiv 2309.11497), as the reference pipeline forwards it (``pipeline_i2vgen_xl.py:623-648``): in
+        front of every skip concat of ``up_blocks[0]`` (b1, s1) and ``up_blocks[1]`` (b2, s2) the first half of the backbone's
+        channels is scaled by b and the skip connection's lowest frequencies by s (``ops.freeu``); the other up blocks are untouched.
+        A step engine captured before the call does not see it: ``I2VGenXLPipeline.enable_freeu`` keys its engines on ``freeu``."""
+        vals = tuple(float(v) for v in (s1, s2, b1, b2))
+        if not all(math.isfinite(v) for v in vals):
+            raise ValueError(f"enable_freeu: s1, s2, b1, b2 = {vals} must be finite")
+        if self.frame_parallel is not None:
+            raise NotImplementedError("enable_freeu: not supported on a frame-parallel clip (set_frame_parallel(None) first)")
+        self.up_blocks[0].freeu = (vals[2], vals[0])
+        self.up_blocks[1].freeu = (vals[3], vals[1])
+
+    def disable_freeu(self):
+        for blk in self.up_blocks:
+            blk.freeu = None
+
+    @property
+    def freeu(self):
+        """(s1, s2, b1, b2) while FreeU is enabled, else None."""
+        f0, f1 = self.up_blocks[0].freeu, self.up_blocks[1].freeu
+        return None if f0 is None or f1 is None else (f0[1], f1[1], f0[0], f1[0])
 
     # ----------------------------------------------------------------------------------- weights
     @property

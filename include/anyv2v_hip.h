@@ -286,6 +286,18 @@ int anyv2v_rotary_f16(void* X, int32_t ld, int64_t rows, int32_t col0, int32_t r
 int anyv2v_copy_cols_f16(const void* X, int32_t ldx, int32_t xcol0, void* Y, int32_t ldy, int32_t ycol0, int64_t M,
                          int32_t C, void* stream);
 
+/* FreeU (arXiv 2309.11497; the reference pipeline forwards enable_freeu to its UNet, pipeline_i2vgen_xl.py:623-648) on the pair of
+ * token matrices [n_img H W, C] (rows ordered (image, h, w)) that an up block concatenates, out of place:
+ *   hidden_out[:, c] = fp16(float(hidden[:, c]) * b) for c < C_hidden / 2, a copy for the other half;
+ *   skip_out = per (image, channel) plane [H, W], in fp32, rounded once: fftn -> fftshift -> the 2 x 2 box
+ *              [H/2-1 : H/2+1, W/2-1 : W/2+1] times s -> ifftshift -> ifftn -> real.  The box holds the frequencies {0, -1} of each
+ *              axis ({0} on an axis of size 1), so the filter is evaluated in closed form -- seven sums per plane and a rank-4
+ *              correction, no FFT (DESIGN.md "FreeU").  No atomics: bit-reproducible, and independent of n_img.
+ * C_hidden, C_skip and the leading dimensions are multiples of 8, every pointer is 16-byte aligned, H + W <= 4096. */
+int anyv2v_freeu_f16(const void* hidden, int32_t ld_hidden, void* hidden_out, int32_t ld_hidden_out, int32_t C_hidden, float b,
+                     const void* skip, int32_t ld_skip, void* skip_out, int32_t ld_skip_out, int32_t C_skip, float s,
+                     int32_t n_img, int32_t H, int32_t W, void* stream);
+
 /* Row softmax of fp32 logits (from anyv2v_gemm_f16 with act = 4) into fp16 probabilities:
  * P[r, c] = softmax_c(scale * S[r, c]), cols <= 8192.  AutoencoderKL mid-block attention (single head of width 512,
  * encode_vae_video / decode_latents, pipeline_i2vgen_xl.py:565-592,598-620). */
