@@ -234,7 +234,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? (NV == 1 ? 4 : 2) : (NV == 1 ? (
             // ---- S^T = K Q^T for this wave's 32 queries x 64 keys
             // K fragments as inline asm with counted lgkmcnt waits: the first block's four reads, then its MFMAs with the second
             // block's reads slotted in, each MFMA waiting only for its own fragment (hipcc would wait lgkmcnt(0) in front of every
-            // MFMA while an LDS-DMA load is in flight -- see gemm.hip / tools/wait_probe.hip -- i.e. also for the read just issued)
+            // MFMA while an LDS-DMA load is in flight -- see gemm_common.h (lds_frag) / tools/wait_probe.hip -- i.e. also for the read just issued)
             h8 kf[2][4];
             unsigned kaddr[2];
             int kfk[2];

@@ -42,11 +42,6 @@ struct FFK {
     int M, ldx, ldr, ldy, nstrips;
 };
 
-__device__ __forceinline__ h8 ffr128(unsigned addr, int off) {   // off: a constant after unrolling (16-bit immediate)
-    h8 v;
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(off) : "memory");
-    return v;
-}
 __device__ __forceinline__ h4 ffr64(unsigned addr) {
     h4 v;
     asm volatile("ds_read_b64 %0, %1" : "=v"(v) : "v"(addr) : "memory");
@@ -197,8 +192,8 @@ __global__ __launch_bounds__(512) void ff_fused_c320_kernel(const FFK p) {
                 const unsigned wb0 = wb + ad.w1c0, wb1 = wb + ad.w1c1;
 #define FF_RD_KS(KS)                                                                     \
     do {                                                                                 \
-        wf[(KS) % (D1 + 1)][0] = ffr128(((KS) & 1) ? wb1 : wb0, ((KS) >> 1) * (64 * 128));          \
-        wf[(KS) % (D1 + 1)][1] = ffr128(((KS) & 1) ? wb1 : wb0, ((KS) >> 1) * (64 * 128) + 2048);   \
+        wf[(KS) % (D1 + 1)][0] = lds_frag(((KS) & 1) ? wb1 : wb0, ((KS) >> 1) * (64 * 128));          \
+        wf[(KS) % (D1 + 1)][1] = lds_frag(((KS) & 1) ? wb1 : wb0, ((KS) >> 1) * (64 * 128) + 2048);   \
     } while (0)
                 FF_RD_KS(0);
                 if constexpr (D1 == 2) FF_RD_KS(1);
@@ -247,9 +242,9 @@ __global__ __launch_bounds__(512) void ff_fused_c320_kernel(const FFK p) {
                 constexpr int D2 = (VAR & 1) ? 3 : 2;   // fragments of read-ahead
                 h8 wf[D2 + 1];
                 const unsigned wbl = wb + ad.w2off;
-                wf[0] = ffr128(wbl, 0);
-                wf[1] = ffr128(wbl, 1024);
-                if constexpr (D2 == 3) wf[2] = ffr128(wbl, 2048);
+                wf[0] = lds_frag(wbl, 0);
+                wf[1] = lds_frag(wbl, 1024);
+                if constexpr (D2 == 3) wf[2] = lds_frag(wbl, 2048);
                 __builtin_amdgcn_sched_barrier(0);
                 if constexpr (D2 == 3)
                     FF_LGKM(3);
@@ -266,7 +261,7 @@ __global__ __launch_bounds__(512) void ff_fused_c320_kernel(const FFK p) {
                 if constexpr ((VAR & 2) != 0) __builtin_amdgcn_s_setprio(1);
 #pragma unroll
                 for (int nf = 0; nf < 10; ++nf) {
-                    if (nf + D2 < 10) wf[(nf + D2) % (D2 + 1)] = ffr128(wbl, (nf + D2) * 1024);
+                    if (nf + D2 < 10) wf[(nf + D2) % (D2 + 1)] = lds_frag(wbl, (nf + D2) * 1024);
                     __builtin_amdgcn_sched_barrier(0);
                     if (nf + 3 < 10 && D2 == 3)
                         FF_LGKM(3);

@@ -1,4 +1,6 @@
-// Definitions shared by the GEMM translation units (gemm.hip, gemm_ws.hip): kernel argument block, gather addressing.
+// Definitions shared by the GEMM translation units (gemm.hip = host entry; gemm_mfma / gemm_big / gemm_pp / gemm_ref / gemm_ws /
+// gemm_sw / gemm_swh .hip = one kernel family each; ff_fused.hip): kernel argument block, gather addressing, the inline-asm
+// fragment reads with their counted waits, and the family launchers.
 #pragma once
 #include "common.h"
 #include "gemm_plan.h"   // MODE_*, ACT_*, GemmPlan
@@ -94,11 +96,112 @@ __device__ __forceinline__ const half_t* a_addr(const GemmK& p, const ASrc& s, i
     return sr < 0 ? p.zeros : g;
 }
 
+// Incremental gather addressing of the ROWS A rows a thread stages per K-tile: inside one (tap, source) run consecutive K-tiles only
+// advance the channel offset (+128 bytes); the row -> shifted-row math is redone only when the tap or the source changes
+// (wave-uniform branch).
+// ORD (conv2d): 0 = tap-major K order (tap, channel slice); 1 = slice-major (channel slice, dy, dx): the three dx taps of one
+// (slice, dy) are consecutive K-tiles and touch the same A lines shifted by one pixel -- L1 (TCP) hits when nothing else allocates
+// there in between (the W pieces then go past L1, `sc1`; probe builds of gemm_sw.hip only)
+template <int MODE, int ROWS, int ORD = 0>
+struct AGen {
+    const half_t* ap[ROWS];
+    int astep[ROWS];  // halves to advance per K-tile: 64, or 0 for rows that read the zero line
+    int ktc, tap;
+    __device__ __forceinline__ void recompute(const GemmK& p, const RowInfo (&ri)[ROWS], int kc) {
+        const ASrc s = a_source(p, ktc, kc);
+#pragma unroll
+        for (int i = 0; i < ROWS; ++i) {
+            const int sr = src_row<MODE>(p, ri[i], tap);
+            ap[i] = a_addr(p, s, sr);
+            astep[i] = sr < 0 ? 0 : 64;
+        }
+    }
+    __device__ __forceinline__ void start(const GemmK& p, const RowInfo (&ri)[ROWS], int kc, int kt0 = 0, int ntap = 1) {
+        tap = kt0 / ntap;          // (tap-major order; ORD 1 launches always start at K-tile 0)
+        ktc = kt0 - tap * ntap;
+        recompute(p, ri, kc);
+    }
+    __device__ __forceinline__ void next(const GemmK& p, const RowInfo (&ri)[ROWS], int kc, int ntap) {
+        if constexpr (ORD == 1) {
+            if (++tap == p.taps) {
+                tap = 0;
+                ++ktc;
+            }
+            recompute(p, ri, kc);
+            return;
+        }
+        if (++ktc == ntap) {
+            ktc = 0;
+            ++tap;
+        }
+        if (ktc == 0 || ktc == p.nt0) {
+            recompute(p, ri, kc);
+        } else {
+#pragma unroll
+            for (int i = 0; i < ROWS; ++i) ap[i] += astep[i];
+        }
+    }
+    // The same step in two parts (ORD 0; the one-wave kernel of gemm_sw.hip only): `bump` = the pointer adds, UNCONDITIONAL, issued
+    // inside the K-tile body as fillers between MFMAs; `count` = the counters and -- when the tap or the source changes -- the
+    // recomputation that overwrites the bumped pointers, between two bodies.  With one wave per SIMD every VALU instruction between
+    // two bodies is matrix-pipe idle time.
+    __device__ __forceinline__ void bump() {
+#pragma unroll
+        for (int i = 0; i < ROWS; ++i) ap[i] += astep[i];
+    }
+    __device__ __forceinline__ void count(const GemmK& p, const RowInfo (&ri)[ROWS], int kc, int ntap) {
+        if (++ktc == ntap) {
+            ktc = 0;
+            ++tap;
+        }
+        if (ktc == 0 || ktc == p.nt0) recompute(p, ri, kc);
+    }
+};
+
 __device__ __forceinline__ void glds16(const half_t* g, char* lds_wave_base) {
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
                                      (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
 }
 
+// The fragment reads below are inline asm with hand-counted waits; what that relies on is checked over the generated assembly by
+// tests/test_isa_guards.py (no scratch access / copy of a pending destination, every MFMA covered by its counted wait).  Validated
+// with ROCm 7.2's hipcc only: a different compiler may schedule around the asm differently -- rerun that test and `-m gpu`.
+#if defined(HIP_VERSION_MAJOR) && (HIP_VERSION_MAJOR != 7 || HIP_VERSION_MINOR != 2)
+#warning "GEMM kernels: inline-asm LDS fragment reads were validated with ROCm 7.2 only; rerun tests/test_isa_guards.py and the -m gpu suite"
+#endif
+// Fragment reads of a K-tile are issued as inline asm with hand-counted `s_waitcnt lgkmcnt(n)`: with an LDS-DMA load
+// (global_load_lds) in flight hipcc treats the LGKM counter as out of order and waits lgkmcnt(0) before every fragment use,
+// i.e. also for the fragment it has just requested two groups ahead -- the roll degenerates into issue -> full LDS latency ->
+// use (tools/wait_probe.hip reproduces it in 30 lines).  LDS reads return in order among themselves, and the DMA completes on
+// vmcnt, so the wait a use needs is "all but the reads issued after mine".
+__device__ __forceinline__ h8 lds_frag(unsigned base, int off) {  // off: a constant after unrolling (16-bit immediate)
+    h8 v;
+    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(base), "n"(off) : "memory");
+    return v;
+}
+__device__ __forceinline__ h8 lds_frag(unsigned addr) {
+    h8 v;
+    asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(addr) : "memory");
+    return v;
+}
+__device__ __forceinline__ void lgkm_wait(int n) {  // n is a constant after unrolling; the switch folds to one s_waitcnt
+    switch (n) {
+#define AV_LGW(k) case k: asm volatile("s_waitcnt lgkmcnt(" #k ")" ::: "memory"); break;
+        AV_LGW(0) AV_LGW(1) AV_LGW(2) AV_LGW(3) AV_LGW(4) AV_LGW(5) AV_LGW(6) AV_LGW(7) AV_LGW(8) AV_LGW(9) AV_LGW(10)
+        AV_LGW(11) AV_LGW(12) AV_LGW(13) AV_LGW(14) AV_LGW(15)
+#undef AV_LGW
+        default: asm volatile("s_waitcnt lgkmcnt(15)" ::: "memory"); break;  // (more than 15 younger reads: the counter saturates there)
+    }
+}
+
+// accumulator element -> VGPR, AT the use (one-wave kernels, accumulators in AGPRs): left to hipcc, the AGPR -> VGPR copies of all 240
+// accumulators are hoisted to the top of the epilogue (they are copies of phi values), which overflows the 256 arch VGPRs into AGPRs
+// and the accumulators into scratch
+__device__ __forceinline__ float acc_read(const float& a) {
+    float v;
+    asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(v) : "a"(a));
+    return v;
+}
 
 // GroupNorm records (K, sum(x - K), sum((x - K)^2)) of one 16-row x 160-column slab of the stored fp16 output, read back from LDS
 // (row stride `ld` halves): one record per channel group of `cg` channels (cg divides 40), K = the record's first element.  Lane
@@ -134,7 +237,15 @@ __device__ __forceinline__ void gn_slab_records(const half_t* slab, int ld, int 
     }
 }
 
-// ---- launchers of the kernels outside gemm.hip: k filled by anyv2v_gemm_f16 from the descriptor and the plan (tiles, grid, raster) ----
+// ---- launchers, one per kernel family: k filled by anyv2v_gemm_f16 (gemm.hip) from the descriptor and the plan (tiles, grid, split-K
+// factor, raster); a launcher only picks the template instantiation ----
+// 128 x NF*32 tile kernel (gemm_mfma.hip), persistent 192 x 320 kernel (gemm_big.hip), its ping-pong form (gemm_pp.hip; opt-in)
+int av_gemm_mfma_launch(const GemmK& k, const AnyV2VGemmDesc* d, const GemmPlan& plan, hipStream_t s);
+int av_gemm_big_launch(const GemmK& k, const AnyV2VGemmDesc* d, const GemmPlan& plan, hipStream_t s);
+int av_gemm_pp_launch(const GemmK& k, const AnyV2VGemmDesc* d, const GemmPlan& plan, hipStream_t s);
+// one thread per output element; the second pass of the split-K launches of the two kernels above (gemm_ref.hip)
+int av_gemm_naive_launch(const GemmK& k, const AnyV2VGemmDesc* d, const GemmPlan& plan, hipStream_t s);
+void av_gemm_splitk_reduce_launch(const GemmK& k, hipStream_t s);
 // weight-stationary kernel (gemm_ws.hip): how (slab, row range) are dealt to the 256 blocks
 struct WsPlan {
     int S;        // 160-column W slabs (= blocks per row range)

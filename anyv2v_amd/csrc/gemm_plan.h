@@ -1,6 +1,6 @@
 // Launch plan of anyv2v_gemm_f16: which kernel family runs a descriptor, at which tile width, split-K factor, grid and tile order.
 // A pure function of the descriptor and the batch-hinted row count (no HIP, no globals): plain C++17, built for the host alone by
-// tests/test_gemm_plan_host.py.  gemm.hip plans, then launches what the plan says; anyv2v_gemm_gn_stats_floats only plans.
+// tests/test_gemm_plan_host.py.  gemm.hip plans, then calls the launcher of the family the plan names; anyv2v_gemm_gn_stats_floats only plans.
 #pragma once
 #include <stddef.h>
 

@@ -23,135 +23,30 @@
 #include <stdlib.h>
 #include <type_traits>
 
-#include "gemm_common.h"
+#include "gemm_onewave.h"
 
 namespace {
 
-#ifndef SW_MF_
-#define SW_MF_ 6
-#endif
-constexpr int SW_MF = SW_MF_;          // 16-row fragments per wave (6: 96 rows, two wave rows -> 192-row block tile)
-constexpr int SW_BM = 32 * SW_MF, SW_BN = 320;
-constexpr int SW_A_BYTES = SW_BM * 128, SW_B_BYTES = SW_BN * 128;   // one K-tile (64 deep): 24 KiB of A, 40 KiB of W
+constexpr int SW_A_BYTES = SW_BM * 128;   // A of one K-tile (64 deep): 24 KiB
 #ifndef SW_ALA
 #define SW_ALA 1   // K-tiles the A stream runs ahead of the consumer: 1 = two A slots, 2 = a ring of three (see the kernel)
 #endif
 
 template <bool REAL = true>
 __device__ __forceinline__ h8 sw_frag(unsigned base, int off) {  // off: a constant after unrolling (16-bit immediate)
-    h8 v;
-    if constexpr (REAL)
-        asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(base), "n"(off) : "memory");
-    else
-    {   // (probe: a register constant instead of the read)
+    if constexpr (REAL) {
+        return lds_frag(base, off);
+    } else {   // (probe: a register constant instead of the read)
         u4 x;
 #pragma unroll
         for (int e = 0; e < 4; ++e) asm volatile("v_mov_b32 %0, %1" : "=v"(x[e]) : "v"(0x3c003c00u + base * 0));
-        v = __builtin_bit_cast(h8, x);
-    }
-    return v;
-}
-__device__ __forceinline__ void sw_lgkm(int n) {  // n is a constant after unrolling; the switch folds to one s_waitcnt
-    switch (n) {
-#define AV_LGW(k) case k: asm volatile("s_waitcnt lgkmcnt(" #k ")" ::: "memory"); break;
-        AV_LGW(0) AV_LGW(1) AV_LGW(2) AV_LGW(3) AV_LGW(4) AV_LGW(5) AV_LGW(6) AV_LGW(7) AV_LGW(8) AV_LGW(9) AV_LGW(10)
-        AV_LGW(11) AV_LGW(12) AV_LGW(13) AV_LGW(14) AV_LGW(15)
-#undef AV_LGW
-        default: asm volatile("s_waitcnt lgkmcnt(15)" ::: "memory"); break;
+        return __builtin_bit_cast(h8, x);
     }
 }
-
-// accumulator element -> VGPR, AT the use: left to hipcc, the AGPR -> VGPR copies of all 240 accumulators are hoisted to the top of the
-// epilogue (they are copies of phi values), which overflows the 256 arch VGPRs into AGPRs and the accumulators into scratch
-__device__ __forceinline__ float sw_acc(const float& a) {
-    float v;
-    asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(v) : "a"(a));
-    return v;
-}
-
-// gather addressing of the six A rows a thread stages per K-tile (rows srow0 + 32 i): inside one (tap, source) run consecutive
-// K-tiles only advance the channel offset; the row -> shifted-row math is redone when the tap or the source changes
-// ORD (conv2d): 0 = tap-major K order (tap, channel slice) as gemm_big_kernel; 1 = slice-major (channel slice, dy, dx): the three dx taps
-// of one (slice, dy) are consecutive K-tiles and touch the same A lines shifted by one pixel -- L1 (TCP) hits when nothing else
-// allocates there in between (the W pieces then go past L1, `sc1`)
-template <int MODE, int ORD = 0>
-struct SwGen {
-    const half_t* ap[SW_MF];
-    int astep[SW_MF];
-    int ktc, tap;
-    __device__ __forceinline__ void recompute(const GemmK& p, const RowInfo (&ri)[SW_MF], int kc) {
-        const ASrc s = a_source(p, ktc, kc);
-#pragma unroll
-        for (int i = 0; i < SW_MF; ++i) {
-            const int sr = src_row<MODE>(p, ri[i], tap);
-            ap[i] = a_addr(p, s, sr);
-            astep[i] = sr < 0 ? 0 : 64;
-        }
-    }
-    __device__ __forceinline__ void start(const GemmK& p, const RowInfo (&ri)[SW_MF], int kc, int kt0 = 0, int ntap = 1) {
-        tap = kt0 / ntap;          // (tap-major order; ORD 1 launches always start at K-tile 0)
-        ktc = kt0 - tap * ntap;
-        recompute(p, ri, kc);
-    }
-    __device__ __forceinline__ void next(const GemmK& p, const RowInfo (&ri)[SW_MF], int kc, int ntap) {
-        if constexpr (ORD == 1) {
-            if (++tap == p.taps) {
-                tap = 0;
-                ++ktc;
-            }
-            recompute(p, ri, kc);
-            return;
-        }
-        if (++ktc == ntap) {
-            ktc = 0;
-            ++tap;
-        }
-        if (ktc == 0 || ktc == p.nt0) {
-            recompute(p, ri, kc);
-        } else {
-#pragma unroll
-            for (int i = 0; i < SW_MF; ++i) ap[i] += astep[i];
-        }
-    }
-    // The same step in two parts (ORD 0): `bump` = the pointer adds, UNCONDITIONAL, issued inside the K-tile body as fillers between
-    // MFMAs; `count` = the counters and -- when the tap or the source changes -- the recomputation that overwrites the bumped pointers,
-    // between two bodies.  With one wave per SIMD every VALU instruction between two bodies is matrix-pipe idle time.
-    __device__ __forceinline__ void bump() {
-#pragma unroll
-        for (int i = 0; i < SW_MF; ++i) ap[i] += astep[i];
-    }
-    __device__ __forceinline__ void count(const GemmK& p, const RowInfo (&ri)[SW_MF], int kc, int ntap) {
-        if (++ktc == ntap) {
-            ktc = 0;
-            ++tap;
-        }
-        if (ktc == 0 || ktc == p.nt0) recompute(p, ri, kc);
-    }
-};
 
 __device__ __forceinline__ void glds16_sc1(const half_t* g, char* lds_wave_base) {   // the same piece past L1 (sc1): L2-served, no TCP line
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
                                      (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 16);
-}
-
-// W row (relative to the wave slab's first row) that LDS row `s + 32 * piece` of the slab holds, as  row = wrow_thread(s) + wrow_piece(piece):
-//  plain : LDS rows of a fragment pair (32 rows) hold W rows 8 (i / 4) + 4 f + i % 4  (f = fragment of the pair, i = row in it)
-//  GEGLU : W comes as 32-row blocks [16 h | 16 gate]; two blocks form a 64-row group [hA gA hB gB] whose A / B fragments interleave
-//          4-channel runs the same way; the fifth block of the slab stays in natural order (its outputs leave as 8-byte stores)
-template <bool GEGLU>
-__device__ __forceinline__ int sw_wrow_thread(int s) {
-    const int i = s & 15, f = s >> 4;
-    if constexpr (GEGLU)
-        return 32 * (i >> 3) + 16 * f + 8 * ((i >> 2) & 1) + (i & 3);
-    else
-        return 8 * (i >> 2) + 4 * f + (i & 3);
-}
-template <bool GEGLU>
-__device__ __forceinline__ constexpr int sw_wrow_piece(int pl) {   // pl: piece within the wave slab, 0..4
-    if constexpr (GEGLU)
-        return pl < 4 ? 64 * (pl >> 1) + 4 * (pl & 1) : 128;
-    else
-        return 32 * pl;
 }
 
 }  // namespace
@@ -221,7 +116,7 @@ __global__ __launch_bounds__(256, 1) void gemm_sw_kernel(const GemmK p) {
     RowInfo ri[MF];
     constexpr int ORD = (MODE == MODE_CONV2D && (KO == 7 || KO == 8)) ? 1 : 0;   // (probe builds: slice-major conv K order)
     constexpr bool WSC1 = KO == 7;                                                // (probe builds: W pieces past L1)
-    SwGen<MODE, ORD> gen;
+    AGen<MODE, MF, ORD> gen;
     int w_tap = 0, w_slice = 0;   // ORD 1: position of the W stream inside the tile
     int a_tile, a_kt;      // A stream position (a_tile >= ntiles: past the end, its pieces read the zero line)
     const half_t* bptr;    // W row of LDS row srow0 of wave slab 0 (pieces: + sw_wrow_piece rows, slab 1: + 160 rows)
@@ -355,7 +250,7 @@ __global__ __launch_bounds__(256, 1) void gemm_sw_kernel(const GemmK p) {
             {
                 int need = w_seq[g];
                 if (g == 10 && a1_seq > need) need = a1_seq;
-                if (need > 0 && g < 18) sw_lgkm(seq - need);   // (groups 18 / 19: covered by the lgkmcnt(0) in front of the barrier)
+                if (need > 0 && g < 18) lgkm_wait(seq - need);   // (groups 18 / 19: covered by the lgkmcnt(0) in front of the barrier)
                 __builtin_amdgcn_sched_barrier(0);
             }
 #pragma unroll
@@ -501,7 +396,7 @@ __global__ __launch_bounds__(256, 1) void gemm_sw_kernel(const GemmK p) {
                         col = 32 * (nf >> 1) + 8 * lq + 4 * (nf & 1);
                     f4 v;
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = sw_acc(acc[mf][nf][e]);
+                    for (int e = 0; e < 4; ++e) v[e] = acc_read(acc[mf][nf][e]);
                     *(f4*)(srow + col) = v;
                 }
                 __builtin_amdgcn_sched_barrier(0);
@@ -544,7 +439,7 @@ __global__ __launch_bounds__(256, 1) void gemm_sw_kernel(const GemmK p) {
                         h8 o;
 #pragma unroll
                         for (int e = 0; e < 4; ++e) {
-                            float v0 = sw_acc(acc[mf][2 * q][e]) + (float)bias8[q][e], v1 = sw_acc(acc[mf][2 * q + 1][e]) + (float)bias8[q][4 + e];
+                            float v0 = acc_read(acc[mf][2 * q][e]) + (float)bias8[q][e], v1 = acc_read(acc[mf][2 * q + 1][e]) + (float)bias8[q][4 + e];
                             if constexpr (HAS_RV) {
                                 v0 += (float)tv[q][e];
                                 v1 += (float)tv[q][4 + e];
@@ -587,8 +482,8 @@ __global__ __launch_bounds__(256, 1) void gemm_sw_kernel(const GemmK p) {
                 for (int np = 0; np < 5; ++np) {
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
-                        const float hv = sw_acc(acc[mf][2 * np][e]) + (float)bh[np][e];
-                        const float gv = sw_acc(acc[mf][2 * np + 1][e]) + (float)bg[np][e];
+                        const float hv = acc_read(acc[mf][2 * np][e]) + (float)bh[np][e];
+                        const float gv = acc_read(acc[mf][2 * np + 1][e]) + (float)bg[np][e];
                         o[np][e] = (half_t)(hv * av_gelu(gv));
                     }
                 }
@@ -685,8 +580,6 @@ __global__ __launch_bounds__(256) void gemm_sw_fixup_kernel(const GemmK p, int G
 
 // ---------------------------------------------------------------------------------------------------------
 // host side (eligibility, tiles, grid and tile order: gemm_plan.cpp)
-static_assert(SW_BM == AV_GEMM_BM && SW_BN == AV_GEMM_BN, "the plan counts tiles of this size");
-
 template <int MODE, bool SK>
 static void sw_launch_mode(const GemmK& k, const AnyV2VGemmDesc* d, dim3 grid, hipStream_t s) {
     if constexpr (MODE == MODE_LINEAR) {

@@ -22,43 +22,12 @@
 // pipeline_i2vgen_xl.py:1146.
 #include <type_traits>
 
-#include "gemm_common.h"
-
-namespace {
-
-constexpr int SWH_MF = 6, SWH_BM = 192, SWH_BN = 320, SWH_B_BYTES = SWH_BN * 128;
-
-__device__ __forceinline__ h8 swh_frag(unsigned addr) {
-    h8 v;
-    asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(addr) : "memory");
-    return v;
-}
-__device__ __forceinline__ h8 swh_frag_off(unsigned base, int off) {  // off: a constant after unrolling (16-bit immediate)
-    h8 v;
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(base), "n"(off) : "memory");
-    return v;
-}
-__device__ __forceinline__ void swh_lgkm(int n) {  // n is a constant after unrolling; the switch folds to one s_waitcnt
-    switch (n) {
-#define AV_LGW(k) case k: asm volatile("s_waitcnt lgkmcnt(" #k ")" ::: "memory"); break;
-        AV_LGW(0) AV_LGW(1) AV_LGW(2) AV_LGW(3) AV_LGW(4) AV_LGW(5) AV_LGW(6) AV_LGW(7) AV_LGW(8) AV_LGW(9) AV_LGW(10)
-        AV_LGW(11) AV_LGW(12) AV_LGW(13) AV_LGW(14) AV_LGW(15)
-#undef AV_LGW
-        default: asm volatile("s_waitcnt lgkmcnt(15)" ::: "memory"); break;
-    }
-}
-__device__ __forceinline__ float swh_acc(const float& a) {   // AGPR -> VGPR at the use (see gemm_sw.hip, sw_acc)
-    float v;
-    asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(v) : "a"(a));
-    return v;
-}
-
-}  // namespace
+#include "gemm_onewave.h"
 
 // WI: image width (16 / 32 / 64); EPI: 0 = bias (+ temb row vector), 1 = bias + residual
 template <int WI, int EPI>
 __global__ __launch_bounds__(256, 1) void gemm_swh_kernel(const GemmK p) {
-    constexpr int MF = SWH_MF, BM = SWH_BM, BN = SWH_BN, B_BYTES = SWH_B_BYTES;
+    constexpr int MF = SW_MF, BM = SW_BM, BN = SW_BN, B_BYTES = SW_B_BYTES;
     constexpr int RT = BM / WI;                 // image rows per tile
     constexpr int P = WI + 8;                   // patch pitch in pixels (pad pixel | WI pixels | pad pixel | 6 unused)
     constexpr int PPIX = RT * P;                // pixel rows of a patch (128 bytes each: one 64-channel slice)
@@ -131,7 +100,7 @@ __global__ __launch_bounds__(256, 1) void gemm_swh_kernel(const GemmK p) {
 
     // ---- W stream (one K-tile ahead): K-tile (dy, slice, dx) reads W columns ((3 dy + dx) ntap + slice) * 64 ----
     const int srow0 = tid >> 3, kc = (tid & 7) ^ (srow0 & 7);
-    const int wperm = 8 * ((srow0 & 15) >> 2) + 4 * (srow0 >> 4) + (srow0 & 3);   // W row permutation of gemm_sw.hip (plain form)
+    const int wperm = sw_wrow_thread<false>(srow0);   // W row permutation of the one-wave kernels (plain form)
     const half_t* wbase;   // W row (n_blk + wperm), column kc * 8
     int w_tile, w_dy = 0, w_slice = 0, w_dx = 0;
     auto w_start = [&](int item) {
@@ -207,7 +176,7 @@ __global__ __launch_bounds__(256, 1) void gemm_swh_kernel(const GemmK p) {
             {
                 int need = w_seq[g];
                 if (g == 10 && a1_seq > need) need = a1_seq;
-                if (need > 0 && g < 18) swh_lgkm(seq - need);
+                if (need > 0 && g < 18) lgkm_wait(seq - need);
                 __builtin_amdgcn_sched_barrier(0);
             }
 #pragma unroll
@@ -220,12 +189,12 @@ __global__ __launch_bounds__(256, 1) void gemm_swh_kernel(const GemmK p) {
             }
             __builtin_amdgcn_sched_barrier(0);
             if (g >= 3 && g < 3 + MF) {
-                a1[g - 3] = swh_frag(ab1 + offA[g - 3]);
+                a1[g - 3] = lds_frag(ab1 + offA[g - 3]);
                 a1_seq = ++seq;
             }
             if (g + 3 < 20) {
                 const int t = g + 3;
-                wq[t & 3] = swh_frag_off(bbase[t / 10], (t % 10) * 2048);
+                wq[t & 3] = lds_frag(bbase[t / 10], (t % 10) * 2048);
                 w_seq[t] = ++seq;
             }
             if (g < 4) {
@@ -239,11 +208,11 @@ __global__ __launch_bounds__(256, 1) void gemm_swh_kernel(const GemmK p) {
                 __builtin_amdgcn_s_barrier();
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-                for (int mf = 0; mf < MF; ++mf) a0[mf] = swh_frag(nab + offA[mf]);
-                wq[0] = swh_frag_off(nbbase, 0);
-                wq[1] = swh_frag_off(nbbase, 2048);
+                for (int mf = 0; mf < MF; ++mf) a0[mf] = lds_frag(nab + offA[mf]);
+                wq[0] = lds_frag(nbbase, 0);
+                wq[1] = lds_frag(nbbase, 2048);
             }
-            if (g == 18) wq[2] = swh_frag_off(nbbase, 2 * 2048);
+            if (g == 18) wq[2] = lds_frag(nbbase, 2 * 2048);
             __builtin_amdgcn_sched_barrier(0);
         }
         static_assert(NPIECE <= 8 + 13, "all pieces of a body are issued by group 16");
@@ -268,10 +237,10 @@ __global__ __launch_bounds__(256, 1) void gemm_swh_kernel(const GemmK p) {
     {
         const unsigned na = sm0 + a_lane(0, 0), nb = sm0 + b_off + wc0;
 #pragma unroll
-        for (int mf = 0; mf < MF; ++mf) a0[mf] = swh_frag(na + offA[mf]);
-        wq[0] = swh_frag_off(nb, 0);
-        wq[1] = swh_frag_off(nb, 2048);
-        wq[2] = swh_frag_off(nb, 2 * 2048);
+        for (int mf = 0; mf < MF; ++mf) a0[mf] = lds_frag(na + offA[mf]);
+        wq[0] = lds_frag(nb, 0);
+        wq[1] = lds_frag(nb, 2048);
+        wq[2] = lds_frag(nb, 2 * 2048);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_sched_barrier(0);
     }
@@ -347,7 +316,7 @@ __global__ __launch_bounds__(256, 1) void gemm_swh_kernel(const GemmK p) {
                     h8 o;
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
-                        float v0 = swh_acc(acc[mf][2 * q][e]) + (float)bias8[q][e], v1 = swh_acc(acc[mf][2 * q + 1][e]) + (float)bias8[q][4 + e];
+                        float v0 = acc_read(acc[mf][2 * q][e]) + (float)bias8[q][e], v1 = acc_read(acc[mf][2 * q + 1][e]) + (float)bias8[q][4 + e];
                         if constexpr (HAS_RV) {
                             v0 += (float)tv[q][e];
                             v1 += (float)tv[q][4 + e];
@@ -376,8 +345,6 @@ __global__ __launch_bounds__(256, 1) void gemm_swh_kernel(const GemmK p) {
 
 // ---------------------------------------------------------------------------------------------------------
 // host side (eligibility, tiles and grid: gemm_plan.cpp)
-static_assert(SWH_BM == AV_GEMM_BM && SWH_BN == AV_GEMM_BN, "the plan counts tiles of this size");
-
 template <int WI>
 static void swh_launch_w(const GemmK& k, const AnyV2VGemmDesc* d, dim3 grid, hipStream_t s) {
     if (d->R != nullptr)

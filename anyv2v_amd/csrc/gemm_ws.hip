@@ -3,7 +3,7 @@
 // Replaces (reference = TIGER-AI-Lab/AnyV2V): attn.to_q / to_k / to_v / to_out[0] at the 320-channel level
 // (i2vgen-xl/pnp_utils.py:175,182-183,216), and the diffusers-0.26.3 Transformer2DModel / TransformerTemporalModel
 // proj_in / proj_out and FeedForward GEGLU up-projection behind pipeline_i2vgen_xl.py:1146 -- the layers where a row of
-// the token matrix is 640 bytes and the tile kernels of gemm.hip spend more time switching tiles than multiplying
+// the token matrix is 640 bytes and the tile kernels (gemm_mfma.hip, gemm_big.hip) spend more time switching tiles than multiplying
 // (profiles/r02_shape_report_B3.txt: 447-642 TF/s, HISTORY.md section 9).
 //
 // Structure:

@@ -391,7 +391,7 @@ class GEGLU(nn.Module):
         self._w = self._b = None
 
     def pack(self):
-        """Interleave [16 rows of h | 16 rows of gate] so that a lane holds matching (h, gate) pairs (gemm.hip)."""
+        """Interleave [16 rows of h | 16 rows of gate] so that a lane holds matching (h, gate) pairs (the GEGLU epilogues of gemm_mfma.hip / gemm_big.hip)."""
         w, b = self.proj.weight.data, self.proj.bias.data
         n = self.dim_out
         assert n % 16 == 0

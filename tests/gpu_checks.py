@@ -184,7 +184,7 @@ def check_gemm_big(extra=0, tag="big", exact=True):
             yn = ops.gemm(a, w, bias=bias, rowvec=rv, rowvec_div=rvd, residual=r, naive=True)
             out.append(_res(f"gemm[{tag}] == naive kernel M{M} N{N} K{K}", y, yn.float(), 2e-3))
             # the two tile-kernel families accumulate every output element in the same order: BIT-equal without split-K (what lets a
-            # batch-hinted launch keep its own kernel family and only take the reference launch's split factor, gemm.hip dispatch)
+            # batch-hinted launch keep its own kernel family and only take the reference launch's split factor, gemm_plan.cpp)
             ops.GEMM_FLAGS = (saved & ~8) | 4 | 16
             ys = ops.gemm(a, w, bias=bias, rowvec=rv, rowvec_div=rvd, residual=r)
             ops.GEMM_FLAGS = (saved & ~4) | 8 | extra

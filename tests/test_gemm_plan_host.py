@@ -1,8 +1,8 @@
 """The GEMM launch planner (anyv2v_amd/csrc/gemm_plan.cpp) on the CPU: which kernel family, tile width, split-K factor, grid and
 tile order a descriptor gets.  The planner is plain C++; this test builds it with the host compiler under the address and
 undefined-behaviour sanitizers, next to tests/gemm_plan_main.cpp, runs that program once as its own process and compares the plans
-with a table worked out BY HAND from the rules of the dispatch code the planner replaced (gemm_impl / dispatch<MODE> of gemm.hip
-and the eligibility helpers of gemm_ws.hip / gemm_sw.hip / gemm_swh.hip) -- each row says how.  No GPU.
+with a table worked out BY HAND from the rules of the dispatch code the planner replaced (gemm_impl / dispatch<MODE> of gemm.hip as it was
+then, and the eligibility helpers of gemm_ws.hip / gemm_sw.hip / gemm_swh.hip) -- each row says how.  No GPU.
 
 Every row: flags = 2 (LDS-DMA staging) unless it says otherwise, a 128 MiB workspace, 16-byte aligned fake pointers,
 hinted rows = M, ldc = N.  nk = K-tiles of 64 = taps x (C0 + C1) / 64; tb = 192 x 320 tiles; tm = 128-row tiles; the split-K rules see

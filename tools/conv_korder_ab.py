@@ -3,7 +3,7 @@ before) against the product library (slice-major (slice, tap) with the increment
 (each arm three times, median of medians), every 3x3 conv shape of the step pair incl. stride 2, the folded nearest-x2 up-sampler and the
 two-source (skip concat) convs.  gpurun_out/r06_conv_slice_major_ab.txt
 The slice-major form is tools/experiments/conv_slice_major_default_path.patch (v2: pointer math at issue time; v1 had it in next());
-build the product library with the patch applied and the un-patched gemm.hip / gemm_sw.hip into tools/libanyv2v_hip_prev.so."""
+build the product library with the patch applied and the un-patched tree (the patch applies to gemm.hip / gemm_sw.hip of commit d39fba4) into tools/libanyv2v_hip_prev.so."""
 import os
 import subprocess
 import sys

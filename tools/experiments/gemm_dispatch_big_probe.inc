@@ -1,4 +1,4 @@
-// Probe build only (-DANYV2V_EXPERIMENTS, `make -C anyv2v_amd/csrc experiments`): included from gemm.hip's launch<MODE>() in front of
+// Probe build only (-DANYV2V_EXPERIMENTS, `make -C anyv2v_amd/csrc experiments`): included from gemm_big.hip's big_launch_mode<MODE>() in front of
 // the persistent-kernel launch.  Flag bit5 + a workspace: the TRACE instantiation writes 32 s_memtime stamps per block
 // (tools/gemm_big_trace.py).  The product library contains none of these instantiations.
             if ((d->flags & ANYV2V_GEMM_PROBE_TRACE) && d->workspace != nullptr && (size_t)grid.x * 32 * sizeof(long long) <= (size_t)d->workspace_bytes) {

@@ -1,4 +1,4 @@
-// Probe build only (-DANYV2V_EXPERIMENTS): included from gemm.hip's launch<MODE>() in front of the 128-row kernel launch.
+// Probe build only (-DANYV2V_EXPERIMENTS): included from gemm_mfma.hip's mfma_launch_mode<MODE>() in front of the 128-row kernel launch.
 // Flag bit5: per-block phase timestamps; flags bits 6-8: K-loop knock-outs (wrong results by design) -- tools/gemm_trace.py.
     if ((d->flags & ANYV2V_GEMM_PROBE_TRACE) && glds && k.splits == 1 && d->workspace != nullptr &&
         (size_t)grid.x * 32 * sizeof(long long) <= (size_t)d->workspace_bytes) {  // debug: per-block phase timestamps

@@ -1,4 +1,4 @@
-"""A/B of two builds of the library on the default dispatch: tools/libanyv2v_hip_prev.so (the previous commit's gemm.hip) against the product
+"""A/B of two builds of the library on the default dispatch: tools/libanyv2v_hip_prev.so (the previous commit's GEMM sources) against the product
 library, alternating PROCESSES on one box (each arm three times, median of medians), seeded inputs, and a checksum of every output so that
 bit-equality between the two builds shows.  Shapes: the tile-kernel launches of the B = 3 edit step and the B = 1 inversion step.
     python tools/lib_ab.py [tag]      -> gpurun_out/<tag>.txt"""

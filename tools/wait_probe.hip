@@ -1,7 +1,7 @@
 // Reproducer (compile only: hipcc --offload-arch=gfx950 -O3 -S --cuda-device-only tools/wait_probe.hip -o - | grep -n "ds_read\|s_waitcnt\|mfma"):
 // with an LDS-DMA load (global_load_lds) in flight, hipcc (ROCm 7.2) waits lgkmcnt(0) before every use of a ds_read result, also
 // when a younger ds_read is outstanding (lgkmcnt(1) would do: LDS reads return in order, the DMA completes on vmcnt).  Remove the
-// glds16 call inside the loop and the same code gets lgkmcnt(1).  gemm.hip's persistent kernel therefore issues its fragment
+// glds16 call inside the loop and the same code gets lgkmcnt(1).  The persistent kernel (gemm_big.hip) therefore issues its fragment
 // reads as inline asm with hand-counted waits (profiles/r02_gemm_frag_wait_ab.txt).
 #include <hip/hip_runtime.h>
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
