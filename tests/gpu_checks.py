@@ -3923,6 +3923,479 @@ def check_edges_softmax_timestep():
     return out
 
 
+# ------------------------------------------------------------------------------------------------ exact data, tolerance 0
+# Inputs for which the exact result is representable at every intermediate step, so the expected output is known to the last bit
+# whatever the summation order.  The builders run on the CPU (tests/test_exact_host.py checks their conditions and references there);
+# the checks move the operands to the GPU.  Every row: ``err`` = the number of differing elements, ``tol`` = 0.
+def _count_row(name, bad):
+    n = int(bad.sum())
+    return dict(name=name, err=float(n), l2=0.0, tol=0.0, ok=n == 0)
+
+
+def _fp16_tie(v64):
+    """Where a float64 value lies exactly midway between two neighbouring fp16 values (normal range)."""
+    a = v64.abs()
+    _, e = torch.frexp(a)                       # a = m 2^e, m in [0.5, 1): the fp16 step at a is 2^(e - 11)
+    t = torch.ldexp(a, 11 - e)
+    return (t - t.floor()) == 0.5
+
+
+def _xg(name, M, N, C0, *, C1=0, mode=None, geo=None, rowvec_div=0, res=False, act=None, seed=0):
+    mode = ops.MODE_LINEAR if mode is None else mode
+    act = ops.ACT_NONE if act is None else act
+    return dict(name=name, M=M, N=N, C0=C0, C1=C1, mode=mode, geo=geo, rowvec_div=rowvec_div, res=res, act=act, seed=seed)
+
+
+def _xg_conv(name, n, H, W, c0, co, kind, *, c1=0, seed=0):
+    """3x3 convolution specs of ``_conv_edge_cases``' geometries: geo = (n, Hi, Wi, Ho, Wo, stride, up, asym)."""
+    Ho, Wo, stride, up, asym, rvd, res = H, W, 1, 0, 0, 0, False
+    if kind == "s1res":
+        res = True
+    elif kind == "s1temb":
+        rvd = H * W
+    elif kind == "s2":
+        Ho, Wo, stride = H // 2, W // 2, 2
+    elif kind == "up":
+        Ho, Wo, up = 2 * H, 2 * W, 1
+    elif kind == "asym":
+        Ho, Wo, stride, asym = (H - 2) // 2 + 1, (W - 2) // 2 + 1, 2, 1     # F.pad right / bottom by 1, stride 2, no other padding
+    elif kind == "two":
+        c1 = c1 or 128
+    else:
+        raise ValueError(kind)
+    return _xg(name, n * Ho * Wo, co, c0, C1=c1, mode=ops.MODE_CONV2D, geo=(n, H, W, Ho, Wo, stride, up, asym), rowvec_div=rvd, res=res,
+               seed=seed)
+
+
+_XG_CONV_KINDS = (("s1res", "s1 +bias+res"), ("s1temb", "s1 +bias+temb"), ("s2", "stride 2"), ("up", "upsample x2"),
+                  ("asym", "asym pad, stride 2"), ("two", "two-source"))
+XG_CROSS = "conv 3 x 16x16 64->320 s1 +bias+res"    # the one shape every eligible family takes: the cross-family rows
+
+
+def exact_gemm_specs():
+    """name -> spec of every exact-integer GEMM case (smallest shapes that reach each code path; every case has a bias, so that
+    the pre-rounding values sit on the 2^-4 grid and not on the integers)."""
+    specs = []
+    for i, (M, N, K) in enumerate([(197, 320, 128), (261, 320, 128), (197, 640, 192)]):
+        specs.append(_xg(f"M{M} N{N} K{K} +bias+res", M, N, K, res=True, seed=100 + i))
+    specs.append(_xg("M130 N168 K128 +bias+rowvec+res", 130, 168, 128, rowvec_div=50, res=True, seed=110))
+    specs.append(_xg("M130 N12 K128 fp32 out", 130, 12, 128, act=ops.ACT_F32OUT, seed=111))
+    specs.append(_xg("M130 N256 K128 fp32 out", 130, 256, 128, act=ops.ACT_F32OUT, seed=112))
+    for j, (kind, tag) in enumerate(_XG_CONV_KINDS):
+        specs.append(_xg_conv(f"conv 3 x 16x16 64->320 {tag}", 3, 16, 16, 64, 320, kind, seed=120 + j))
+        specs.append(_xg_conv(f"conv 3 x 12x10 64->128 {tag}", 3, 12, 10, 64, 128, kind, seed=130 + j))
+    specs.append(_xg("temporal B2 F5 HW24 64->320 +bias+res", 240, 320, 64, mode=ops.MODE_TEMPORAL, geo=(2, 5, 24), res=True, seed=140))
+    for j, (ci, co) in enumerate([(256, 320), (640, 1280)]):      # the two shapes of check_edges_splitk
+        s = _xg_conv(f"conv 48 x 8x8 {ci}->{co} s1 +bias+temb+res", 48, 8, 8, ci, co, "s1res", seed=150 + j)
+        s["rowvec_div"] = 16 * 64
+        specs.append(s)
+    specs.append(_xg_conv("conv 1 x 32x32 64->320 s1 +bias+res", 1, 32, 32, 64, 320, "s1res", seed=160))
+    specs.append(_xg_conv("conv 1 x 64x64 64->320 s1 +bias+res", 1, 64, 64, 64, 320, "s1res", seed=161))
+    specs.append(_xg("M2049 N320 K320 +bias+res", 2049, 320, 320, res=True, seed=170))
+    specs.append(_xg("M100 N160 K320 +bias", 100, 160, 320, seed=171))
+    specs.append(_xg("M100 N512 K512 +bias+res", 100, 512, 512, res=True, seed=172))
+    out = {s["name"]: s for s in specs}
+    assert len(out) == len(specs) and XG_CROSS in out
+    return out
+
+
+_XG_CASES = {}
+
+
+def exact_gemm_case(spec):
+    """Operands (CPU), the exact pre-rounding values ``v`` (float64) and the contract's expected output ``want`` of one spec:
+    A, W integers in [-r, r] (r = 8 up to K = 4096, 4 above, halved until the range conditions hold), bias / rowvec multiples of 2^-4 in
+    [-32, 32), residual multiples of 2^-4 in [-64, 64).  Seeded; built once per process."""
+    if spec["name"] in _XG_CASES:
+        return _XG_CASES[spec["name"]]
+    M, N, C0, C1, mode, geo = spec["M"], spec["N"], spec["C0"], spec["C1"], spec["mode"], spec["geo"]
+    ci = C0 + C1
+    taps = 1 if mode == ops.MODE_LINEAR else (9 if mode == ops.MODE_CONV2D else 3)
+    K = taps * ci
+    rows_a = M if mode != ops.MODE_CONV2D else geo[0] * geo[1] * geo[2]
+    g = torch.Generator().manual_seed(spec["seed"])
+    grid16 = lambda lim, *shape: (torch.randint(-16 * lim, 16 * lim, shape, generator=g).double() / 16.0)
+    bias, rowvec, res = grid16(32, N), None, None
+    if spec["rowvec_div"]:
+        rowvec = grid16(32, (M + spec["rowvec_div"] - 1) // spec["rowvec_div"], N)
+    if spec["res"]:
+        res = grid16(64, M, N)
+    r = 8 if K <= 4096 else 4
+    while True:
+        a = torch.randint(-r, r + 1, (rows_a, ci), generator=g).double()
+        if mode == ops.MODE_LINEAR:
+            w = torch.randint(-r, r + 1, (N, ci), generator=g).double()
+            wp, v = w, a @ w.t()
+        elif mode == ops.MODE_CONV2D:
+            n, H, W, Ho, Wo, stride, up, asym = geo
+            w = torch.randint(-r, r + 1, (N, ci, 3, 3), generator=g).double()
+            wp = _pack_conv(w)
+            x = a.view(n, H, W, ci).permute(0, 3, 1, 2)
+            if up:
+                x = F.interpolate(x, scale_factor=2.0, mode="nearest")
+            v = F.conv2d(F.pad(x, (0, 1, 0, 1)), w, stride=2) if asym else F.conv2d(x, w, stride=stride, padding=1)
+            assert tuple(v.shape[2:]) == (Ho, Wo)
+            v = _to_tokens(v)
+        else:
+            B, Fr, HW = geo
+            w = torch.randint(-r, r + 1, (N, ci, 3), generator=g).double()
+            wp = w.permute(0, 2, 1).reshape(N, 3 * ci).contiguous()
+            v = F.conv1d(a.view(B, Fr, HW, ci).permute(0, 2, 3, 1).reshape(B * HW, ci, Fr), w, padding=1)
+            v = v.view(B, HW, N, Fr).permute(0, 3, 1, 2).reshape(M, N)
+        v = v + bias
+        if rowvec is not None:
+            v = v + rowvec[torch.arange(M) // spec["rowvec_div"]]
+        # sum_k |a||w| <= K r^2: with |bias| + |rowvec| on top every partial sum in any order stays below 2^18 on the 2^-4 grid, i.e.
+        # within 24 bits: exact in fp32
+        abs_bound = K * r * r + float(bias.abs().max()) + (float(rowvec.abs().max()) if rowvec is not None else 0.0)
+        if abs_bound < 2 ** 18 and float(v.abs().max()) <= 32768 or r == 1:
+            break
+        r //= 2
+    h = v.half()
+    case = dict(spec=spec, r=r, K=K, abs_bound=abs_bound, a0=a[:, :C0].half().contiguous(), a1=a[:, C0:].half().contiguous() if C1 else None,
+                w=wp.half().contiguous(), bias=bias.half(), rowvec=None if rowvec is None else rowvec.half(),
+                res=None if res is None else res.half(), v=v)
+    if spec["act"] == ops.ACT_F32OUT:
+        case["want"] = v.float()
+    else:
+        case["want"] = h if res is None else (h.double() + res).half()       # fp16(fp16(acc + bias + rowvec) + R): gemm_ref.hip
+        case["single"] = None if res is None else (v + res).half()            # one rounding: NOT the contract
+    _XG_CASES[spec["name"]] = case
+    return case
+
+
+def exact_gemm_conditions(case):
+    """The measured conditions of one case (tests/test_exact_host.py asserts them)."""
+    v, h = case["v"], case["v"].half()
+    c = dict(abs_bound=case["abs_bound"], vmax=float(v.abs().max()), unrepresentable=float((h.double() != v).double().mean()),
+             ties=int(_fp16_tie(v).sum()))
+    if case.get("single") is not None:
+        c["single_differs"] = float((case["single"] != case["want"]).double().mean())
+    return c
+
+
+def _xg_launch(case, naive=False):
+    spec = case["spec"]
+    if "dev" not in case:
+        case["dev"] = {k: (None if case[k] is None else case[k].to(DEV)) for k in ("a0", "a1", "w", "bias", "rowvec", "res")}
+        case["dev"]["want"] = case["want"].to(DEV)
+    d = case["dev"]
+    f32 = spec["act"] == ops.ACT_F32OUT
+    out = torch.zeros(spec["M"], (spec["N"] + 7) // 8 * 8, dtype=torch.float32 if f32 else torch.float16, device=DEV)[:, :spec["N"]]
+    kw = {}
+    if spec["mode"] == ops.MODE_CONV2D:
+        kw["conv"] = spec["geo"][1:]
+    elif spec["mode"] == ops.MODE_TEMPORAL:
+        kw["temporal"] = spec["geo"][1:]
+    return ops.gemm(d["a0"], d["w"], a1=d["a1"], bias=d["bias"], rowvec=d["rowvec"], rowvec_div=spec["rowvec_div"], residual=d["res"],
+                    act=spec["act"], out=out, mode=spec["mode"], M=spec["M"], naive=naive, **kw)
+
+
+def _xg_edge_kw(spec):
+    """The spec in the words ``_sw_eligible`` / ``_sk_blocks`` read."""
+    return dict(mode=spec["mode"], residual=True if spec["res"] else None, rowvec=True if spec["rowvec_div"] else None)
+
+
+XG_PERSISTENT_CASES = ("M197 N320 K128 +bias+res", "M261 N320 K128 +bias+res", "M197 N640 K192 +bias+res", XG_CROSS,
+                       "conv 3 x 16x16 64->320 s1 +bias+temb", "temporal B2 F5 HW24 64->320 +bias+res")
+XG_SPLITK_CASES = (("split-K on the 128-row kernel", "conv 48 x 8x8 256->320 s1 +bias+temb+res"),
+                   ("split-K on the persistent kernel", "conv 48 x 8x8 640->1280 s1 +bias+temb+res"))
+XG_LDS_PATCH_CASES = (XG_CROSS, "conv 1 x 32x32 64->320 s1 +bias+res", "conv 1 x 64x64 64->320 s1 +bias+res")
+XG_WS_CASES = ("M2049 N320 K320 +bias+res", "M100 N160 K320 +bias", "M100 N512 K512 +bias+res")
+XG_GROUPS = ("tile reg", "tile glds", "naive", "persistent", "split-K", "LDS patch", "weight-stationary", "cross-family")
+
+
+def _xg_tile_cases(specs):
+    return [n for n, s in specs.items() if n not in XG_WS_CASES and n not in XG_LDS_PATCH_CASES[1:] and not n.startswith("conv 48 x")]
+
+
+def exact_gemm_launches(groups=XG_GROUPS):
+    """(group, family, spec name, GEMM_FLAGS bits, USE_GLDS, naive, skip reason or None) of every launch ``check_gemm_exact`` makes; the
+    cross-family launches are repeats of launches of the other groups and are not listed.  tests/test_gemm_plan_host.py pins the
+    family each one names on the CPU."""
+    specs = exact_gemm_specs()
+    L = []
+    for var in ("tile reg", "tile glds", "naive"):
+        if var in groups:
+            L += [(var, "naive kernel" if var == "naive" else "128-row " + var[5:], n, 4 | 16, var == "tile glds", var == "naive", None)
+                  for n in _xg_tile_cases(specs)]
+    if "persistent" in groups:
+        for fam, bits in PERSISTENT_FAMILIES:
+            for n in XG_PERSISTENT_CASES:
+                s, why = specs[n], None
+                if bits in (1 << 21, 1 << 27) and not _sw_eligible(s["N"], _xg_edge_kw(s), s["C0"]):
+                    why = "shape not eligible for the one-wave-per-SIMD kernel"
+                elif bits == 1 << 27 and _sk_blocks(s["M"], s["N"], _xg_edge_kw(s), s["C0"]) == 0:
+                    why = "fewer than 8 (tile, K-tile) units: no stream-K form"
+                L.append(("persistent", fam, n, bits, True, False, why))
+    if "split-K" in groups:
+        L += [("split-K", fam, n, 0, True, False, None) for fam, n in XG_SPLITK_CASES]
+    if "LDS patch" in groups:
+        L += [("LDS patch", "LDS patch", n, 1 << 28, True, False, None) for n in XG_LDS_PATCH_CASES]
+    if "weight-stationary" in groups:
+        L += [("weight-stationary", "ws", n, 1024, True, False, None) for n in XG_WS_CASES]
+    return L
+
+
+def _xg_run(case, bits, glds, naive):
+    saved, saved_glds = ops.GEMM_FLAGS, ops.USE_GLDS
+    try:
+        ops.USE_GLDS = glds
+        ops.GEMM_FLAGS = ((saved & ~4) | bits) if not bits & 4 else (saved | bits)
+        return _xg_launch(case, naive=naive)
+    finally:
+        ops.GEMM_FLAGS, ops.USE_GLDS = saved, saved_glds
+
+
+def check_gemm_exact(groups=XG_GROUPS):
+    """Every GEMM family on exact-integer data against the epilogue contract of gemm_ref.hip, fp16(fp16(acc + bias + rowvec) + R), bit
+    for bit: the 128-row kernel (register- and LDS-DMA-staged), the naive kernel, the five forced persistent families, both split-K forms
+    (fp32 workspace NaN-filled), the LDS-patch convolution, the weight-stationary kernel; fp32 outputs equal the exact value.  Then, on
+    one shape every eligible family takes, each family's output against the naive kernel's."""
+    out = []
+    specs = exact_gemm_specs()
+    for (group, fam, n, bits, glds, naive, why) in exact_gemm_launches(groups):
+        name = f"exact gemm[{fam}] {n}"
+        if why is not None:
+            out.append(_skip_row(name, why))
+            continue
+        case = exact_gemm_case(specs[n])
+        if group == "split-K":
+            ops._workspace(DEV).fill_(float("nan"))
+        y = _xg_run(case, bits, glds, naive)
+        out.append(_count_row(name + ": differing elements", y != case["dev"]["want"]))
+    if "cross-family" in groups:
+        case = exact_gemm_case(specs[XG_CROSS])
+        y_naive = _xg_run(case, 4 | 16, True, True)
+        fams = [("128-row reg", 4 | 16, False), ("128-row glds", 4 | 16, True)] + [(f, b, True) for f, b in PERSISTENT_FAMILIES] + [("LDS patch", 1 << 28, True)]
+        for fam, bits, glds in fams:
+            out.append(_count_row(f"exact gemm[{fam}] {XG_CROSS} == the naive kernel, bit for bit", _xg_run(case, bits, glds, False) != y_naive))
+        out.append(_skip_row(f"exact gemm[split-K] {XG_CROSS} == the naive kernel", "9 K-tiles: no split-K plan takes this shape"))
+        out.append(_skip_row(f"exact gemm[ws] {XG_CROSS} == the naive kernel", "the weight-stationary kernel takes Linear layers only"))
+    torch.cuda.synchronize()
+    return out
+
+
+def exact_gemm_plan_rows():
+    """(row name, descriptor line for tests/gemm_plan_main.cpp, family the check names) of every launch of ``check_gemm_exact``."""
+    specs = exact_gemm_specs()
+    rows = []
+    for k, (group, fam, n, bits, glds, naive, why) in enumerate(exact_gemm_launches()):
+        if why is not None:
+            continue
+        s = specs[n]
+        flags = (1 if naive else 0) | (2 if glds else 0) | bits
+        ld = (s["N"] + 7) // 8 * 8
+        desc = f"mode={s['mode']} M={s['M']} N={s['N']} C0={s['C0']} C1={s['C1']} ldc={ld} bias=1 act={s['act']} flags={flags}"
+        if s["rowvec_div"]:
+            desc += f" rowvec=1 rowvec_div={s['rowvec_div']}"
+        if s["res"]:
+            desc += " R=1"
+        if s["mode"] == ops.MODE_CONV2D:
+            desc += " Hi={1} Wi={2} Ho={3} Wo={4} stride={5} up={6} asym={7}".format(*s["geo"])
+        elif s["mode"] == ops.MODE_TEMPORAL:
+            desc += " F={1} HW={2}".format(*s["geo"])
+        rows.append((f"exact_{k:03d}", desc, fam, n))
+    return rows
+
+
+# ---- attention: every key, once
+def _xa_rows(batch, S, inner, strides):
+    outer, inner_s, seq = strides
+    i = torch.arange(batch)
+    return ((i // inner) * outer + (i % inner) * inner_s)[:, None] + torch.arange(S)[None] * seq   # [batch, S]
+
+
+def _xa(name, kernel, *, batch, heads, Sq, Sk, d=64, inner=1, q_strides=None, kv_strides=None, kv_div=1, qk_mod=0, causal=False,
+        bias=False, naive=False, seed=0):
+    return dict(name=name, kernel=kernel, batch=batch, heads=heads, Sq=Sq, Sk=Sk, d=d, inner=inner,
+                q_strides=(Sq, 0, 1) if q_strides is None else q_strides, kv_strides=(Sk, 0, 1) if kv_strides is None else kv_strides,
+                kv_div=kv_div, qk_mod=qk_mod, causal=causal, bias=bias, naive=naive, seed=seed)
+
+
+XA_KERNELS = ("4-wave flash", "short one-wave", "shared-softmax 4-wave", "8-wave", "whole-sequence MFMA", "96-key loop", "bias", "generic")
+
+
+def exact_attention_specs():
+    """The smallest shapes that reach each kernel of attention.hip (dispatch: anyv2v_attention_f16 / _small_f16 / _bias_f16)."""
+    S = []
+    t = lambda Fr, HW: dict(inner=HW, q_strides=(Fr * HW, 1, HW), kv_strides=(Fr * HW, 1, HW))   # temporal: a sequence's rows HW apart
+    S.append(_xa("b2 h2 S333", "4-wave flash", batch=2, heads=2, Sq=333, Sk=333, seed=1))
+    S.append(_xa("cross b6 h2 Sq100 Sk145 kv_div3", "4-wave flash", batch=6, heads=2, Sq=100, Sk=145, kv_div=3, seed=2))
+    S.append(_xa("temporal F40 (3 x 20 px) h2", "4-wave flash", batch=60, heads=2, Sq=40, Sk=40, seed=3, **t(40, 20)))
+    for Fr in (16, 8):
+        S.append(_xa(f"temporal F{Fr} (3 x 20 px) h2", "short one-wave", batch=60, heads=2, Sq=Fr, Sk=Fr, seed=4 + Fr, **t(Fr, 20)))
+        S.append(_xa(f"temporal F{Fr} (3 x 20 px) h2 qk_mod (three streams)", "short one-wave", batch=60, heads=2, Sq=Fr, Sk=Fr, qk_mod=20,
+                     seed=5 + Fr, **t(Fr, 20)))
+    S.append(_xa("b3 h1 S333 qk_mod1 (three streams)", "shared-softmax 4-wave", batch=3, heads=1, Sq=333, Sk=333, qk_mod=1, seed=30))
+    S.append(_xa("plain b64 h4 Sq1024 Sk2100 kv_div64", "8-wave", batch=64, heads=4, Sq=1024, Sk=2100, kv_div=64, seed=31))
+    S.append(_xa("shared-softmax b96 h4 S2100 qk_mod32", "8-wave", batch=96, heads=4, Sq=2100, Sk=2100, qk_mod=32, seed=32))
+    for (B, h, Sn, d, causal) in [(2, 3, 257, 80, False), (2, 2, 77, 160, False), (3, 8, 24, 40, False), (3, 4, 77, 64, True)]:
+        S.append(_xa(f"B{B} h{h} S{Sn} d{d} causal={causal}", "whole-sequence MFMA", batch=B, heads=h, Sq=Sn, Sk=Sn, d=d, causal=causal, seed=Sn + d))
+    for (B, h, Sn, d, causal) in [(2, 2, 401, 40, False), (2, 2, 160, 160, False), (1, 2, 401, 56, True)]:
+        S.append(_xa(f"B{B} h{h} S{Sn} d{d} causal={causal}", "96-key loop", batch=B, heads=h, Sq=Sn, Sk=Sn, d=d, causal=causal, seed=Sn + d + 1))
+    S.append(_xa("8 x 80, 16 frames (2 x 6 px): MFMA form", "bias", batch=12, heads=8, Sq=16, Sk=16, d=80, bias=True, seed=40, **t(16, 6)))
+    S.append(_xa("2 x 20, 5 frames (2 x 6 px): generic kernel", "bias", batch=12, heads=2, Sq=5, Sk=5, d=20, bias=True, seed=41, **t(5, 6)))
+    S.append(_xa("naive=True b2 h2 S333", "generic", batch=2, heads=2, Sq=333, Sk=333, naive=True, seed=1))
+    S.append(_xa("naive=True B3 h8 S24 d40", "generic", batch=3, heads=8, Sq=24, Sk=24, d=40, naive=True, seed=64))
+    S.append(_xa("naive=True B3 h4 S77 d64 causal", "generic", batch=3, heads=4, Sq=77, Sk=77, d=64, causal=True, naive=True, seed=141))
+    assert len({s["name"] + s["kernel"] for s in S}) == len(S) and {s["kernel"] for s in S} == set(XA_KERNELS)
+    return S
+
+
+def exact_attention_patterns(spec):
+    """selection everywhere; counting without the causal mask at Sk <= 1024 (there Sk / (Sk +- 1) is no fp16 neighbour of 1 that the
+    rounding of O could hide); the causal edge on the kernels with the causal flag."""
+    return ("selection",) + (("causal edge",) if spec["causal"] else (("counting",) if spec["Sk"] <= 1024 else ()))
+
+
+def _xa_layout(spec):
+    b, kv_div = spec["batch"], spec["kv_div"]
+    n_kv = (b + kv_div - 1) // kv_div
+    rq = _xa_rows(b, spec["Sq"], spec["inner"], spec["q_strides"])
+    rkv = _xa_rows(n_kv, spec["Sk"], spec["inner"], spec["kv_strides"])
+    i = torch.arange(b)
+    iq = i % spec["qk_mod"] if spec["qk_mod"] else i
+    return rq, rkv, i, iq, n_kv, int(rq.max()) + 1, int(rkv.max()) + 1
+
+
+def exact_attention_gain(scale):
+    """The smallest power of two g with 2 g scale log2(e) >= 160."""
+    return 2.0 ** math.ceil(math.log2(80.0 / (scale * math.log2(math.e))))
+
+
+def _xa_keys(Sk, causal):
+    if causal:     # 0, the 64-query block edges +- 1 and the 96-key block edges +- 1
+        ks = {0} | {e + o for e in list(range(64, Sk + 1, 64)) + list(range(96, Sk + 1, 96)) for o in (-1, 0, 1)}
+    else:          # the first and last key of every 16-key step (the 64- and 96-key tile edges are among them), and the last key
+        ks = {k for t in range(0, Sk, 16) for k in (t, t + 15)} | {Sk - 1}
+    return sorted(k for k in ks if 0 <= k < Sk)
+
+
+def exact_attention_case(spec, pattern):
+    """Operands (CPU) and the expectation of one launch: dict(q, k, v [rows, heads * d] fp16, bias or None, rows = the output rows the
+    launch writes, want = their expected values [len(rows), heads * d] fp16, pi / keys = what the pattern selected)."""
+    b, h, Sq, Sk, d = spec["batch"], spec["heads"], spec["Sq"], spec["Sk"], spec["d"]
+    C = h * d
+    rq, rkv, i, iq, n_kv, Mq, Mk = _xa_layout(spec)
+    g = torch.Generator().manual_seed(spec["seed"])
+    gauss = lambda *shape: torch.randn(*shape, generator=g).half()
+    case = dict(spec=spec, pattern=pattern, rows=rq.reshape(-1), bias=None, scale=d ** -0.5)
+    vrows = rkv[i // spec["kv_div"]]                                   # [batch, Sk]: the V rows of element i
+    hh = torch.arange(h)
+    if pattern == "selection":
+        nbits = max(1, math.ceil(math.log2(Sk)))
+        assert 2 <= nbits <= d
+        v = gauss(Mk, C)
+        q, k = torch.zeros(Mq, C, dtype=torch.float16), gauss(Mk, C)
+        s = torch.arange(Sq)
+        if spec["bias"]:   # the selection sits in the bias: q = 0, another permutation per head
+            pi = ((s[None, :] + 3 * hh[:, None] + 1) % Sk)[None].expand(b, h, Sq)
+            bias = torch.full((h, Sq, Sk), -200.0)
+            bias.scatter_(2, pi[0][:, :, None], 0.0)
+            case["bias"] = bias
+        else:
+            codes = torch.zeros(Sk, d)
+            codes[:, :nbits] = ((torch.arange(Sk)[:, None] >> torch.arange(nbits)[None]) & 1).float() * 2 - 1
+            n_q = spec["qk_mod"] if spec["qk_mod"] else b
+            e = torch.arange(n_q)
+            if spec["causal"]:    # a visible key: the query's own, or the one before it on every other (element, head)
+                pi = (s[None, None, :] - ((e[:, None, None] + hh[None, :, None]) & 1)).clamp_min(0).expand(n_q, h, Sq)
+            else:
+                pi = (s[None, None, :] + (e[:, None, None] * h + hh[None, :, None]) * Sq) % Sk
+            gain = exact_attention_gain(case["scale"])
+            k = torch.zeros(Mk, C, dtype=torch.float16)
+            k[rkv.reshape(-1)] = codes.half().repeat(1, h).repeat(n_kv, 1)
+            q[rq[:n_q].reshape(-1)] = (gain * codes[pi.permute(0, 2, 1)]).reshape(n_q * Sq, C).half()     # [n_q, Sq, h, d]
+            pi = pi[iq]                                                  # [batch, h, Sq]
+        vsel = vrows[torch.arange(b)[:, None, None], pi]                # [batch, h, Sq]: V row of (element, head, query)
+        want = v.view(Mk, h, d)[vsel.permute(0, 2, 1), hh[None, None, :]]   # [batch, Sq, h, d]
+        case.update(q=q, k=k, v=v, pi=pi, want=want.reshape(b * Sq, C))
+    else:
+        keys = _xa_keys(Sk, pattern == "causal edge")
+        assert n_kv * h * d >= len(keys), "not enough (element, head, channel) slots for the key sweep"
+        key_c = torch.tensor(keys)[torch.arange(n_kv * C) % len(keys)].view(n_kv, C)       # slot (element, head, channel) -> key
+        v = torch.zeros(Mk, C, dtype=torch.float16)
+        v[rkv[torch.arange(n_kv)[:, None], key_c].reshape(-1), torch.arange(C).repeat(n_kv)] = float(Sk) if pattern == "counting" else 1.0
+        q, k = torch.zeros(Mq, C, dtype=torch.float16), gauss(Mk, C)
+        if spec["bias"]:
+            case["bias"] = torch.zeros(h, Sq, Sk)
+        kc = key_c[i // spec["kv_div"]]                                 # [batch, C]
+        if pattern == "counting":
+            want = torch.ones(b * Sq, C, dtype=torch.float16)
+        else:
+            s = torch.arange(Sq)
+            inv = _round_once_fp16(1.0 / (s.double() + 1.0)).cpu()
+            want = torch.where(kc[:, None, :] > s[None, :, None], torch.zeros((), dtype=torch.float16), inv[None, :, None]).reshape(b * Sq, C)
+        case.update(q=q, k=k, v=v, keys=keys, key_c=kc, want=want)
+    return case
+
+
+def exact_attention_sdpa(case, only):
+    """fp32 SDPA on the CPU with the entry point's addressing, for the batch elements ``only``: [len(only), Sq, heads * d]."""
+    spec = case["spec"]
+    h, d, Sq, Sk = spec["heads"], spec["d"], spec["Sq"], spec["Sk"]
+    rq, rkv, i, iq, n_kv, Mq, Mk = _xa_layout(spec)
+    only = torch.tensor(only)
+    sp = lambda x, rows, S: x[rows.reshape(-1)].float().view(len(only), S, h, d).transpose(1, 2)
+    q, k = sp(case["q"], rq[iq[only]], Sq), sp(case["k"], rkv[iq[only] // spec["kv_div"]], Sk)
+    v = sp(case["v"], rkv[only // spec["kv_div"]], Sk)
+    if case["bias"] is not None:
+        o = F.scaled_dot_product_attention(q, k, v, attn_mask=case["bias"][None], scale=case["scale"])
+    else:
+        o = F.scaled_dot_product_attention(q, k, v, is_causal=spec["causal"], scale=case["scale"])
+    return o.transpose(1, 2).reshape(len(only), Sq, h * d)
+
+
+def exact_attention_bad(case, got):
+    """Elementwise verdict of ``got`` (the written rows, [len(rows), C] fp16) against the expectation: selection and counting bit for
+    bit; causal edge exactly 0 above the diagonal and within 1 fp16 step of 1 / (i + 1) elsewhere."""
+    want = case["want"].to(got.device)
+    if case["pattern"] != "causal edge":
+        return got != want
+    return torch.where(want == 0, got != 0, (_fp16_ulps(got, want) > 1) | (got == 0))
+
+
+def _xa_launch(case):
+    spec = case["spec"]
+    h, d = spec["heads"], spec["d"]
+    C = h * d
+    q, k, v = case["q"], case["k"], case["v"]
+    if q.shape[0] == k.shape[0] and spec["kv_div"] == 1 and spec["q_strides"] == spec["kv_strides"]:
+        t = torch.cat([q, k, v], 1).to(DEV)          # self-attention: column windows of one fused QKV matrix
+        q, k, v = t[:, :C], t[:, C:2 * C], t[:, 2 * C:]
+    else:
+        t = torch.cat([k, v], 1).to(DEV)             # Q of its own, K / V column windows of one matrix
+        q, k, v = q.to(DEV), t[:, :C], t[:, C:]
+    o = torch.full((q.shape[0], C), float("nan"), dtype=torch.float16, device=DEV)
+    extra = {} if d == 64 and not spec["causal"] and not spec["bias"] else dict(scale=case["scale"], head_dim=d, causal=spec["causal"])
+    ops.attention(q, k, v, o, batch=spec["batch"], heads=h, Sq=spec["Sq"], Sk=spec["Sk"], inner=spec["inner"], q_strides=spec["q_strides"],
+                  kv_strides=spec["kv_strides"], kv_div=spec["kv_div"], qk_mod=spec["qk_mod"], naive=spec["naive"],
+                  bias=None if case["bias"] is None else case["bias"].to(DEV), **extra)
+    return o[case["rows"].to(DEV)]
+
+
+def check_attention_exact(kernels=XA_KERNELS):
+    """Every kernel of attention.hip on three exact patterns.  Selection: a one-hot softmax (keys = the +-1 codes of their index,
+    query i = a power-of-two gain x the code of pi(i), so every other score sits >= 160 binary orders below; on the bias kernels the
+    selection is in the bias) -- O[i] = V[pi(i)] bit for bit, every key a target.  Counting: q = 0, V[key_c, c] = Sk -- every output
+    exactly 1.0 (each key read once and counted once in the denominator).  Causal edge: q = 0, V[key_c, c] = 1 -- exactly 0 iff
+    key_c > i, else 1 / (i + 1) to 1 fp16 step.  No kernel needs a last-bit allowance on the first two: P is exactly 0 or 1 in fp16, l is
+    exactly 1 (selection; the flash kernels' l = exp2 of a rounding residual < 2^-13 leaves V x (1 / l) inside V's rounding interval)
+    or Sk (counting), and Sk x fl(1 / Sk) rounds to 1."""
+    out = []
+    for spec in exact_attention_specs():
+        if spec["kernel"] not in kernels:
+            continue
+        for pattern in exact_attention_patterns(spec):
+            case = exact_attention_case(spec, pattern)
+            got = _xa_launch(case)
+            what = "differing elements" if pattern != "causal edge" else "elements off (0 above the diagonal, 1 / (i + 1) +- 1 ulp below)"
+            out.append(_count_row(f"exact attention[{spec['kernel']}] {spec['name']}, {pattern}: {what}", exact_attention_bad(case, got)))
+    torch.cuda.synchronize()
+    return out
+
+
 EDGE_CHECKS = [check_edges_gemm_tile, check_edges_conv, check_edges_gemm_persistent, check_edges_splitk, check_edges_conv_lds_patch,
                check_edges_gemm_ws, check_edges_ff_fused, check_edges_attention, check_edges_attention_8wave, check_edges_attention_small,
                check_edges_elementwise, check_edges_layout, check_edges_softmax_timestep]
@@ -3930,7 +4403,7 @@ EDGE_CHECKS = [check_edges_gemm_tile, check_edges_conv, check_edges_gemm_persist
 ALL_KERNEL_CHECKS = [check_selftest, check_gemm, check_gemm_big, check_gemm_ws, check_gemm_ws_ln, check_gemm_splitk, check_conv, check_norms, check_attention,
                      check_attention_small_mfma, check_attention_bias_and_rotary_windows, check_gelu_all_inputs, check_silu_all_inputs,
                      check_timestep_embedding_all_timesteps, check_elementwise,
-                     check_full_size_properties, check_vae_kernels] + EDGE_CHECKS
+                     check_full_size_properties, check_vae_kernels] + EDGE_CHECKS + [check_gemm_exact, check_attention_exact]
 
 
 def check_frame_parallel(Fr=4, hw=16, tol=4e-3):

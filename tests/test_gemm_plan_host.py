@@ -218,6 +218,40 @@ ROWS = [
     ("lda_644", "mode=0 M=4096 N=320 C0=640 lda0=644 flags=2", dict(grid=5120, family="naive")),
 ]
 
+# ---- the launches of the exact-data check (tests/gpu_checks.py: check_gemm_exact; descriptors from exact_gemm_plan_rows, ldc = N rounded
+# up to 8): a retune that moves one of them must not silently take an exact row off the family it names.  The expected plan comes from
+# the family the CHECK names, worked out from the rules once per family:
+#  * flags 4 | 16 (no persistent kernel -- which also keeps the weight-stationary kernel out -- and no split-K): every operand is
+#    16-byte aligned with ld % 8 = 0 -> `fast`, 128-row kernel, unsplit, with LDS-DMA staging (flags 2) or without; bit0: the naive kernel;
+#  * bit3: big_ok (N % 320 = 0, act 0) and forced -> persistent kernel, and bit3 switches its split-K off;
+#  * bit17 + bit19 / bit20: no case splits (nk <= 9 < 32), so the ping-pong arm takes them on 192- / 256-row tiles;
+#  * bit21: N % 320 = 0, act 0, nk >= 2, never residual AND rowvec -> one-wave-per-SIMD kernel;
+#  * bit27: the same test, and tiles x nk >= 8 units (M197 N640 K192: 4 x 3; the 16x16 convs: 4 x 9) -> forced stream-K on units / 4 blocks;
+#    the launches below 8 units are skipped by name in the check and have no row here;
+#  * no bits, 48 x 8x8 256->320: tb = 16 does not fill, nk = 36 < 72 -> 128-row kernel, N = 320 -> NF 5 (320 % 128 != 0), tm = 24 x 2 = 48
+#    <= 128 with nk >= 32: sp = min(ceil(512 / 48) = 11, 8, 36 / 8) = 4; 640->1280: tb = 16 x 4 = 64 <= 128, nk = 90 >= 72:
+#    sp = min(256 / 64, 8, 90 / 12) = 4, 256 >= 224 work items, 4 x 3072 x 1280 x 4 B = 62.9 MB fits -> persistent kernel, 4 splits;
+#  * bit28: stride 1, "same", Wi = 16 / 32 / 64, N = 320, act 0, residual without rowvec -> LDS-patch kernel;
+#  * bit10: Linear, C0 = 320 with N % 160 = 0, or C0 = 512 with N = 512; no rowvec -> weight-stationary kernel below its row threshold.
+EXACT_PLANS = {
+    "naive kernel": dict(family="naive", splits=1), "128-row reg": dict(family="mfma128", splits=1), "128-row glds": dict(family="mfma128", splits=1),
+    "persistent 192x320": dict(family="big", splits=1), "ping-pong 192": dict(family="pp", pp_mf=3, splits=1),
+    "ping-pong 256": dict(family="pp", pp_mf=4, splits=1), "one-wave-per-SIMD": dict(family="sw", splits=1),
+    "stream-K": dict(family="sw_streamk", splits=1), "split-K on the 128-row kernel": dict(family="mfma128", nf=5, splits=4, tiles=48, grid=192),
+    "split-K on the persistent kernel": dict(family="big", splits=4, tilesN=4, tiles=64, grid=256), "LDS patch": dict(family="swh", splits=1),
+    "ws": dict(family="ws", splits=1),
+}
+
+
+def _exact_rows():
+    import gpu_checks as gc
+    rows = gc.exact_gemm_plan_rows()
+    assert {fam for _n, _d, fam, _c in rows} == set(EXACT_PLANS)      # every family the check names has a launch that is not skipped
+    return [(name, desc, EXACT_PLANS[fam]) for name, desc, fam, _case in rows]
+
+
+ROWS += _exact_rows()
+
 
 @pytest.fixture(scope="module")
 def plans(tmp_path_factory):
