@@ -115,6 +115,7 @@ SYMBOLS = {
     "anyv2v_copy_cols_f16": (C.c_int, [_VP, _I32, _I32, _VP, _I32, _I32, _I64, _I32, _VP]),
     "anyv2v_gather_rows_f16": (C.c_int, [_VP, _I32, _I32, _VP, _VP, _I32, _I32, _I64, _I32, _VP]),
     "anyv2v_freeu_f16": (C.c_int, [_VP, _I32, _VP, _I32, _I32, _F32, _VP, _I32, _VP, _I32, _I32, _F32, _I32, _I32, _I32, _VP]),
+    "anyv2v_tile_blend_f16": (C.c_int, [_VP, _I64, _I32, _I32, _VP, _VP, _VP, _VP, _I32, _I32, _VP, _I32, _I32, _I32, _VP]),
     "anyv2v_rotary_f16":(C.c_int, [_VP, _I32, _I64, _I32, _I32, _I32, _I32, _I32, _I32, C.c_float, _VP]),
     "anyv2v_cfg_ddim_step_f16": (C.c_int, [_VP, _I32, _I32, _I32, _F32, _VP, _VP, _VP, _I32, _I32, _I32, _VP]),
     "anyv2v_ddim_step_f16": (C.c_int, [_VP, _VP, _VP, _F32, _F32, _F32, _F32, _I64, _VP]),

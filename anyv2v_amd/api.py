@@ -89,6 +89,7 @@ class AnyV2V_I2VGenXL:
         frame_list = read_frames(str(video_path))
         cfg = self.config
         cfg.inverse_config.image_size = list(frame_list[0].size)
+        self.pipe.auto_vae_tiling(cfg.inverse_config.image_size[1], cfg.inverse_config.image_size[0])   # frames over one VAE tile
         cfg.inverse_config.n_steps = ddim_inversion_steps
         cfg.inverse_config.n_frames = len(frame_list)
         cfg.inverse_config.output_dir = ddim_latents_path

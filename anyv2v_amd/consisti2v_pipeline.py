@@ -291,6 +291,15 @@ class ConditionalVideoEditingPipeline:
         for k, v in kwargs.items():
             setattr(self, k, v)
 
+    def enable_vae_tiling(self):
+        """Frames over the VAE's ``sample_size`` in blended tiles (``AutoencoderKL.enable_tiling``); a VAE without tiling is left alone."""
+        if hasattr(self.vae, "enable_tiling"):
+            self.vae.enable_tiling()
+
+    def disable_vae_tiling(self):
+        if hasattr(self.vae, "disable_tiling"):
+            self.vae.disable_tiling()
+
     @property
     def device(self):
         return self._device

@@ -121,6 +121,21 @@ class NativeVAE:
         self.model.to(device)
         return self
 
+    def enable_tiling(self, on: bool = True):
+        """Tiled encode / decode of frames over ``cfg.sample_size`` pixels (``AutoencoderKL.enable_tiling``)."""
+        self.model.enable_tiling(on)
+
+    def disable_tiling(self):
+        self.model.disable_tiling()
+
+    @property
+    def use_tiling(self):
+        return self.model.use_tiling
+
+    @property
+    def tile_sample_size(self):
+        return self.model.cfg.sample_size
+
     def _encode(self, x, device):
         self.model.to(device)
         mean, logvar = self.model.encode_moments(x)

@@ -470,6 +470,22 @@ def freeu(hidden: torch.Tensor, skip: torch.Tensor, n_img: int, H: int, W: int, 
     return ho, so
 
 
+def tile_blend(tiles: torch.Tensor, C: int, plan, bases, n_img: int, out=None):
+    """Stitch of the tiled VAE (``anyv2v_tile_blend_f16``, include/anyv2v_hip.h): ``tiles`` is the token matrix [rows, ld] that holds
+    the raw tiles -- tile (ty, tx) of image n at row ``bases[ty][tx] + n * th * tw`` -- ``plan`` a ``vae_tiling.StitchPlan``.
+    -> fp16 [n_img, C, plan.H, plan.W]."""
+    lib = _lib.load()
+    _rowmajor(tiles, "tiles")
+    ph, wh, pd, wd = plan.tables(bases, tiles.device)
+    if out is None:
+        out = torch.empty((n_img, C, plan.H, plan.W), dtype=torch.float16, device=tiles.device)
+    assert out.is_contiguous() and out.dtype == torch.float16 and tuple(out.shape) == (n_img, C, plan.H, plan.W)
+    _lib.check(lib.anyv2v_tile_blend_f16(_p(tiles), tiles.shape[0], tiles.stride(0), C, ph.data_ptr(), wh.data_ptr(), _p(pd), _p(wd),
+                                         plan.ay.n_tiles, plan.ax.n_tiles, _p(out), n_img, plan.H, plan.W, _stream()),
+               "anyv2v_tile_blend_f16")
+    return out
+
+
 def rotary(x: torch.Tensor, col0: int, rot_dim: int, rows_per_pos: int, n_pos: int, theta: float = 10000.0, windows: int = 1,
            window_stride: int = 0):
     """In-place rotary position embedding of columns [col0 + w * window_stride, ... + rot_dim), w < windows (interleaved pairs);

@@ -208,6 +208,19 @@ class _StepEngine:
         g.replay()
 
 
+def _vae_config(root):
+    """``VAEConfig`` with the tile size (``sample_size``) of ``<root>/vae/config.json`` when the checkpoint has one, else None."""
+    path = os.path.join(root, "vae", "config.json")
+    if not os.path.isfile(path):
+        return None
+    import json
+
+    from .vae import VAEConfig
+    with open(path) as f:
+        js = json.load(f)
+    return VAEConfig(sample_size=int(js["sample_size"])) if "sample_size" in js else None
+
+
 class I2VGenXLPipeline:
     def __init__(self, vae=None, text_encoder=None, tokenizer=None, image_encoder=None, feature_extractor=None,
                  unet: Optional[I2VGenXLUNet] = None, scheduler=None):
@@ -264,7 +277,7 @@ class I2VGenXLPipeline:
             from safetensors.torch import load_file
 
             from .encoders import NativeVAE
-            pipe.vae = NativeVAE(state_dict=load_file(vpath))
+            pipe.vae = NativeVAE(state_dict=load_file(vpath), cfg=_vae_config(root))
         if os.path.isdir(os.path.join(root, "text_encoder")):
             # CLIP towers of a local checkpoint on the HIP kernels (anyv2v_amd.clip)
             from .encoders import attach_native_clip_encoders
@@ -402,11 +415,29 @@ class I2VGenXLPipeline:
         self._vae_slicing = False
 
     def enable_vae_tiling(self):
-        logger.warning("enable_vae_tiling: frames are decoded whole on this device; the output equals the reference's UNTILED decode")
+        """``pipeline_i2vgen_xl.py:208-214``: frames over the VAE's ``sample_size`` are encoded / decoded in blended tiles
+        (``AutoencoderKL.enable_tiling``).  A VAE without tiling (``SyntheticVAE``, none loaded) accepts the call and decodes whole."""
+        if hasattr(self.vae, "enable_tiling"):
+            self.vae.enable_tiling()
+        else:
+            logger.warning("enable_vae_tiling: frames are decoded whole on this device; the output equals the reference's UNTILED decode")
         self._vae_tiling = True
 
     def disable_vae_tiling(self):
+        if hasattr(self.vae, "disable_tiling"):
+            self.vae.disable_tiling()
         self._vae_tiling = False
+
+    def auto_vae_tiling(self, height, width):
+        """Turn tiling on when a ``height`` x ``width`` frame exceeds one tile of a VAE that can tile AND cannot be encoded / decoded
+        whole (the mid-block attention takes at most 8192 latent tokens): jobs that could not run now run, the others keep their
+        untiled output (a tiled result differs from the untiled one by design).  ``enable_vae_tiling`` itself has no such condition."""
+        ts = getattr(self.vae, "tile_sample_size", None)
+        if ts is None or not height or not width or self.vae.use_tiling:
+            return
+        tokens = (int(height) // self.vae_scale_factor) * (int(width) // self.vae_scale_factor)
+        if max(int(height), int(width)) > ts and tokens > 8192:
+            self.enable_vae_tiling()
 
     def enable_freeu(self, s1, s2, b1, b2):
         """``:623-648``: forwarded to the UNet (``I2VGenXLUNet.enable_freeu``: FreeU re-weights the decoder's backbone / skip features

@@ -32,6 +32,7 @@ MODEL_ID = "ali-vilab/i2vgen-xl"
 def ddim_inversion(config, first_frame, frame_list, pipe: I2VGenXLPipeline, inverse_scheduler, g, write=True):
     """``run_group_ddim_inversion.py:29-55``."""
     pipe.scheduler = inverse_scheduler
+    pipe.auto_vae_tiling(config.image_size[1], config.image_size[0])   # a frame over one VAE tile is encoded / decoded in tiles
     video_latents_at_0 = pipe.encode_vae_video(frame_list, device=pipe._execution_device, height=config.image_size[1],
                                                width=config.image_size[0])
     ddim_latents = pipe.invert(prompt=config.prompt, image=first_frame, height=config.image_size[1],
@@ -47,6 +48,7 @@ def ddim_inversion(config, first_frame, frame_list, pipe: I2VGenXLPipeline, inve
 def ddim_sampling(config, first_frame, ddim_latents_at_T, pipe: I2VGenXLPipeline, ddim_scheduler, ddim_init_latents_t_idx, g):
     """``run_group_ddim_inversion.py:58-77``."""
     pipe.scheduler = ddim_scheduler
+    pipe.auto_vae_tiling(config.image_size[1], config.image_size[0])
     return pipe(prompt=config.prompt, image=first_frame, height=config.image_size[1], width=config.image_size[0],
                 num_frames=config.n_frames, num_inference_steps=config.n_steps, guidance_scale=config.cfg,
                 negative_prompt=config.negative_prompt, target_fps=config.target_fps, latents=ddim_latents_at_T,
@@ -235,6 +237,7 @@ class Stage1:
             for p in group:
                 seed_everything(p["seed"])
                 c = p["config"].inverse_config
+                pipe.auto_vae_tiling(c.image_size[1], c.image_size[0])
                 lat0 = pipe.encode_vae_video(p["frame_list"], device=pipe._execution_device, height=c.image_size[1], width=c.image_size[0])
                 clips.append(dict(prompt=c.prompt, negative_prompt=c.negative_prompt, image=p["first_frame"], latents=lat0))
             self.logger.info(f"inverting {len(group)} clips in one batch: {[p['config'].video_name for p in group]}")

@@ -153,6 +153,7 @@ class Stage2:
 
         init_pnp(pipe, ddim_scheduler, config)
         pipe.register_modules(scheduler=ddim_scheduler)
+        pipe.auto_vae_tiling(config.image_size[1], config.image_size[0])
         edited_latents = pipe.sample_with_pnp(
             prompt=config.editing_prompt, image=edited_1st_frame, height=config.image_size[1], width=config.image_size[0],
             num_frames=config.n_frames, num_inference_steps=config.n_steps, guidance_scale=config.cfg,

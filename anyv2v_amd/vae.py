@@ -21,13 +21,15 @@ import torch.nn as nn
 from . import ops
 from .ops import ACT_F32OUT
 from .unet import Conv2d, GroupNorm, Linear
+from .vae_tiling import TilingParams
 
 PAD_CIN = 64  # 3 (RGB) / 4 (latent) input channels are zero-padded to one MFMA K-tile
 
 
 class VAEConfig:
     def __init__(self, in_channels=3, out_channels=3, latent_channels=4, block_out_channels=(128, 256, 512, 512),
-                 layers_per_block=2, norm_num_groups=32, scaling_factor=0.18215):
+                 layers_per_block=2, norm_num_groups=32, scaling_factor=0.18215, sample_size=512):
+        self.sample_size = int(sample_size)   # pixels of one tile of the tiled encode / decode (``enable_tiling``)
         self.in_channels, self.out_channels, self.latent_channels = in_channels, out_channels, latent_channels
         self.block_out_channels, self.layers_per_block = tuple(block_out_channels), layers_per_block
         self.norm_num_groups, self.scaling_factor = norm_num_groups, scaling_factor
@@ -191,6 +193,76 @@ class AutoencoderKL(nn.Module):
         self.post_quant_conv = Conv2d(self.cfg.latent_channels, self.cfg.latent_channels, 1)
         self._packed = False
         self._sc = _Scratch()
+        self.use_tiling = False
+        self.tile_frames = 4   # images per tiled encode / decode pass: bounds the raw-tile matrix and the tile batches
+        self._plans = {}
+
+    # ---- tiling (the reference's ``enable_vae_tiling``; definition: DESIGN.md "VAE tiling", host plan: vae_tiling.py) ----------------
+    def enable_tiling(self, on: bool = True):
+        """Frames larger than ``cfg.sample_size`` pixels (latents larger than the matching latent tile) are encoded / decoded in
+        overlapping tiles of at most that size and blended, as diffusers' ``AutoencoderKL.enable_tiling`` does; smaller frames keep
+        the whole-frame path, bit for bit."""
+        self.use_tiling = bool(on)
+
+    def disable_tiling(self):
+        self.enable_tiling(False)
+
+    def tiling_params(self) -> TilingParams:
+        return TilingParams(self.cfg.sample_size, len(self.cfg.block_out_channels))
+
+    def _plan(self, kind, h, w):
+        key = (kind, h, w, self.cfg.sample_size)
+        plan = self._plans.get(key)
+        if plan is None:
+            if len(self._plans) >= 8:
+                self._plans.clear()
+            tp = self.tiling_params()
+            plan = self._plans[key] = tp.decode_plan(h, w) if kind == "dec" else tp.encode_plan(h, w)
+        return plan
+
+    def _tiled(self, plan, x, C, run):
+        """Every tile of ``plan`` through ``run(x_tile, out=rows of the tile matrix)`` -- one batch per tile position, all images of the
+        pass, i.e. exactly the whole-frame call the definition makes on that crop -- then ONE stitch launch per pass."""
+        ay, ax, n = plan.ay, plan.ax, x.shape[0]
+        out = torch.empty((n, C, plan.H, plan.W), dtype=torch.float16, device=self.quant_conv.weight.device)
+        for n0 in range(0, n, self.tile_frames):
+            m = min(self.tile_frames, n - n0)
+            bases, rows = [], 0
+            for th in ay.sizes:
+                bases.append([])
+                for tw in ax.sizes:
+                    bases[-1].append(rows)
+                    rows += m * th * tw
+            raw = torch.empty((rows, 8), dtype=torch.float16, device=out.device)
+            for ty, (y0, hy) in enumerate(zip(ay.starts, ay.in_sizes)):
+                for tx, (x0, wx) in enumerate(zip(ax.starts, ax.in_sizes)):
+                    b = bases[ty][tx]
+                    run(x[n0:n0 + m, :, y0:y0 + hy, x0:x0 + wx], raw[b:b + m * ay.sizes[ty] * ax.sizes[tx]])
+            ops.tile_blend(raw, C, plan, bases, m, out=out[n0:n0 + m])
+        return out
+
+    @torch.no_grad()
+    def tiled_decode(self, z: torch.Tensor):
+        """``decode`` in tiles (see ``enable_tiling``), whatever the size of ``z``: [n,4,h,w] -> fp32 [n,3,8h,8w]."""
+        if not self._packed:
+            self.pack()
+        plan = self._plan("dec", z.shape[2], z.shape[3])
+        return self._tiled(plan, z, self.cfg.out_channels, lambda t, out: self._decode_tokens(t, out)).float()
+
+    @torch.no_grad()
+    def tiled_encode(self, x: torch.Tensor):
+        """``raw_moments`` in tiles: [n,3,H,W] -> fp32 [n,8,H/8,W/8], blended before the split into mean and log-variance."""
+        if not self._packed:
+            self.pack()
+        plan = self._plan("enc", x.shape[2], x.shape[3])
+        return self._tiled(plan, x, 2 * self.cfg.latent_channels, lambda t, out: self._encode_tokens(t, out)).float()
+
+    def _tiles_decode(self, z):
+        tp = self.tiling_params()
+        return self.use_tiling and (z.shape[2] > tp.T_l or z.shape[3] > tp.T_l)
+
+    def _tiles_encode(self, x):
+        return self.use_tiling and (x.shape[2] > self.cfg.sample_size or x.shape[3] > self.cfg.sample_size)
 
     def load_state_dict(self, sd, strict=True, **kw):
         r = super().load_state_dict({k: v.to(torch.float16) for k, v in sd.items()}, strict=strict, **kw)
@@ -212,8 +284,23 @@ class AutoencoderKL(nn.Module):
     @torch.no_grad()
     def encode_moments(self, x: torch.Tensor):
         """[n,3,H,W] in [-1,1] (any float dtype, on the module's device) -> (mean, logvar) fp32 [n,4,H/8,W/8]."""
+        m = self.raw_moments(x)
+        L = self.cfg.latent_channels
+        return m[:, :L].contiguous(), m[:, L:].clamp(-30.0, 20.0).contiguous()
+
+    @torch.no_grad()
+    def raw_moments(self, x: torch.Tensor):
+        """``quant_conv(encoder(x))``: fp32 [n,8,H/8,W/8], mean and unclamped log-variance stacked (a view of the token matrix)."""
         if not self._packed:
             self.pack()
+        if self._tiles_encode(x):
+            return self.tiled_encode(x)
+        n = x.shape[0]
+        m, H, W = self._encode_tokens(x)
+        return m.float().view(n, H, W, 2 * self.cfg.latent_channels).permute(0, 3, 1, 2)
+
+    def _encode_tokens(self, x, out=None):
+        """-> (moment tokens [n h w, 8] fp16, h, w); ``out``: rows to write them to."""
         n, c, H, W = x.shape
         dev = self.quant_conv.weight.device
         tok = torch.zeros((n * H * W, PAD_CIN), dtype=torch.float16, device=dev)
@@ -227,16 +314,22 @@ class AutoencoderKL(nn.Module):
         h = ops.groupnorm(h, g.weight, g.bias, sc.get(h.shape[0], H * W, dev, g.num_groups), H * W, groups=g.num_groups,
                           eps=g.eps, silu=True)
         m = enc.conv_out.tokens(h, H, W)                      # [n h w, 8]
-        m = self.quant_conv.tokens(m, H, W)                   # 1x1 conv
-        L = self.cfg.latent_channels
-        m = m.float().view(n, H, W, 2 * L).permute(0, 3, 1, 2)
-        return m[:, :L].contiguous(), m[:, L:].clamp(-30.0, 20.0).contiguous()
+        return self.quant_conv.tokens(m, H, W, out=out), H, W   # 1x1 conv
 
     @torch.no_grad()
     def decode(self, z: torch.Tensor):
         """[n,4,h,w] (already divided by scaling_factor) -> fp32 [n,3,8h,8w]."""
         if not self._packed:
             self.pack()
+        if self._tiles_decode(z):
+            return self.tiled_decode(z)
+        n = z.shape[0]
+        out, H, W = self._decode_tokens(z)
+        img = ops.tokens_to_ncfhw(out, 1, self.cfg.out_channels, n, H, W)  # [1,3,n,H,W]
+        return img[0].permute(1, 0, 2, 3).float().contiguous()
+
+    def _decode_tokens(self, z, out=None):
+        """-> (image tokens [n H W, 8] fp16 (``out_channels`` columns used), H, W); ``out``: rows to write them to."""
         n, L, H, W = z.shape
         dev = self.quant_conv.weight.device
         z16 = torch.zeros((n * H * W, 8), dtype=torch.float16, device=dev)
@@ -252,10 +345,10 @@ class AutoencoderKL(nn.Module):
         g = dec.conv_norm_out
         h = ops.groupnorm(h, g.weight, g.bias, sc.get(h.shape[0], H * W, dev, g.num_groups), H * W, groups=g.num_groups,
                           eps=g.eps, silu=True)
-        out = torch.empty((n * H * W, 8), dtype=torch.float16, device=dev)
+        if out is None:
+            out = torch.empty((n * H * W, 8), dtype=torch.float16, device=dev)
         dec.conv_out.tokens(h, H, W, out=out)
-        img = ops.tokens_to_ncfhw(out, 1, self.cfg.out_channels, n, H, W)  # [1,3,n,H,W]
-        return img[0].permute(1, 0, 2, 3).float().contiguous()
+        return out, H, W
 
 
 def init_random_weights_(vae: AutoencoderKL, seed: int = 0):

@@ -298,6 +298,23 @@ int anyv2v_freeu_f16(const void* hidden, int32_t ld_hidden, void* hidden_out, in
                      const void* skip, int32_t ld_skip, void* skip_out, int32_t ld_skip_out, int32_t C_skip, float s,
                      int32_t n_img, int32_t H, int32_t W, void* stream);
 
+/* Stitch of the tiled AutoencoderKL encode / decode (diffusers-0.26.3 tiled_encode / tiled_decode / blend_v / blend_h behind the reference's
+ * enable_vae_tiling, pipeline_i2vgen_xl.py:208-221): gathers the planar image out[n_img, C, H, W] (fp16) from the RAW tiles, channels-last
+ * token matrices inside `tiles` [tile_rows, ld] (C <= 8 channels used, ld % 8 == 0, 16-byte aligned).  The definition blends in place in
+ * row-major tile order (with the tile above, then with the tile on the left, each already blended) and keeps tile[:limit, :limit]; unrolled:
+ *   out[n, c, y, x] = wy wx R[py, px] + wy (1 - wx) L[py, qx] + (1 - wy) wx^2 U[qy, px] + (1 - wy)(1 - wx^2) UL[qy, qx]
+ * R / L / U / UL = raw tiles (ky, kx), (ky, kx - 1), (ky - 1, kx), (ky - 1, kx - 1) of image n, (ky, py, qy) = row table [y], wy = row
+ * weight [y] (p / e' inside a blend band, 1 outside, where the q entry and the tiles it selects are not read), columns likewise.
+ * Four products and their sum in fp64, ONE rounding to fp16 (exact, hence bit-equal to the sequential definition, when e' is a power
+ * of two); a pixel outside every band is copied.  Every output element is written exactly once.
+ *   plan  int32: [nty * ntx][4] tile records {first row of image 0 in `tiles`, height, width, 0} (image n of a tile follows image n - 1),
+ *                then [H][3] rows {k, p, q}, then [W][3] columns {k, p, q};      weight  fp64: [H] wy, then [W] wx.
+ * Both tables are passed twice: the host copy, which the entry point checks against tile_rows and the tile extents before it launches
+ * (ANYV2V_EINVAL), and the device copy of the SAME values, which the kernel reads. */
+int anyv2v_tile_blend_f16(const void* tiles, int64_t tile_rows, int32_t ld, int32_t C, const int32_t* plan_host,
+                          const double* weight_host, const int32_t* plan_dev, const double* weight_dev, int32_t nty, int32_t ntx,
+                          void* out, int32_t n_img, int32_t H, int32_t W, void* stream);
+
 /* Row softmax of fp32 logits (from anyv2v_gemm_f16 with act = 4) into fp16 probabilities:
  * P[r, c] = softmax_c(scale * S[r, c]), cols <= 8192.  AutoencoderKL mid-block attention (single head of width 512,
  * encode_vae_video / decode_latents, pipeline_i2vgen_xl.py:565-592,598-620). */
@@ -357,7 +374,8 @@ const char* anyv2v_last_error(void);
  * _apply_pivot_f16 (the earlier pair is unchanged).  105: AnyV2VGemmDesc grew gn_stats / gn_stats_floats / gn_rows_per_group /
  * gn_groups (GroupNorm statistics from the GEMM epilogue), anyv2v_gemm_gn_stats_floats, anyv2v_gemm_gn_launches,
  * anyv2v_groupnorm_stats_floats, anyv2v_groupnorm_apply_stats_f16; nothing earlier changed (a 104 caller that zero-initialises its descriptors, as required,
- * must still be recompiled against this header because the structure grew). */
+ * must still be recompiled against this header because the structure grew).  anyv2v_freeu_f16 and anyv2v_tile_blend_f16 were added under 105: new entry points, no structure changed
+ * (a binding that needs them finds out when it resolves the symbol). */
 #define ANYV2V_ABI_VERSION 105
 int anyv2v_version(void);
 /* MFMA / LDS layout self-test used by the gpu test-suite (returns 0 when the layouts the kernels assume hold) */
