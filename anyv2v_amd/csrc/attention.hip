@@ -691,6 +691,7 @@ static int fill(const AnyV2VAttnDesc* d, AttnK& k, int head_dim) {
     AV_CHECK(d->Q && d->K && d->V && d->O, "attention: null pointer");
     AV_CHECK(d->batch > 0 && d->heads > 0 && d->Sq > 0 && d->Sk > 0, "attention: bad sizes");
     AV_CHECK(d->inner > 0 && d->kv_div > 0 && d->qk_mod >= 0, "attention: bad inner/kv_div/qk_mod");
+    AV_CHECK(d->ldq > 0 && d->ldk > 0 && d->ldv > 0 && d->ldo > 0, "attention: leading dimensions must be positive");
     k.Q = (const half_t*)d->Q;
     k.K = (const half_t*)d->K;
     k.V = (const half_t*)d->V;
@@ -720,6 +721,8 @@ static inline bool av_attn_pnp3(const AttnK& k, const AnyV2VAttnDesc* d) {
     return k.qk_mod > 0 && k.batch == 3 * k.qk_mod && k.kv_div == 1 && !(d->flags & 8);
 }
 
+static int launch_loop_d64(const AttnK& k, hipStream_t s);   // behind loop_attn_mfma_kernel, below
+
 extern "C" int anyv2v_attention_f16(const AnyV2VAttnDesc* d, void* stream) {
     AttnK k;
     int rc = fill(d, k, 64);
@@ -738,6 +741,19 @@ extern "C" int anyv2v_attention_f16(const AnyV2VAttnDesc* d, void* stream) {
         const long long units = (long long)k.batch * k.heads;
         hipLaunchKernelGGL(short_attn_d64_kernel<1>, dim3((unsigned)((units + 3) / 4)), dim3(256), 0, s, k);
         return av_launch_status("short_attn_d64");
+    }
+    // The flash kernels keep the per-lane K / V source offsets of one 64-key tile in 32 bits (koff / voff_g: byte offsets of key rows
+    // 0 .. 63 from the tile pointer, 16-byte chunk included).  A layout whose largest in-tile byte offset does not fit -- or a negative
+    // sequence stride, which those unsigned offsets cannot hold -- runs on kernels that address every row in 64 bits: the 96-key loop
+    // kernel (same addressing contract: strides, kv_div, qk_mod as per-branch aliasing), or the generic kernel when the grid does not
+    // fit the loop kernel's.  Every shape the models issue stays far below the limit (4096 x 960 elements per key step against 34.1 M).
+    {
+        const long long ldkv = d->ldk > d->ldv ? d->ldk : d->ldv;
+        const bool wide = d->kv_seq < 0 || d->kv_seq > ((long long)0xFFFFFFFFll / 2 - 64) / 63 / ldkv;   // (63 kv_seq ld + 64) * 2 > 2^32 - 1
+        if (wide) {
+            if (k.heads <= 65535 && k.batch <= 65535) return launch_loop_d64(k, s);
+            return launch_naive(k, s);
+        }
     }
     const long long nwg = (long long)k.batch * k.heads * k.q_tiles;
     AV_CHECK(nwg < (1ll << 31), "attention: grid too large");
@@ -903,6 +919,14 @@ __global__ __launch_bounds__(256) void loop_attn_mfma_kernel(const AttnK p) {
             }
         }
     }
+}
+
+// head_dim 64 on the loop kernel: where anyv2v_attention_f16 sends layouts whose K / V tile offsets do not fit the flash kernels' 32 bits
+static int launch_loop_d64(const AttnK& k, hipStream_t s) {
+    const dim3 grid((unsigned)((k.Sq + 63) / 64), (unsigned)k.heads, (unsigned)k.batch);
+    const size_t lds = (size_t)96 * (2 * 32 + 8) * 2 + (size_t)(2 * 32) * (96 + 4) * 2;   // 26 KiB: below the default dynamic-LDS limit
+    hipLaunchKernelGGL((loop_attn_mfma_kernel<2>), grid, dim3(256), lds, s, k);
+    return av_launch_status("loop_attn_mfma<wide K/V strides>");
 }
 
 extern "C" int anyv2v_attention_small_f16(const AnyV2VAttnDesc* d, int32_t head_dim, void* stream) {

@@ -330,6 +330,7 @@ extern "C" int anyv2v_cfg_ddim_step_f16(const void* Vtok, int32_t ldv, int32_t b
                                         int32_t HW, void* stream) {
     AV_CHECK(Vtok && coef && lat && out && C > 0 && F > 0 && HW > 0 && ldv >= C && b_cond >= 0,
              "cfg_ddim_step: bad arguments");
+    AV_CHECK((long long)F * HW < (1ll << 31), "cfg_ddim_step: F * HW must fit an int (the kernel's pixel index)");
     hipLaunchKernelGGL(cfg_ddim_step_kernel, dim3(nblk((long long)F * HW, 256, 1 << 30)), dim3(256), 0,
                        (hipStream_t)stream, (const half_t*)Vtok, ldv, b_unc, b_cond, guidance, coef, (const half_t*)lat,
                        (half_t*)out, C, F, HW);

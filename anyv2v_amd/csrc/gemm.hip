@@ -37,6 +37,9 @@ extern "C" int anyv2v_gemm_f16(const AnyV2VGemmDesc* d, void* stream) {
              "gemm: gn_stats set, but this launch runs on %s, which writes no GroupNorm statistics (ask anyv2v_gemm_gn_stats_floats first)",
              plan.gn_decline);
     if (plan.status != ANYV2V_OK) return plan.status;
+    // the kernels hold SOURCE row numbers in int (RowInfo / src_row): a stride-2 convolution reads up to four times M rows
+    AV_CHECK(d->mode != MODE_CONV2D || (long long)(d->M / (d->Ho * d->Wo)) * d->Hi * d->Wi < (1ll << 31),
+             "gemm: the convolution's source has 2^31 rows or more");
     GemmK k = {};   // (trace, gn_* and what the plan leaves 0 stay off)
     k.A0 = (const half_t*)d->A0;
     k.A1 = d->C1 > 0 ? (const half_t*)d->A1 : (const half_t*)d->A0;

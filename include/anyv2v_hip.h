@@ -218,6 +218,13 @@ int anyv2v_layernorm_f16(const void* X, void* Y, const void* gamma, const void* 
  * K/V use batch index i / kv_div (cross-attention: all F frames of a clip share one K/V).
  * PnP injection (pnp_utils.py:189-196, :295-302): qk_mod > 0 makes Q and K of batch element i come
  * from element i % qk_mod (the source branch) -- aliasing instead of the reference's copies.
+ * Strides are 64-bit and every kernel forms row addresses in 64 bits, with one limit: the flash kernels (Sq or Sk > 16) hold the
+ * byte offsets of the 64 key rows of a K / V tile in 32 bits, so they run only while
+ *     (63 * kv_seq * max(ldk, ldv) + 64) * 2 < 2^32      (kv_seq * ld below about 34.1 M elements; kv_seq >= 0).
+ * A launch beyond that limit is not an error: it runs on the 96-key loop kernel of anyv2v_attention_small_f16 (64-bit addressing
+ * throughout, same strides / kv_div / qk_mod; several times slower), or on the one-thread-per-query kernel when batch or heads
+ * exceed 65535.  Same result within the kernels' rounding, not bit for bit; flags bit2, bit3 and bit7 select among the flash
+ * kernels' forms only and mean nothing there.  Leading dimensions must be positive (ANYV2V_EINVAL otherwise).
  */
 typedef struct AnyV2VAttnDesc {
     const void* Q;

@@ -4494,3 +4494,722 @@ def check_frame_parallel(Fr=4, hw=16, tol=4e-3):
     out.append({"name": f"frame-parallel rank {fp.rank}: all-to-all payload > 0", "err": 0.0 if fp.bytes_moved > 0 else 1.0,
                 "tol": 0.5, "ok": fp.bytes_moved > 0})
     return out
+
+
+# ------------------------------------------------------------------------------------------------ far operands: offsets past 2^32 bytes
+# A small logical operand inside one large allocation, its rows so far apart that the last row starts 2^32 bytes or more behind the
+# pointer the kernel gets, and that pointer FAR_LEAD bytes into the allocation.  An offset a kernel truncates to 32 bits -- signed or
+# unsigned, counted in elements or in bytes -- then lies between the pointer - 4 GiB and the true offset, i.e. inside the allocation:
+# a truncating kernel reads or writes a wrong row (a failing row of the check), it does not fault.  With power-of-two strides every
+# such image falls on the start of another row of the operand or, for the negative ones, in front of it; the helper writes those
+# places ("decoys") with other random data, so a wrong read is wrong deterministically and a wrong store is seen.  The geometry is
+# plain integers (numpy): tests/test_far_operands_host.py checks every case on the CPU.  Memory is ``torch.empty`` and never filled;
+# only the operand's rows and the decoys are written.
+FAR_LEAD = 4 << 30
+FAR_CAP = 10 << 30
+FAR_MIN_FREE = 12 << 30
+FAR_KINDS = ("unsigned elements", "signed elements", "unsigned bytes", "signed bytes")
+
+
+def far_geometry(name, offsets, cols, item=2, **extra):
+    """``offsets``: element offsets of the operand's row starts from the pointer handed to the kernel, in logical row order."""
+    import numpy as np
+    offs = np.asarray(offsets, dtype=np.int64).reshape(-1)
+    return dict(name=name, offsets=offs, cols=int(cols), item=int(item), lead=FAR_LEAD, **extra)
+
+
+def far_images(geo):
+    """The four 32-bit images of every row offset, as element offsets: {kind: int64 array}."""
+    o, it = geo["offsets"], geo["item"]
+    u = lambda v: v & 0xFFFFFFFF
+    s = lambda v: ((v + (1 << 31)) & 0xFFFFFFFF) - (1 << 31)
+    return {"unsigned elements": u(o), "signed elements": s(o), "unsigned bytes": u(o * it) // it, "signed bytes": s(o * it) // it}
+
+
+def far_decoys(geo):
+    """Images that are not themselves a row start (sorted, unique)."""
+    import numpy as np
+    return np.setdiff1d(np.unique(np.concatenate(list(far_images(geo).values()))), geo["offsets"])
+
+
+def far_span_bytes(geo):
+    return geo["lead"] + (int(geo["offsets"].max()) + geo["cols"]) * geo["item"]
+
+
+def far_ld(rows, item=2):
+    """The power-of-two row stride (elements) that puts row ``rows - 1`` at or past 2^32 bytes."""
+    ld = 1
+    while (rows - 1) * ld * item < (1 << 32):
+        ld *= 2
+    return ld
+
+
+def far_matrix_geometry(name, M, cols, item=2):
+    ld = far_ld(M, item)
+    assert ld < (1 << 31) and cols <= ld
+    import numpy as np
+    return far_geometry(name, np.arange(M, dtype=np.int64) * ld, cols, item, ld=ld, rows=M)
+
+
+def far_skip_reason():
+    free = torch.cuda.mem_get_info()[0]
+    return None if free >= FAR_MIN_FREE else f"{free / 2 ** 30:.1f} GiB of device memory free, the far cases need 12"
+
+
+FAR_PEAK = {}   # case name -> peak bytes allocated (torch) while it ran
+
+
+class _FarBuffer:
+    """The allocation behind one far operand."""
+
+    def __init__(self, geo, dtype, seed=0):
+        item = torch.empty(0, dtype=dtype).element_size()
+        assert item == geo["item"] and far_span_bytes(geo) <= FAR_CAP
+        self.geo, self.cols = geo, geo["cols"]
+        self.flat = torch.empty((far_span_bytes(geo) // item + 7) // 8 * 8, dtype=dtype, device=DEV)
+        self.base = geo["lead"] // item
+        ar = torch.arange(self.cols, device=DEV)
+        self.ix = ((torch.from_numpy(geo["offsets"]).to(DEV) + self.base)[:, None] + ar[None]).reshape(-1)
+        dec = far_decoys(geo)
+        self.dix = ((torch.from_numpy(dec).to(DEV) + self.base)[:, None] + ar[None]).reshape(-1)
+        g = torch.Generator().manual_seed(977 + seed)
+        self.dvals = (torch.randn(len(dec) * self.cols, generator=g) * 3.0 + 40.0).to(dtype).to(DEV)   # no operand holds such values
+        if len(dec):
+            self.flat[self.dix] = self.dvals
+
+    def write(self, t):
+        assert t.numel() == self.ix.numel()
+        self.flat[self.ix] = t.reshape(-1).to(self.flat.dtype)
+        # the indexed store above, checked through plain slices (whose offsets the host computes) on the first and the last row
+        for r in (0, len(self.geo["offsets"]) - 1):
+            o = self.base + int(self.geo["offsets"][r])
+            bits = torch.int16 if self.flat.element_size() == 2 else torch.int32
+            assert torch.equal(self.flat[o:o + self.cols].view(bits), t.reshape(-1, self.cols)[r].to(self.flat.dtype).contiguous().view(bits))
+
+    def read(self):
+        return self.flat[self.ix].view(-1, self.cols)
+
+    def decoys_intact(self):
+        return bool(torch.equal(self.flat[self.dix], self.dvals)) if self.dix.numel() else True
+
+    def view(self, shape, strides):
+        return torch.as_strided(self.flat, shape, strides, self.base)
+
+
+def _poison(shape, dtype):
+    if dtype == torch.float32:
+        return torch.full(shape, POISON32, dtype=torch.int32, device=DEV).view(torch.float32)
+    return torch.full(shape, POISON16, dtype=torch.int16, device=DEV).view(torch.float16)
+
+
+class _FarOperands:
+    """Hands a launch its matrices: plain tensors, except the one called ``which``, which lies in a ``_FarBuffer`` with
+    ``far_matrix_geometry`` (a power-of-two leading dimension).  ``out`` matrices start as the poison pattern."""
+
+    def __init__(self, which=None):
+        self.which, self.buf, self.is_out = which, None, False
+
+    def mat(self, name, t, out=False, inplace=False):
+        if t is None:
+            return None
+        shape, dtype = tuple(t.shape), t.dtype
+        init = _poison(shape, dtype) if out and not inplace else t
+        if name != self.which:
+            return init.clone() if out else t
+        geo = far_matrix_geometry(name, shape[0], shape[1], t.element_size())
+        self.buf, self.is_out = _FarBuffer(geo, dtype, seed=shape[0]), out
+        self.buf.write(init)
+        return self.buf.view(shape, (geo["ld"], 1))
+
+    def result(self, y):
+        return self.buf.read() if (self.buf is not None and self.is_out) else y
+
+    def intact(self):
+        return self.buf is None or self.buf.decoys_intact()
+
+    def release(self):
+        self.buf = None
+
+
+def _same_row(name, a, b, also=True):
+    same = bool(torch.equal(a.view(torch.int16 if a.element_size() == 2 else torch.int32), b.view(torch.int16 if b.element_size() == 2 else torch.int32)))
+    bad = 0.0 if same else float((a != b).sum())
+    return dict(name=name, err=bad if also else max(bad, 1.0), tol=0.0, ok=same and also)
+
+
+def _far_case_rows(name, run, fars, ref, tol=KTOL, other_family=()):
+    """The rows of one kernel case: the plain ("near") launch against ``ref`` at ``tol``, then one launch per operand in ``fars`` with
+    that operand far: far result == near result bit for bit and the decoys of the far operand untouched.  For an operand in
+    ``other_family`` the far layout legitimately runs another kernel: that row compares with ``ref`` at ``tol`` instead."""
+    why = far_skip_reason()
+    if why is not None:
+        return [_skip_row(f"{name}: near and {len(fars)} far launches", why)]
+    f0 = _FarOperands(None)
+    y_near = f0.result(run(f0))
+    torch.cuda.synchronize()
+    want = ref(y_near) if callable(ref) else ref
+    rows = [_res(f"{name}: near vs reference", y_near, want, tol)]
+    for which in fars:
+        torch.cuda.reset_peak_memory_stats()
+        f = _FarOperands(which)
+        y = f.result(run(f))
+        torch.cuda.synchronize()
+        assert f.buf is not None, f"{name}: no operand called {which}"
+        if which in other_family:
+            r = _res(f"{name}: {which} far (another kernel: 64-bit fallback) vs reference", y, want, tol)
+            r["ok"] = r["ok"] and f.intact()
+            rows.append(r)
+        else:
+            rows.append(_same_row(f"{name}: {which} far == near, bit for bit, decoys untouched", y.contiguous(), y_near.contiguous(), f.intact()))
+        FAR_PEAK[f"{name}: {which} far"] = torch.cuda.max_memory_allocated()
+        f.release()
+        del f, y
+        torch.cuda.empty_cache()
+    return rows
+
+
+def far_skipped(rows):
+    n = sum(1 for r in rows if r.get("skipped"))
+    print(f"far operands: {n} of {len(rows)} rows skipped")
+    return n
+
+
+# ---- GEMM families
+# (family, GEMM_FLAGS bits, LDS-DMA staging, naive, case).  Row counts M with (M - 1) between 2^k and 1.5 x 2^k, so that the far
+# matrix stays inside FAR_CAP with a power-of-two leading dimension.
+FAR_GEMM_FAMILIES = (("128-row reg", 4 | 16, False, False), ("128-row glds", 4 | 16, True, False), ("naive", 4 | 16, True, True),
+                     ("persistent 192x320", 8, True, False), ("ping-pong 192", (1 << 17) | (1 << 19), True, False),
+                     ("ping-pong 256", (1 << 17) | (1 << 20), True, False), ("one-wave-per-SIMD", 1 << 21, True, False),
+                     ("stream-K", 1 << 27, True, False), ("LDS patch", 1 << 28, True, False), ("weight-stationary", 1024, True, False),
+                     ("weight-stationary + LayerNorm", 1024, True, False), ("split-K", 0, True, False))
+
+
+def far_gemm_specs(family):
+    """[(case name, descriptor words for the planner, operands made far in turn)] of one family; ``check_far_gemm`` builds the data."""
+    if family in ("128-row reg", "128-row glds", "naive"):
+        return [("M130 N136 K128 +bias+rowvec/50+res", dict(mode=0, M=130, N=136, C0=128, rowvec_div=50, R=1, bias=1), ("A0", "C", "R", "rowvec")),
+                ("two-source M130 N320 K128+64", dict(mode=0, M=130, N=320, C0=128, C1=64), ("A1",)),
+                ("conv3x3 3 x 12x10 64->128 +bias+temb+res", dict(mode=1, M=360, N=128, C0=64, Hi=12, Wi=10, Ho=12, Wo=10, stride=1, rowvec_div=120, R=1, bias=1), ("A0",)),
+                ("temporal B2 F5 HW17 64->64 +bias+res", dict(mode=2, M=170, N=64, C0=64, F=5, HW=17, R=1, bias=1), ("A0",))]
+    if family in ("persistent 192x320", "ping-pong 192", "ping-pong 256", "one-wave-per-SIMD", "stream-K"):
+        return [("M261 N640 K192 +bias+res", dict(mode=0, M=261, N=640, C0=192, R=1, bias=1), ("A0", "C", "R")),
+                ("two-source M261 N640 K128+64 +bias+rowvec/100", dict(mode=0, M=261, N=640, C0=128, C1=64, rowvec_div=100, bias=1), ("A1", "rowvec"))]
+    if family == "LDS patch":
+        return [("conv3x3 5 x 16x16 64->320 +bias+res", dict(mode=1, M=1280, N=320, C0=64, Hi=16, Wi=16, Ho=16, Wo=16, stride=1, R=1, bias=1), ("A0", "C", "R")),
+                ("conv3x3 5 x 16x16 64+64->320 +bias+temb", dict(mode=1, M=1280, N=320, C0=64, C1=64, Hi=16, Wi=16, Ho=16, Wo=16, stride=1, rowvec_div=512, bias=1),
+                 ("A1", "rowvec"))]
+    if family == "weight-stationary":
+        return [("M130 N320 K320 +bias+res", dict(mode=0, M=130, N=320, C0=320, R=1, bias=1), ("A0", "C", "R"))]
+    if family == "weight-stationary + LayerNorm":
+        return [("M130 N160 K320 LayerNorm fold", dict(mode=0, M=130, N=160, C0=320, bias=1, ln=1), ("A0", "C"))]
+    if family == "split-K":
+        return [("conv3x3 40 x 8x8 256->320 +bias+temb+res M2560", dict(mode=1, M=2560, N=320, C0=256, Hi=8, Wi=8, Ho=8, Wo=8, stride=1, rowvec_div=1024, R=1, bias=1),
+                 ("A0", "C", "R", "rowvec")),
+                ("conv3x3 40 x 8x8 128+128->320 +bias+temb+res M2560", dict(mode=1, M=2560, N=320, C0=128, C1=128, Hi=8, Wi=8, Ho=8, Wo=8, stride=1, rowvec_div=1024,
+                                                                            R=1, bias=1), ("A1",))]
+    raise KeyError(family)
+
+
+def far_gemm_operand_rows(words, which):
+    """(rows, cols) of operand ``which`` of the launch ``words`` describes (A of a convolution has the INPUT rows: stride 1 here)."""
+    M, N = words["M"], words["N"]
+    return {"A0": (M, words["C0"]), "A1": (M, words.get("C1", 0)), "C": (M, N), "R": (M, N),
+            "rowvec": ((M + words.get("rowvec_div", 1) - 1) // words.get("rowvec_div", 1), N)}[which]
+
+
+def far_gemm_plan_rows():
+    """(row name, descriptor line for tests/gemm_plan_main.cpp) of every near and far GEMM launch, in pairs: the planner must give
+    both the same family (tests/test_far_operands_host.py)."""
+    rows = []
+    field = {"A0": "lda0", "A1": "lda1", "C": "ldc", "R": "ldr", "rowvec": "ldrv"}
+    for fam, bits, glds, naive in FAR_GEMM_FAMILIES:
+        for cname, words, fars in far_gemm_specs(fam):
+            flags = (1 if naive else 0) | (2 if glds else 0) | bits
+            base = " ".join(f"{k}={v}" for k, v in words.items() if k not in ("rowvec_div",)) + f" flags={flags}"
+            if "rowvec_div" in words:
+                base += f" rowvec=1 rowvec_div={words['rowvec_div']}"
+            rows.append((f"{fam} | {cname} | near", base))
+            for which in fars:
+                r, _c = far_gemm_operand_rows(words, which)
+                rows.append((f"{fam} | {cname} | {which} far", base + f" {field[which]}={far_ld(r)}"))
+    return rows
+
+
+def _far_gemm_data(words):
+    M, N, C0, C1, mode = words["M"], words["N"], words["C0"], words.get("C1", 0), words["mode"]
+    taps = {0: 1, 1: 9, 2: 3}[mode]
+    K = taps * (C0 + C1)
+    a0, a1 = rnd(M, C0, seed=M + 1), (rnd(M, C1, seed=M + 2) if C1 else None)
+    w = rnd(N, K, scale=1 / math.sqrt(K), seed=N + 3)
+    bias = rnd(N, seed=N + 4) if words.get("bias") else None
+    div = words.get("rowvec_div", 0)
+    rv = rnd((M + div - 1) // div, N, seed=N + 5) if div else None
+    res = rnd(M, N, seed=M + 6) if words.get("R") else None
+    kw = {}
+    A = (a0 if a1 is None else torch.cat([a0, a1], 1)).double()
+    if mode == 0:
+        acc = A @ w.double().t()
+    elif mode == 1:
+        H, W_ = words["Hi"], words["Wi"]
+        n = M // (H * W_)
+        x = A.view(n, H, W_, C0 + C1).permute(0, 3, 1, 2)
+        wk = w.double().view(N, 9, C0 + C1).permute(0, 2, 1).reshape(N, C0 + C1, 3, 3)
+        acc = F.conv2d(x, wk, padding=1).permute(0, 2, 3, 1).reshape(M, N)
+        kw = dict(mode=ops.MODE_CONV2D, conv=(H, W_, H, W_, 1, 0))
+    else:
+        Fr, HW = words["F"], words["HW"]
+        B = M // (Fr * HW)
+        x = A.view(B, Fr, HW, C0).permute(0, 2, 3, 1).reshape(B * HW, C0, Fr)
+        wk = w.double().view(N, 3, C0).permute(0, 2, 1)
+        acc = F.conv1d(x, wk, padding=1).view(B, HW, N, Fr).permute(0, 3, 1, 2).reshape(M, N)
+        kw = dict(mode=ops.MODE_TEMPORAL, temporal=(Fr, HW))
+    ln = None
+    if words.get("ln"):
+        gamma, beta = (1.0 + 0.3 * rnd(C0, seed=32).float()).half(), (0.2 * rnd(C0, seed=33).float()).half()
+        a0 = (a0.float() * 1.5 + 2.0).half()
+        acc = F.layer_norm(a0.double(), (C0,), gamma.double(), beta.double(), 1e-5) @ w.double().t()
+        w, bias_f, c1 = ops.ln_fold(w, bias, gamma, beta)
+        acc = acc + bias.double()
+        bias, ln = bias_f, (c1, 1e-5)
+    elif bias is not None:
+        acc = acc + bias.double()
+    if rv is not None:
+        acc = acc + rv.double().repeat_interleave(div, 0)[:M]
+    if res is not None:
+        acc = acc + res.double()
+    return dict(a0=a0, a1=a1, w=w, bias=bias, rv=rv, div=div, res=res, ln=ln, kw=kw, ref=acc)
+
+
+def check_far_gemm(family):
+    """One GEMM family with A0 / A1 / C / R / rowvec far in turn (``far_gemm_specs``); the stream-K and split-K workspace NaN-filled."""
+    fam, bits, glds, naive = next(f for f in FAR_GEMM_FAMILIES if f[0] == family)
+    out = []
+    saved, saved_glds = ops.GEMM_FLAGS, ops.USE_GLDS
+    try:
+        ops.USE_GLDS = glds
+        ops.GEMM_FLAGS = ((saved & ~4) | bits) if not bits & 4 else (saved | bits)
+        for cname, words, fars in far_gemm_specs(fam):
+            d = _far_gemm_data(words)
+            M, N = words["M"], words["N"]
+
+            def run(f, d=d, M=M, N=N):
+                if fam in ("stream-K", "split-K"):
+                    ops._workspace(DEV).fill_(float("nan"))
+                return ops.gemm(f.mat("A0", d["a0"]), d["w"], a1=f.mat("A1", d["a1"]), bias=d["bias"], rowvec=f.mat("rowvec", d["rv"]),
+                                rowvec_div=d["div"], residual=f.mat("R", d["res"]), out=f.mat("C", torch.empty(M, N, dtype=torch.float16, device=DEV), out=True),
+                                naive=naive, ln=d["ln"], **d["kw"])
+            out += _far_case_rows(f"far gemm[{fam}] {cname}", run, fars, d["ref"])
+    finally:
+        ops.GEMM_FLAGS, ops.USE_GLDS = saved, saved_glds
+    return out
+
+
+def check_far_ff_fused():
+    """``ff_geglu`` with X, R and Y far (M = 161: one strip and a ragged tail)."""
+    C, H, M = 320, 1280, 161
+    w1, b1 = rnd(2 * H, C, scale=1 / math.sqrt(C)), rnd(2 * H, scale=0.1)
+    w2, b2 = rnd(C, H, scale=1 / math.sqrt(H)), rnd(C, scale=0.1)
+    w1p, b1p = _geglu_pack(w1, b1, H)
+    w2s = ops.ff_pack_w2(w2)
+    x, r = rnd(M, C, seed=M), rnd(M, C, seed=M + 1)
+    proj = x.double() @ w1.double().t() + b1.double()
+    hid = (proj[:, :H] * F.gelu(proj[:, H:])).half().double()
+    ref = (hid @ w2.double().t() + b2.double()).half().double() + r.double()
+
+    def run(f):
+        return ops.ff_geglu(f.mat("X", x), w1p, b1p, w2s, b2, residual=f.mat("R", r), out=f.mat("Y", torch.empty(M, C, dtype=torch.float16, device=DEV), out=True))
+    return _far_case_rows(f"far ff_fused M{M} +res", run, ("X", "R", "Y"), ref)
+
+
+# ---- attention
+FAR_ATTN_SEQ_ROWS = 512      # far through a sequence stride: batch element i, position s at row i + 512 s
+FAR_ATTN_OUTER_ROWS = 4096   # far through the outer (batch) stride: row 4096 i + s
+
+
+FLASH_LIMIT_LD = ((1 << 31) - 1 - 64) // 63 // 8 * 8     # 34 087 040: the largest kv_seq * ld, a multiple of 8, that fits
+
+
+def flash_tile_offsets_fit(kv_seq, ldk, ldv):
+    """Host mirror of the entry point's test: the largest K / V byte offset inside a 64-key tile fits 32 bits."""
+    return kv_seq >= 0 and (63 * kv_seq * max(ldk, ldv) + 64) * 2 < (1 << 32)
+
+
+def _fa(name, kernel, fars, *, batch, heads, Sq, Sk, d=64, qk_mod=0, causal=False, bias=False, naive=False, flags=0, only=None):
+    return dict(name=name, kernel=kernel, fars=fars, batch=batch, heads=heads, Sq=Sq, Sk=Sk, d=d, qk_mod=qk_mod, causal=causal, bias=bias,
+                naive=naive, flags=flags, only=only)
+
+
+def far_attention_specs():
+    """Every attention case: ``fars`` = (operand, "seq" | "outer") pairs made far in turn.  Sk = 40: one ragged tile; Sk = 88: a full and
+    a ragged tile (K / V far through kv_seq below the flash kernels' limit: 104 keys at a power-of-two stride of 2^25 elements would
+    span 6.4 GiB behind the 4 GiB lead); Sk = 104 with Q / O far.  Far K / V through kv_seq at Sk = 40 exceeds the limit (2^26
+    elements per key) and takes the 64-bit fallback."""
+    S = "seq"
+    return [
+        _fa("flash 4-wave b3 h2 Sq130 Sk40", "4-wave flash", (("Q", S), ("K", S), ("V", S), ("O", S), ("K", "outer"), ("Q", "outer")), batch=3, heads=2, Sq=130, Sk=40),
+        _fa("flash 4-wave b1 h1 Sq130 Sk70 at the limit of the 32-bit tile offsets", "4-wave flash", (("K", "limit"), ("K", "limit+8"), ("V", "limit"), ("V", "limit+8")),
+            batch=1, heads=1, Sq=130, Sk=70),
+        _fa("flash 4-wave b2 h2 Sq130 Sk88", "4-wave flash", (("K", S), ("V", S)), batch=2, heads=2, Sq=130, Sk=88),
+        _fa("flash 4-wave b2 h2 Sq130 Sk104", "4-wave flash", (("Q", S), ("O", S)), batch=2, heads=2, Sq=130, Sk=104),
+        _fa("flash 8-wave b264 h1 Sq1024 Sk2100", "8-wave", (("K", S), ("V", "outer")), batch=264, heads=1, Sq=1024, Sk=2100, only=(0, 263)),
+        _fa("PnP shared-softmax 4-wave b3 h2 S130", "shared-softmax 4-wave", (("K", S), ("V", S), ("O", S), ("V", "outer")), batch=3, heads=2, Sq=130, Sk=130, qk_mod=1),
+        _fa("PnP shared-softmax 4-wave b3 h2 Sq130 Sk40", "shared-softmax 4-wave", (("K", S), ("V", S)), batch=3, heads=2, Sq=130, Sk=40, qk_mod=1),
+        _fa("PnP shared-softmax 8-wave b129 h3 Sq2048 Sk2100", "shared-softmax 8-wave", (("V", S), ("K", "outer")), batch=129, heads=3, Sq=2048, Sk=2100,
+            qk_mod=43, only=(0, 43, 128)),
+        _fa("short one-wave b5 h2 S12", "short one-wave", (("Q", S), ("K", S), ("V", S), ("O", S), ("V", "outer")), batch=5, heads=2, Sq=12, Sk=12),
+        _fa("short one-wave PnP b6 h2 S12", "short one-wave PnP", (("K", S), ("V", S), ("O", S), ("K", "outer")), batch=6, heads=2, Sq=12, Sk=12, qk_mod=2),
+        _fa("whole-sequence MFMA b3 h2 S40 d80", "whole-sequence MFMA", (("Q", S), ("K", S), ("V", S), ("O", S), ("K", "outer")), batch=3, heads=2, Sq=40, Sk=40, d=80),
+        _fa("whole-sequence MFMA causal b3 h2 S40 d64", "whole-sequence MFMA", (("K", S), ("V", S)), batch=3, heads=2, Sq=40, Sk=40, causal=True),
+        _fa("96-key loop b3 h2 S330 d80", "96-key loop", (("K", S), ("V", S), ("O", S), ("K", "outer")), batch=3, heads=2, Sq=330, Sk=330, d=80),
+        _fa("96-key loop causal b2 h1 S330 d64", "96-key loop", (("K", S), ("Q", S)), batch=2, heads=1, Sq=330, Sk=330, causal=True),
+        _fa("score bias b3 h2 Sq20 Sk40 d40", "bias", (("K", S), ("V", S), ("O", "outer")), batch=3, heads=2, Sq=20, Sk=40, d=40, bias=True),
+        _fa("score bias (generic kernel) b2 h2 Sq33 Sk130 d40", "bias", (("K", S),), batch=2, heads=2, Sq=33, Sk=130, d=40, bias=True),
+        _fa("generic kernel b3 h2 Sq33 Sk40", "generic", (("Q", S), ("K", S), ("V", S), ("O", S), ("K", "outer")), batch=3, heads=2, Sq=33, Sk=40, naive=True),
+    ]
+
+
+def far_attention_layout(spec, which, via):
+    """The far launch of ``spec`` with ``which`` far through ``via``: the pair that shares strides with ``which`` (Q / O, K / V) lies on
+    the sparse row pattern; ``which`` gets the power-of-two leading dimension that puts its last row at or past 2^32 bytes.
+    -> dict(strides of the pair, ld of ``which``, S, nb, geometry)."""
+    import numpy as np
+    pair_q = which in ("Q", "O")
+    S = spec["Sq"] if pair_q else spec["Sk"]
+    nb = spec["batch"]
+    if via.startswith("limit"):
+        # one key per row, the leading dimension at the last value the flash kernels' 32-bit tile offsets hold (kv_seq * ld = 34 087 040
+        # elements, a multiple of 8) and 8 elements past it: the entry point's test, pinned on both sides of its edge
+        assert not pair_q and nb == 1
+        strides = (S, 0, 1)
+        ld = FLASH_LIMIT_LD + (8 if via.endswith("+8") else 0)
+    elif via == "seq":
+        assert nb <= FAR_ATTN_SEQ_ROWS
+        strides = (1, 0, FAR_ATTN_SEQ_ROWS)
+        ld = far_ld(S) // FAR_ATTN_SEQ_ROWS            # (S - 1) * seq * ld >= 2^31 elements
+    else:
+        assert S <= FAR_ATTN_OUTER_ROWS and nb >= 3
+        strides = (FAR_ATTN_OUTER_ROWS, 0, 1)
+        ld = far_ld(nb) // FAR_ATTN_OUTER_ROWS
+    C = spec["heads"] * spec["d"]
+    assert ld >= C and ld % 8 == 0
+    i, s = np.arange(nb, dtype=np.int64)[:, None], np.arange(S, dtype=np.int64)[None]
+    rows = (i * strides[0] + s * strides[2]).reshape(-1)
+    geo = far_geometry(f"{spec['name']}: {which} far via {via}", rows * ld, C, 2, **({} if via.startswith("limit") else dict(ld=ld)))
+    fallback = spec["kernel"] in ("4-wave flash", "8-wave", "shared-softmax 4-wave", "shared-softmax 8-wave") and not pair_q and \
+        not flash_tile_offsets_fit(strides[2], ld, C)
+    return dict(strides=strides, ld=ld, S=S, nb=nb, rows=rows, geo=geo, pair_q=pair_q, fallback=fallback)
+
+
+def _far_attn_case(spec):
+    why = far_skip_reason()
+    name = f"far attention[{spec['kernel']}] {spec['name']}"
+    if why is not None:
+        return [_skip_row(f"{name}: near and {len(spec['fars'])} far launches", why)]
+    b, h, Sq, Sk, d = spec["batch"], spec["heads"], spec["Sq"], spec["Sk"], spec["d"]
+    C = h * d
+    seed = Sq + Sk + d
+    data = dict(Q=rnd(b * Sq, C, seed=seed + 1), K=rnd(b * Sk, C, seed=seed + 2), V=rnd(b * Sk, C, seed=seed + 3))
+    bias = torch.randn(h, Sq, Sk, generator=torch.Generator().manual_seed(Sk)).to(DEV) if spec["bias"] else None
+    kw = dict(batch=b, heads=h, Sq=Sq, Sk=Sk, inner=1, qk_mod=spec["qk_mod"])
+    extra = {} if d == 64 and not spec["causal"] and bias is None else dict(scale=d ** -0.5, head_dim=d, causal=spec["causal"])
+    near = dict(q_strides=(Sq, 0, 1), kv_strides=(Sk, 0, 1))
+    saved, ops.ATTN_FLAGS = ops.ATTN_FLAGS, ops.ATTN_FLAGS | spec["flags"]
+    try:
+        o = _poison((b * Sq, C), torch.float16)
+        y_near = ops.attention(data["Q"], data["K"], data["V"], o, naive=spec["naive"], bias=bias, **kw, **near, **extra)
+        torch.cuda.synchronize()
+        rows_ref, ref = _attn_ref(data["Q"], data["K"], data["V"], d=d, causal=spec["causal"], bias=bias, only=spec["only"], **kw, **near)
+        out = [_res(f"{name}: near vs reference", y_near[rows_ref], ref, KTOL)]
+        for which, via in spec["fars"]:
+            torch.cuda.reset_peak_memory_stats()
+            L = far_attention_layout(spec, which, via)
+            idx = torch.from_numpy(L["rows"]).to(DEV)
+            n_rows = int(L["rows"].max()) + 1
+            ops_t, buf = {}, None
+            for nm in ("Q", "O") if L["pair_q"] else ("K", "V"):
+                src = _poison((b * Sq, C), torch.float16) if nm == "O" else data[nm]
+                if nm == which:
+                    buf = _FarBuffer(L["geo"], torch.float16, seed=seed)
+                    buf.write(src)
+                    ops_t[nm] = buf.view((n_rows, C), (L["ld"], 1))
+                else:
+                    m = torch.empty(n_rows, C, dtype=torch.float16, device=DEV)
+                    m[idx] = src
+                    ops_t[nm] = m
+            for nm in ("K", "V") if L["pair_q"] else ("Q", "O"):
+                ops_t[nm] = _poison((b * Sq, C), torch.float16) if nm == "O" else data[nm]
+            st = dict(near)
+            st["q_strides" if L["pair_q"] else "kv_strides"] = L["strides"]
+            ops.attention(ops_t["Q"], ops_t["K"], ops_t["V"], ops_t["O"], naive=spec["naive"], bias=bias, **kw, **st, **extra)
+            torch.cuda.synchronize()
+            y = buf.read() if which == "O" else (ops_t["O"][idx] if L["pair_q"] else ops_t["O"])
+            tag = f"{name}: {which} far via {via}"
+            if L["fallback"]:
+                r = _res(f"{tag} (beyond the flash kernels' limit: 64-bit fallback) vs reference", y[rows_ref], ref, KTOL)
+                r["ok"] = r["ok"] and buf.decoys_intact()
+                out.append(r)
+            else:
+                out.append(_same_row(f"{tag} == near, bit for bit, decoys untouched", y.contiguous(), y_near, buf.decoys_intact()))
+            FAR_PEAK[tag] = torch.cuda.max_memory_allocated()
+            del buf, ops_t, y, idx
+            torch.cuda.empty_cache()
+    finally:
+        ops.ATTN_FLAGS = saved
+    return out
+
+
+def check_far_attention(kernel):
+    out = []
+    for spec in far_attention_specs():
+        if spec["kernel"] == kernel or (kernel == "short one-wave" and spec["kernel"] == "short one-wave PnP"):
+            out += _far_attn_case(spec)
+    return out
+
+
+def check_attention_negative_kv_seq():
+    """kv_seq = -1 (K / V handed over at their last key, walked backwards): the flash kernels' unsigned tile offsets cannot hold it, the
+    entry point takes the 64-bit kernels.  softmax(Q K^T) V does not depend on the order of the keys: the reference is the plain one."""
+    b, h, Sq, Sk = 2, 2, 130, 70
+    C = 64 * h
+    q, k, v = rnd(b * Sq, C, seed=1), rnd(b * Sk, C, seed=2), rnd(b * Sk, C, seed=3)
+    kw = dict(batch=b, heads=h, Sq=Sq, Sk=Sk, inner=1, q_strides=(Sq, 0, 1))
+    rows, ref = _attn_ref(q, k, v, kv_strides=(Sk, 0, 1), **kw)
+    o = _poison((b * Sq, C), torch.float16)
+    ops.attention(q, k[Sk - 1:], v[Sk - 1:], o, kv_strides=(Sk, 0, -1), **kw)
+    torch.cuda.synchronize()
+    return [_res(f"attention b{b} h{h} Sq{Sq} Sk{Sk}, kv_seq = -1 (64-bit fallback) vs reference", o[rows], ref, KTOL)]
+
+
+FAR_ATTN_KERNELS = ("4-wave flash", "8-wave", "shared-softmax 4-wave", "shared-softmax 8-wave", "short one-wave", "whole-sequence MFMA", "96-key loop",
+                    "bias", "generic")
+
+
+# ---- layout and elementwise kernels with a leading dimension
+FAR_LAYOUT_M = 161     # rows of the far matrices below: (M - 1) * 2^24 elements = 5 GiB of fp16
+FAR_LAYOUT_CASES = ("copy_cols", "gather_rows", "rotary", "ncfhw_to_tokens", "tokens_to_ncfhw", "softmax_rows", "cfg_ddim_step", "freeu", "tile_blend")
+FAR_FREEU = (2, 9, 9, 16, 8)            # n_img, H, W, C_hidden, C_skip: 162 rows
+FAR_TILE_ROWS = 1281                    # rows of the far tile matrix (the stitch of 2 images of 14 x 20 needs 936: the last tile lies at its end)
+
+
+def far_layout_geometries():
+    """(name, rows, cols, item) of every far matrix the layout cases make (``far_matrix_geometry``)."""
+    M = FAR_LAYOUT_M
+    return [("copy_cols x", M, 24, 2), ("copy_cols y", M, 32, 2), ("gather_rows x", M, 16, 2), ("gather_rows y", M, 16, 2), ("rotary x", M, 64, 2),
+            ("ncfhw_to_tokens y", 2 * 3 * 30, 16, 2), ("tokens_to_ncfhw x", 2 * 3 * 30, 16, 2), ("softmax_rows s", 5, 257, 4), ("softmax_rows p", 5, 257, 2),
+            ("cfg_ddim_step v", 3 * 3 * 20, 8, 2), ("freeu hidden", 162, 16, 2), ("freeu hidden'", 162, 16, 2), ("freeu skip", 162, 8, 2),
+            ("freeu skip'", 162, 8, 2), ("tile_blend tiles", FAR_TILE_ROWS, 8, 2)]
+
+
+def check_far_layout(case):
+    M = FAR_LAYOUT_M
+    if case == "copy_cols":
+        x, pre = rnd(M, 24, seed=1), rnd(M, 32, seed=2)
+        want = pre.clone()
+        want[:, 5:18] = x[:, 3:16]
+        return _far_case_rows("far copy_cols x[:, 3:16] -> y[:, 5:18]", lambda f: ops.copy_cols(f.mat("x", x), 3, f.mat("y", pre, out=True, inplace=True), 5, 13),
+                              ("x", "y"), want.double(), 0.0)
+    if case == "gather_rows":
+        src, pre = rnd(M, 16, seed=3), rnd(M, 16, seed=4)
+        idx = torch.randint(0, M, (M,), generator=torch.Generator().manual_seed(5)).to(torch.int32)
+        idx[:3] = torch.tensor([M - 1, 0, M - 1])      # the far row is named first and last
+        idx[-1] = M - 1
+        idx = idx.to(DEV)
+        want = pre.clone()
+        want[:, 8:16] = src[idx.long(), 8:16]
+        return _far_case_rows("far gather_rows", lambda f: ops.gather_rows(f.mat("x", src), 8, idx, f.mat("y", pre, out=True, inplace=True), 8, 8),
+                              ("x", "y"), want.double(), 0.0)
+    if case == "rotary":
+        x = rnd(M, 64, seed=6)
+        rot, n_pos, rpp, theta = 32, 7, 5, 10000.0
+        pos = ((torch.arange(M, device=DEV) // rpp) % n_pos).double()
+        ang = pos[:, None] * theta ** (-torch.arange(0, rot, 2, device=DEV).double() / rot)[None]
+        xr = x.double().clone()
+        a, b = xr[:, 8:8 + rot:2].clone(), xr[:, 9:9 + rot:2].clone()
+        xr[:, 8:8 + rot:2], xr[:, 9:9 + rot:2] = a * ang.cos() - b * ang.sin(), a * ang.sin() + b * ang.cos()
+        return _far_case_rows("far rotary cols 8..40", lambda f: ops.rotary(f.mat("x", x, out=True, inplace=True), 8, rot, rpp, n_pos, theta), ("x",), xr, KTOL)
+    if case in ("ncfhw_to_tokens", "tokens_to_ncfhw"):
+        B, C, Fr, H, W = 2, 9, 3, 5, 6
+        lat, pre = rnd(B, C, Fr, H, W, seed=7), rnd(B * Fr * H * W, 16, seed=8)
+        tok = pre.clone()
+        tok[:, 4:4 + C] = lat.permute(0, 2, 3, 4, 1).reshape(-1, C)
+        if case == "ncfhw_to_tokens":
+            return _far_case_rows("far ncfhw_to_tokens -> tokens[:, 4:13]", lambda f: ops.ncfhw_to_tokens(lat, f.mat("y", pre, out=True, inplace=True), col0=4),
+                                  ("y",), tok.double(), 0.0)
+        return _far_case_rows("far tokens_to_ncfhw <- tokens[:, 4:13]",
+                              lambda f: ops.tokens_to_ncfhw(f.mat("x", tok), B, C, Fr, H, W, col0=4).reshape(B * C, -1), ("x",), lat.double().reshape(B * C, -1), 0.0)
+    if case == "softmax_rows":
+        s = (torch.randn(5, 257, generator=torch.Generator().manual_seed(9)) * 3.0).to(DEV)
+        sc = 0.044194173824159216
+        return _far_case_rows("far softmax_rows 5 x 257", lambda f: ops.softmax_rows(f.mat("s", s), sc, out=f.mat("p", torch.empty(5, 257, dtype=torch.float16, device=DEV), out=True)),
+                              ("s", "p"), torch.softmax(sc * s.double(), 1), KTOL)
+    if case == "cfg_ddim_step":
+        Fr, H, W, C = 3, 4, 5, 4
+        vt, latx = rnd(3 * Fr * H * W, 8, seed=10), rnd(1, C, Fr, H, W, seed=11)
+        cf = torch.tensor((0.8, 0.6, 0.9, math.sqrt(1 - 0.81)), dtype=torch.float32, device=DEV)
+        c = [float(t) for t in cf]
+        vv = vt[:, :C].double().view(3, Fr, H * W, C).permute(0, 3, 1, 2).reshape(3, C, Fr, H, W)
+        v = _h(vv[0].float() + _h(7.5 * _h(vv[2].float() - vv[0].float()))).double()   # the kernel's fp16 CFG rounding points
+        xx = latx.double()[0]
+        ref = c[2] * (c[0] * xx - c[1] * v) + c[3] * (c[0] * v + c[1] * xx)
+        return _far_case_rows("far cfg_ddim_step b_unc 0, b_cond 2 (the last branch's rows are the far ones)",
+                              lambda f: ops.cfg_ddim_step(f.mat("v", vt), 0, 2, 7.5, cf, latx, torch.empty_like(latx))[0].reshape(C, -1), ("v",), ref.reshape(C, -1), KTOL)
+    if case == "freeu":
+        import freeu_spec
+        n_img, H, W, Ch, Cs = FAR_FREEU
+        rows, b_, s_ = n_img * H * W, 1.2, 0.9
+        g = torch.Generator().manual_seed(77)
+        hidden, skip = (1.5 * torch.randn(rows, Ch, generator=g) + 2).half(), (1.5 * torch.randn(rows, Cs, generator=g) + 2).half()
+        ref_h, ref_s = freeu_spec.freeu_tokens_reference(hidden, skip, n_img, H, W, b_, s_, dtype=torch.float64)
+        hd, sd = hidden.to(DEV), skip.to(DEV)
+
+        def run(f):
+            ho, so = ops.freeu(f.mat("hidden", hd), f.mat("skip", sd), n_img, H, W, b_, s_,
+                               out=(f.mat("hidden'", torch.empty(rows, Ch, dtype=torch.float16, device=DEV), out=True),
+                                    f.mat("skip'", torch.empty(rows, Cs, dtype=torch.float16, device=DEV), out=True)))
+            if f.which == "hidden'":
+                ho = f.buf.read()
+            if f.which == "skip'":
+                so = f.buf.read()
+            f.is_out = False      # both outputs are returned, joined: the far one is already read back
+            return torch.cat([ho, so], 1)
+        return _far_case_rows(f"far freeu {n_img} x {H}x{W} C{Ch} / C{Cs}", run, ("hidden", "skip", "hidden'", "skip'"),
+                              torch.cat([ref_h.double(), ref_s.double()], 1), KTOL)
+    if case == "tile_blend":
+        import vae_tiling_spec as vts
+        from anyv2v_amd.vae_tiling import AxisPlan, StitchPlan
+        p, size, n_img, C = vts.DEC, (14, 20), 2, 8
+        plan = StitchPlan(AxisPlan(size[0], **p), AxisPlan(size[1], **p))
+        g = torch.Generator().manual_seed(14020)
+        tiles = [[torch.randn(n_img, C, th, tw, generator=g).half() for tw in plan.ax.sizes] for th in plan.ay.sizes]
+        want = vts.stitch([[t.double() for t in r] for r in tiles], p["e"], p["limit"], crop=(plan.H, plan.W))
+        bases, rows = [], 0
+        for th in plan.ay.sizes:
+            bases.append([])
+            for tw in plan.ax.sizes:
+                bases[-1].append(rows)
+                rows += n_img * th * tw
+        assert rows <= FAR_TILE_ROWS
+        bases[-1][-1] = FAR_TILE_ROWS - n_img * plan.ay.sizes[-1] * plan.ax.sizes[-1]     # the last tile ends on the matrix's last row
+        raw = torch.full((FAR_TILE_ROWS, 8), float("nan"), dtype=torch.float16)
+        for ty, r in enumerate(tiles):
+            for tx, t in enumerate(r):
+                m = t.shape[0] * t.shape[2] * t.shape[3]
+                raw[bases[ty][tx]:bases[ty][tx] + m, :C] = t.permute(0, 2, 3, 1).reshape(m, C)
+        raw = raw.to(DEV)
+        # one rounding of an fp64 sum: within one fp16 ulp of the exact value, i.e. 2^-10 of it
+        return _far_case_rows("far tile_blend 2 x 14x20 C8 (tile_rows 1281)", lambda f: ops.tile_blend(f.mat("tiles", raw), C, plan, bases, n_img).reshape(n_img * C, -1),
+                              ("tiles",), want.reshape(n_img * C, -1), 2.0 ** -10)
+    raise KeyError(case)
+
+
+# ---- norms: no leading dimension in the ABI, so the source itself is 4 GiB (M * C just past 2^31 elements) and so is the output
+FAR_NORM_ENTRIES = ("groupnorm", "groupnorm pivot entry points", "groupnorm_from_stats", "layernorm")
+FAR_NORM_SHAPE = (2, 13 << 18, 320, 32)     # statistics groups, rows per group (13 reference chunks of 2^18 rows), C, G: M * C = 2^31 + 33 554 432
+
+
+def check_far_norm(entry):
+    """One norm entry point on a real [M, 320] source of 2^31 + 2^25 elements: the first and the last 2048 rows and every 4099th row
+    against float64 (statistics summed in float64 over the whole source, in chunks) at KTOL.  The rows past 2^31 elements hold their
+    own random data, so a 32-bit row offset reads, or writes, a wrong row."""
+    nsg, rpg, C, G = FAR_NORM_SHAPE
+    M, cg, eps = nsg * rpg, C // G, 1e-5
+    name = f"far {entry} M{M} C{C} (2^31 + {M * C - (1 << 31)} elements)"
+    why = far_skip_reason()
+    if why is not None:
+        return [_skip_row(name, why)]
+    assert M * C > 1 << 31
+    torch.cuda.reset_peak_memory_stats()
+    x = torch.empty(M, C, dtype=torch.float16, device=DEV)
+    g = torch.Generator(device=DEV).manual_seed(47)
+    step = 1 << 19
+    for r in range(0, M, step):
+        x[r:r + step].normal_(0.5, 1.0, generator=g)
+    ga, be = _affine(C, 31)
+    idx = torch.cat([torch.arange(2048), torch.arange(2048, M - 2048, 4099), torch.arange(M - 2048, M)]).to(DEV)
+    xs = x[idx].double()
+    if entry == "layernorm":
+        y = ops.layernorm(x, ga, be, eps)
+        ref = _ln_ref64(xs, ga, be, eps)
+    else:
+        s1 = torch.zeros(nsg, G, dtype=torch.float64, device=DEV)
+        s2 = torch.zeros(nsg, G, dtype=torch.float64, device=DEV)
+        chunk = 1 << 18
+        assert rpg % chunk == 0
+        for r in range(0, M, chunk):
+            xc = x[r:r + chunk].double().view(chunk, G, cg)
+            s1[r // rpg] += xc.sum((0, 2))
+            s2[r // rpg] += xc.square_().sum((0, 2))
+        mean = s1 / (rpg * cg)
+        rstd = torch.rsqrt(s2 / (rpg * cg) - mean * mean + eps)      # float64: the cancellation costs 1e-16 x (1 + mean^2 / var)
+        sg = idx // rpg
+        yn = ((xs.view(-1, G, cg) - mean[sg][:, :, None]) * rstd[sg][:, :, None]).view(-1, C) * ga.double() + be.double()
+        ref = yn * torch.sigmoid(yn)
+        if entry == "groupnorm_from_stats":
+            need = ops.gn_stats_floats(M, rpg, G)
+            stats = torch.zeros(need, dtype=torch.float32, device=DEV)
+            rec = stats[:3 * (M // 16) * G].view(M // 16, G, 3)
+            for r in range(0, M, chunk):     # the records a producing GEMM writes: (K, sum(x - K), sum((x - K)^2)) per (16 rows, channel group)
+                xc = x[r:r + chunk].float().view(chunk // 16, 16, G, cg)
+                K = xc[:, 0, :, 0].clone()
+                dlt = xc - K[:, None, :, None]
+                out = rec[r // 16:(r + chunk) // 16]
+                out[:, :, 0], out[:, :, 1], out[:, :, 2] = K, dlt.sum((1, 3)), dlt.square().sum((1, 3))
+            y = ops.groupnorm_from_stats(x, ga, be, stats, rpg, groups=G, eps=eps, silu=True)
+        else:
+            stats = torch.zeros(ops.gn_scratch_floats(M, rpg, G), dtype=torch.float32, device=DEV)
+            shard = (1, lambda t: None) if entry == "groupnorm pivot entry points" else None
+            y = ops.groupnorm(x, ga, be, stats, rpg, groups=G, eps=eps, silu=True, shard=shard)
+    torch.cuda.synchronize()
+    rows = [_res(f"{name}: first / last 2048 rows and every 4099th row vs float64", y[idx], ref, KTOL)]
+    FAR_PEAK[name] = torch.cuda.max_memory_allocated()
+    del x, y
+    torch.cuda.empty_cache()
+    return rows
+
+
+# ---- flat kernels: the only cases that move 4 GiB per operand
+FAR_FLAT_N = (1 << 31) + 8 * 1024 + 3
+
+
+def check_far_flat(which):
+    """``silu`` / ``add`` on n = 2^31 + 8 x 1024 + 3 elements: the first and the last 2^20 elements and a strided sample against float64
+    (2e-3, the elementwise edge check's bound), the whole output against torch's own elementwise result in chunks."""
+    name = f"far {which} n = 2^31 + 8195"
+    why = far_skip_reason()
+    if why is not None:
+        return [_skip_row(name, why)]
+    n, ch = FAR_FLAT_N, 1 << 26    # chunked compares: the temporaries stay far below the two 4 GiB operands
+    torch.cuda.reset_peak_memory_stats()
+    x = torch.empty(n, dtype=torch.float16, device=DEV)
+    g = torch.Generator(device=DEV).manual_seed(31)
+    for o in range(0, n, 1 << 28):
+        x[o:o + (1 << 28)].normal_(0.0, 2.0, generator=g)
+    if which == "silu":
+        y = ops.silu(x)
+        f64 = lambda sl: F.silu(x[sl].double())
+        native = lambda sl: F.silu(x[sl].float()).half()
+    else:
+        b = x    # both addends are the one 4 GiB buffer: the case stays inside FAR_CAP
+        y = ops.add(x, b)
+        f64 = lambda sl: x[sl].double() + b[sl].double()
+        native = lambda sl: x[sl] + b[sl]
+    torch.cuda.synchronize()
+    rows = []
+    for tag, sl in (("first 2^20", slice(0, 1 << 20)), ("last 2^20", slice(n - (1 << 20), n)), ("every 4099th", slice(0, n, 4099))):
+        rows.append(_res(f"{name}: {tag} elements vs float64", y[sl], f64(sl), 2e-3))
+    bad = 0
+    for o in range(0, n, ch):
+        sl = slice(o, min(o + ch, n))
+        bad += int((y[sl] != native(sl)).sum())
+    if which == "add":
+        rows.append(dict(name=f"{name}: whole output == torch's fp16 add, differing elements", err=float(bad), tol=0.0, ok=bad == 0))
+    else:   # silu in fp32 rounded once: torch's own kernel may round the last bit differently; the count is reported, the bound is 1 ulp
+        ulp = 0
+        for o in range(0, n, ch):
+            sl = slice(o, min(o + ch, n))
+            ulp = max(ulp, int((_fp16_key(y[sl]) - _fp16_key(native(sl))).abs().max()))
+        rows.append(dict(name=f"{name}: whole output vs torch's fp32 silu rounded to fp16, max ulps ({bad} elements differ)", err=float(ulp), tol=1.0, ok=ulp <= 1))
+    FAR_PEAK[name] = torch.cuda.max_memory_allocated()
+    del x, y
+    torch.cuda.empty_cache()
+    return rows
