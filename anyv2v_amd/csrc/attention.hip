@@ -20,6 +20,7 @@
 // Next KV tile is prefetched global->registers while the current one is consumed (async-stage split, T14).
 #include <type_traits>
 
+#include "attention_plan.h"
 #include "common.h"
 
 struct AttnK {
@@ -686,12 +687,8 @@ __global__ __launch_bounds__(256) void small_attn_mfma_kernel(const AttnK p, con
     }
 }
 
-static int fill(const AnyV2VAttnDesc* d, AttnK& k, int head_dim) {
-    AV_CHECK(d != nullptr, "attention: null descriptor");
-    AV_CHECK(d->Q && d->K && d->V && d->O, "attention: null pointer");
-    AV_CHECK(d->batch > 0 && d->heads > 0 && d->Sq > 0 && d->Sk > 0, "attention: bad sizes");
-    AV_CHECK(d->inner > 0 && d->kv_div > 0 && d->qk_mod >= 0, "attention: bad inner/kv_div/qk_mod");
-    AV_CHECK(d->ldq > 0 && d->ldk > 0 && d->ldv > 0 && d->ldo > 0, "attention: leading dimensions must be positive");
+// The launch arguments of a planned descriptor (attention_plan.cpp validated it and chose q_tiles / causal).
+static void fill(const AnyV2VAttnDesc* d, const AttnPlan& p, AttnK& k, int head_dim) {
     k.Q = (const half_t*)d->Q;
     k.K = (const half_t*)d->K;
     k.V = (const half_t*)d->V;
@@ -702,98 +699,70 @@ static int fill(const AnyV2VAttnDesc* d, AttnK& k, int head_dim) {
     k.kv_outer = d->kv_outer; k.kv_inner = d->kv_inner; k.kv_seq = d->kv_seq;
     k.kv_div = d->kv_div; k.qk_mod = d->qk_mod;
     k.scale_log2 = d->scale * 1.4426950408889634f;
-    k.q_tiles = (d->Sq + 127) / 128;
+    k.q_tiles = p.q_tiles;
     k.head_dim = head_dim;
-    k.causal = 0;
+    k.causal = p.causal;
     k.narrow_store = (d->flags & 128) ? 1 : 0;
-    return ANYV2V_OK;
 }
 
-static int launch_naive(const AttnK& k, hipStream_t s, const float* bias = nullptr) {
-    const long long total = (long long)k.batch * k.heads * k.Sq;
-    hipLaunchKernelGGL(attn_naive_kernel, dim3((unsigned)((total + 127) / 128)), dim3(128), 0, s, k, bias);
+static int launch_naive(const AttnK& k, const AttnPlan& p, hipStream_t s, const float* bias = nullptr) {
+    hipLaunchKernelGGL(attn_naive_kernel, dim3(p.grid_x), dim3(p.block), 0, s, k, bias);
     return av_launch_status("attention_naive");
 }
 
-// PnP injection launch (i2vgen-xl/pnp_utils.py:189-196, :295-302): three branches whose Q / K are the source branch's -> the shared-softmax
-// kernels.  ONE predicate for the short and the flash path (flag bit3 forces the per-branch aliasing form).
-static inline bool av_attn_pnp3(const AttnK& k, const AnyV2VAttnDesc* d) {
-    return k.qk_mod > 0 && k.batch == 3 * k.qk_mod && k.kv_div == 1 && !(d->flags & 8);
+// A plan whose instantiation the entry point does not hold: an error, never another kernel.
+static int no_instantiation(const AttnPlan& p) {
+    anyv2v_set_error("attention: no launch for the planned kernel %s", av_attn_kernel_name(p));
+    return ANYV2V_EINVAL;
 }
 
-static int launch_loop_d64(const AttnK& k, hipStream_t s);   // behind loop_attn_mfma_kernel, below
+static int launch_loop_d64(const AttnK& k, const AttnPlan& p, hipStream_t s);   // behind loop_attn_mfma_kernel, below
 
+// Which kernel runs a descriptor, and why, is attention_plan.cpp's; the entry points below launch what the plan names.
 extern "C" int anyv2v_attention_f16(const AnyV2VAttnDesc* d, void* stream) {
+    const AttnPlan p = av_attn_plan(d, ATTN_ENTRY_D64, 64, false);
+    if (p.status != ANYV2V_OK) return p.status;
     AttnK k;
-    int rc = fill(d, k, 64);
-    if (rc != ANYV2V_OK) return rc;
+    fill(d, p, k, 64);
     hipStream_t s = (hipStream_t)stream;
-    const bool fast = !(d->flags & 1) && d->ldq % 8 == 0 && d->ldk % 8 == 0 && d->ldv % 8 == 0 && d->ldo % 4 == 0 &&
-                      av_aligned16(d->Q) && av_aligned16(d->K) && av_aligned16(d->V) && av_aligned16(d->O);
-    if (!fast) return launch_naive(k, s);
-    if (k.Sq <= 16 && k.Sk <= 16 && d->ldo % 8 == 0 && !(d->flags & 2)) {  // temporal attention at <= 16 frames: one wave per sequence
-        if (av_attn_pnp3(k, d)) {
-            // PnP injection step: one wave per (source element, head), one softmax, three V / O streams (flag bit3: aliasing form)
-            const long long units3 = (long long)k.qk_mod * k.heads;
-            hipLaunchKernelGGL(short_attn_d64_kernel<3>, dim3((unsigned)((units3 + 3) / 4)), dim3(256), 0, s, k);
+    const dim3 grid(p.grid_x, p.grid_y, p.grid_z), block(p.block);
+    switch (p.kernel) {
+    case ATTN_NAIVE: return launch_naive(k, p, s);
+    case ATTN_SHORT:   // temporal attention at <= 16 frames: one wave per sequence; <3>: the PnP injection step's three V / O streams
+        if (p.streams == 3) {
+            hipLaunchKernelGGL(short_attn_d64_kernel<3>, grid, block, 0, s, k);
             return av_launch_status("short_attn_d64<pnp3>");
         }
-        const long long units = (long long)k.batch * k.heads;
-        hipLaunchKernelGGL(short_attn_d64_kernel<1>, dim3((unsigned)((units + 3) / 4)), dim3(256), 0, s, k);
+        if (p.streams != 1) return no_instantiation(p);
+        hipLaunchKernelGGL(short_attn_d64_kernel<1>, grid, block, 0, s, k);
         return av_launch_status("short_attn_d64");
+    case ATTN_LOOP: return p.ds == 2 ? launch_loop_d64(k, p, s) : no_instantiation(p);   // K / V strides beyond the flash kernels' 32-bit tile offsets
+    case ATTN_FLASH: break;
+    default: return no_instantiation(p);
     }
-    // The flash kernels keep the per-lane K / V source offsets of one 64-key tile in 32 bits (koff / voff_g: byte offsets of key rows
-    // 0 .. 63 from the tile pointer, 16-byte chunk included).  A layout whose largest in-tile byte offset does not fit -- or a negative
-    // sequence stride, which those unsigned offsets cannot hold -- runs on kernels that address every row in 64 bits: the 96-key loop
-    // kernel (same addressing contract: strides, kv_div, qk_mod as per-branch aliasing), or the generic kernel when the grid does not
-    // fit the loop kernel's.  Every shape the models issue stays far below the limit (4096 x 960 elements per key step against 34.1 M).
-    {
-        const long long ldkv = d->ldk > d->ldv ? d->ldk : d->ldv;
-        const bool wide = d->kv_seq < 0 || d->kv_seq > ((long long)0xFFFFFFFFll / 2 - 64) / 63 / ldkv;   // (63 kv_seq ld + 64) * 2 > 2^32 - 1
-        if (wide) {
-            if (k.heads <= 65535 && k.batch <= 65535) return launch_loop_d64(k, s);
-            return launch_naive(k, s);
-        }
-    }
-    const long long nwg = (long long)k.batch * k.heads * k.q_tiles;
-    AV_CHECK(nwg < (1ll << 31), "attention: grid too large");
     static const half_t* zeros = nullptr;
     if (zeros == nullptr) {
         void* ptr = nullptr;
         if (hipGetSymbolAddress(&ptr, HIP_SYMBOL(g_attn_zero_line)) == hipSuccess) zeros = (const half_t*)ptr;
     }
     AV_CHECK(zeros != nullptr, "attention: zero line symbol unavailable");
-    if (av_attn_pnp3(k, d)) {
-        // PnP injection step: one softmax per source element, three V / O streams (flag bit3 forces the aliasing form)
-        const long long nwg3 = (long long)k.qk_mod * k.heads * k.q_tiles;
-        // long KV loops with enough 256-query blocks to fill the chip (the 64x64 level: 16 x 5 x 16 = 1280): 8-wave blocks around a
-        // 3-stage ring -- two K / V tile sets in flight instead of one, half the LDS-DMA per query, one 96-KiB block per CU (the same
-        // two waves per SIMD as two 4-wave blocks).  0.6845 -> 0.6479 ms at (48, 5, 4096); 7 % slower at (48, 10, 1024), which stays
-        // on the 4-wave form (profiles/r05_attn_pnp_8wave_ab.txt); bit-equal.  Flag bit2: never (as for the plain kernel).
-        const long long n8 = (long long)k.qk_mod * k.heads * ((d->Sq + 255) / 256);
-        if (!(d->flags & 4) && d->Sk >= 2048 && d->Sq >= 2048 && n8 >= 1024) {
-            k.q_tiles = (d->Sq + 255) / 256;
-            hipLaunchKernelGGL((flash_attn_d64_v2_kernel<3, 3, 8>), dim3((unsigned)n8), dim3(512), 0, s, k, zeros);
-            return av_launch_status("flash_attn_d64_v2<pnp3, 8 waves>");
-        }
-        hipLaunchKernelGGL((flash_attn_d64_v2_kernel<2, 3, 4>), dim3((unsigned)nwg3), dim3(256), 0, s, k, zeros);
+    if (p.stages == 3 && p.streams == 3 && p.waves == 8) {
+        hipLaunchKernelGGL((flash_attn_d64_v2_kernel<3, 3, 8>), grid, block, 0, s, k, zeros);
+        return av_launch_status("flash_attn_d64_v2<pnp3, 8 waves>");
+    }
+    if (p.stages == 2 && p.streams == 3 && p.waves == 4) {
+        hipLaunchKernelGGL((flash_attn_d64_v2_kernel<2, 3, 4>), grid, block, 0, s, k, zeros);
         return av_launch_status("flash_attn_d64_v2<pnp3>");
     }
-    // 8-wave blocks (256 query rows per K / V ring) for launches that still fill the chip with them and whose KV loop is long
-    // enough to amortise the bigger block (measured: 1.19 -> 1.09 ms at 48 x 5 x 4096^2, equal at 1024^2, slower at Sk = 145)
-    const long long nwg8 = (long long)k.batch * k.heads * ((d->Sq + 255) / 256);
-    // (round 5: from Sk = 2048 on -- at 48 x 10 x 1024^2 the 4-wave kernel on its 2-stage ring is 4 % faster, 146.4 vs 152.0 us)
-    if (!(d->flags & 4) && d->Sk >= 2048 && d->Sq >= 1024 && nwg8 >= 1024) {
-        k.q_tiles = (d->Sq + 255) / 256;
-        hipLaunchKernelGGL((flash_attn_d64_v2_kernel<3, 1, 8>), dim3((unsigned)nwg8), dim3(512), 0, s, k, zeros);
+    if (p.stages == 3 && p.streams == 1 && p.waves == 8) {
+        hipLaunchKernelGGL((flash_attn_d64_v2_kernel<3, 1, 8>), grid, block, 0, s, k, zeros);
         return av_launch_status("flash_attn_d64_v2<8 waves>");
     }
-    // 4-wave blocks on a 2-stage ring: 32 KiB of LDS per block = four blocks per CU (three with 3 stages; the kernel's launch bounds ask
-    // for four waves per SIMD, it allocates 126 VGPRs -- profiles/r06_attention_resource_usage.txt); the short-KV launches
-    // (cross-attention, Sk = 145: three tiles per block, 7680 blocks) are bound by how many blocks are in flight -- 95.8 -> 82.6 us at
-    // (48, 5, 4096, 145), never slower up to Sk = 1024 (profiles/r05_attn_cross_2stage_ab.txt); bit-equal
-    hipLaunchKernelGGL((flash_attn_d64_v2_kernel<2, 1, 4>), dim3((unsigned)nwg), dim3(256), 0, s, k, zeros);
-    return av_launch_status("flash_attn_d64_v2");
+    if (p.stages == 2 && p.streams == 1 && p.waves == 4) {
+        hipLaunchKernelGGL((flash_attn_d64_v2_kernel<2, 1, 4>), grid, block, 0, s, k, zeros);
+        return av_launch_status("flash_attn_d64_v2");
+    }
+    return no_instantiation(p);
 }
 
 // Any sequence length at head_dim <= 160 (a multiple of 8): the whole-sequence kernel above with a loop over 96-key blocks and the
@@ -922,51 +891,34 @@ __global__ __launch_bounds__(256) void loop_attn_mfma_kernel(const AttnK p) {
 }
 
 // head_dim 64 on the loop kernel: where anyv2v_attention_f16 sends layouts whose K / V tile offsets do not fit the flash kernels' 32 bits
-static int launch_loop_d64(const AttnK& k, hipStream_t s) {
-    const dim3 grid((unsigned)((k.Sq + 63) / 64), (unsigned)k.heads, (unsigned)k.batch);
-    const size_t lds = (size_t)96 * (2 * 32 + 8) * 2 + (size_t)(2 * 32) * (96 + 4) * 2;   // 26 KiB: below the default dynamic-LDS limit
-    hipLaunchKernelGGL((loop_attn_mfma_kernel<2>), grid, dim3(256), lds, s, k);
+static int launch_loop_d64(const AttnK& k, const AttnPlan& p, hipStream_t s) {
+    hipLaunchKernelGGL((loop_attn_mfma_kernel<2>), dim3(p.grid_x, p.grid_y, p.grid_z), dim3(p.block), p.lds_bytes, s, k);
     return av_launch_status("loop_attn_mfma<wide K/V strides>");
 }
 
 extern "C" int anyv2v_attention_small_f16(const AnyV2VAttnDesc* d, int32_t head_dim, void* stream) {
-    AV_CHECK(head_dim > 0 && head_dim <= 160, "attention_small: head_dim must be in 1..160");
+    const AttnPlan p = av_attn_plan(d, ATTN_ENTRY_SMALL, head_dim, false);
+    if (p.status != ANYV2V_OK) return p.status;
     AttnK k;
-    int rc = fill(d, k, head_dim);
-    if (rc != ANYV2V_OK) return rc;
-    k.causal = (d->flags & 16) ? 1 : 0;
-    // short sequences, head_dim a multiple of 8 (16-byte chunks of a head are loaded whole): whole-sequence MFMA kernel (K and V^T of
-    // a head in LDS, zero-padded to 32 DS columns); flag bit0 = naive kernel.  DS = 5 (head_dim 136..160, ConsistI2V's temporal
-    // attention at C = 1280 / 8 heads) fits the LDS with up to 96 keys only.
-    const int ds = (head_dim + 31) / 32;
-    const int nkb = d->Sk <= 96 ? 6 : (d->Sk <= 288 && ds <= 4 ? 18 : 0);
-    const bool fast = !(d->flags & 1) && head_dim % 8 == 0 && ds >= 2 && ds <= 5 && nkb > 0 && d->ldq % 8 == 0 && d->ldk % 8 == 0 &&
-                      d->ldv % 8 == 0 && d->ldo % 4 == 0 && av_aligned16(d->Q) && av_aligned16(d->K) && av_aligned16(d->V) &&
-                      (((uintptr_t)d->O) & 7) == 0 && d->heads <= 65535 && d->batch <= 65535;
-    // the same conditions with a longer key sequence: the 96-key loop kernel (online softmax)
-    const bool loop_ok = !(d->flags & 1) && head_dim % 8 == 0 && ds >= 1 && ds <= 5 && nkb == 0 && d->ldq % 8 == 0 && d->ldk % 8 == 0 &&
-                         d->ldv % 8 == 0 && d->ldo % 4 == 0 && av_aligned16(d->Q) && av_aligned16(d->K) && av_aligned16(d->V) &&
-                         (((uintptr_t)d->O) & 7) == 0 && d->heads <= 65535 && d->batch <= 65535;
-    if (loop_ok) {
-        const dim3 lgrid((unsigned)((d->Sq + 63) / 64), (unsigned)d->heads, (unsigned)d->batch);
-        const int dsl = ds < 2 ? 2 : ds;
-        const size_t llds = (size_t)96 * (dsl * 32 + 8) * 2 + (size_t)(dsl * 32) * (96 + 4) * 2;
+    fill(d, p, k, head_dim);
+    const dim3 grid(p.grid_x, p.grid_y, p.grid_z), block(p.block);
+    const size_t lds = p.lds_bytes;
+    if (p.kernel == ATTN_NAIVE) return launch_naive(k, p, (hipStream_t)stream);
+    if (p.kernel == ATTN_LOOP) {   // the 96-key loop kernel (online softmax)
 #define AV_LA(DS_)                                                                                                            \
     do {                                                                                                                      \
         static bool attr_set = false;                                                                                         \
         if (!attr_set) {                                                                                                      \
-            (void)hipFuncSetAttribute((const void*)loop_attn_mfma_kernel<DS_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)llds); \
+            (void)hipFuncSetAttribute((const void*)loop_attn_mfma_kernel<DS_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
             attr_set = true;                                                                                                  \
         }                                                                                                                     \
-        hipLaunchKernelGGL((loop_attn_mfma_kernel<DS_>), lgrid, dim3(256), llds, (hipStream_t)stream, k);                     \
+        hipLaunchKernelGGL((loop_attn_mfma_kernel<DS_>), grid, block, lds, (hipStream_t)stream, k);                           \
     } while (0)
-        if (dsl == 2) AV_LA(2); else if (dsl == 3) AV_LA(3); else if (dsl == 4) AV_LA(4); else AV_LA(5);
+        if (p.ds == 2) AV_LA(2); else if (p.ds == 3) AV_LA(3); else if (p.ds == 4) AV_LA(4); else if (p.ds == 5) AV_LA(5); else return no_instantiation(p);
 #undef AV_LA
         return av_launch_status("loop_attn_mfma");
     }
-    if (!fast) return launch_naive(k, (hipStream_t)stream);
-    const dim3 grid((unsigned)((d->Sq + 63) / 64), (unsigned)d->heads, (unsigned)d->batch);
-    const size_t lds = (size_t)(nkb * 16) * (ds * 32 + 8) * 2 + (size_t)(ds * 32) * (nkb * 16 + 4) * 2;
+    if (p.kernel != ATTN_SMALL) return no_instantiation(p);
 #define AV_SA(DS_, NKB_)                                                                                                   \
     do {                                                                                                                   \
         static bool attr_set = false;                                                                                      \
@@ -975,33 +927,30 @@ extern "C" int anyv2v_attention_small_f16(const AnyV2VAttnDesc* d, int32_t head_
                                 (int)lds);                                                                                 \
             attr_set = true;                                                                                               \
         }                                                                                                                  \
-        hipLaunchKernelGGL((small_attn_mfma_kernel<DS_, NKB_>), grid, dim3(256), lds, (hipStream_t)stream, k);            \
+        hipLaunchKernelGGL((small_attn_mfma_kernel<DS_, NKB_>), grid, block, lds, (hipStream_t)stream, k);                \
     } while (0)
-    if (nkb == 6) {
-        if (ds == 2) AV_SA(2, 6); else if (ds == 3) AV_SA(3, 6); else if (ds == 4) AV_SA(4, 6); else AV_SA(5, 6);
+    if (p.nkb == 6) {
+        if (p.ds == 2) AV_SA(2, 6); else if (p.ds == 3) AV_SA(3, 6); else if (p.ds == 4) AV_SA(4, 6); else if (p.ds == 5) AV_SA(5, 6); else return no_instantiation(p);
+    } else if (p.nkb == 18) {
+        if (p.ds == 2) AV_SA(2, 18); else if (p.ds == 3) AV_SA(3, 18); else if (p.ds == 4) AV_SA(4, 18); else return no_instantiation(p);
     } else {
-        if (ds == 2) AV_SA(2, 18); else if (ds == 3) AV_SA(3, 18); else AV_SA(4, 18);
+        return no_instantiation(p);
     }
 #undef AV_SA
     return av_launch_status("small_attn_mfma");
 }
 
-// Attention with an additive score bias (fp32 [heads, Sq, Sk], added to scale * q.k before the softmax): the generic kernel.
+// Attention with an additive score bias (fp32 [heads, Sq, Sk], added to scale * q.k before the softmax): the whole-sequence MFMA kernel
+// with the bias added to the score fragments, or the generic kernel.
 extern "C" int anyv2v_attention_bias_f16(const AnyV2VAttnDesc* d, int32_t head_dim, const float* bias, void* stream) {
-    AV_CHECK(head_dim > 0 && head_dim <= 160, "attention_bias: head_dim must be in 1..160");
-    AV_CHECK(bias != nullptr, "attention_bias: null bias");
-    AV_CHECK(d && d->scale > 0.f, "attention_bias: scale must be positive");
-    {   // short sequences at head_dim % 8 == 0: the whole-sequence MFMA kernel with the bias added to the score fragments
-        const int ds = (head_dim + 31) / 32;
-        if (!(d->flags & 1) && head_dim % 8 == 0 && ds >= 2 && ds <= 5 && d->Sk <= 96 && d->ldq % 8 == 0 && d->ldk % 8 == 0 && d->ldv % 8 == 0 &&
-            d->ldo % 4 == 0 && av_aligned16(d->Q) && av_aligned16(d->K) && av_aligned16(d->V) && (((uintptr_t)d->O) & 7) == 0 &&
-            d->heads <= 65535 && d->batch <= 65535 && !(d->flags & 16)) {
-            AttnK kb;
-            int rcb = fill(d, kb, head_dim);
-            if (rcb != ANYV2V_OK) return rcb;
-            kb.causal = 0;
-            const dim3 grid((unsigned)((d->Sq + 63) / 64), (unsigned)d->heads, (unsigned)d->batch);
-            const size_t lds = (size_t)96 * (ds * 32 + 8) * 2 + (size_t)(ds * 32) * (96 + 4) * 2;
+    const AttnPlan p = av_attn_plan(d, ATTN_ENTRY_BIAS, head_dim, bias != nullptr);
+    if (p.status != ANYV2V_OK) return p.status;
+    AttnK k;
+    fill(d, p, k, head_dim);
+    if (p.kernel == ATTN_NAIVE) return launch_naive(k, p, (hipStream_t)stream, bias);
+    if (p.kernel != ATTN_SMALL || !p.bias || p.nkb != 6) return no_instantiation(p);
+    const dim3 grid(p.grid_x, p.grid_y, p.grid_z), block(p.block);
+    const size_t lds = p.lds_bytes;
 #define AV_SB(DS_)                                                                                                                       \
     do {                                                                                                                                 \
         static bool attr_set = false;                                                                                                    \
@@ -1009,16 +958,9 @@ extern "C" int anyv2v_attention_bias_f16(const AnyV2VAttnDesc* d, int32_t head_d
             (void)hipFuncSetAttribute((const void*)small_attn_mfma_kernel<DS_, 6, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
             attr_set = true;                                                                                                             \
         }                                                                                                                                \
-        hipLaunchKernelGGL((small_attn_mfma_kernel<DS_, 6, true>), grid, dim3(256), lds, (hipStream_t)stream, kb, bias);                \
+        hipLaunchKernelGGL((small_attn_mfma_kernel<DS_, 6, true>), grid, block, lds, (hipStream_t)stream, k, bias);                     \
     } while (0)
-            if (ds == 2) AV_SB(2); else if (ds == 3) AV_SB(3); else if (ds == 4) AV_SB(4); else AV_SB(5);
+    if (p.ds == 2) AV_SB(2); else if (p.ds == 3) AV_SB(3); else if (p.ds == 4) AV_SB(4); else if (p.ds == 5) AV_SB(5); else return no_instantiation(p);
 #undef AV_SB
-            return av_launch_status("small_attn_mfma<bias>");
-        }
-    }
-    AttnK k;
-    int rc = fill(d, k, head_dim);
-    if (rc != ANYV2V_OK) return rc;
-    k.causal = (d->flags & 16) ? 1 : 0;
-    return launch_naive(k, (hipStream_t)stream, bias);
+    return av_launch_status("small_attn_mfma<bias>");
 }

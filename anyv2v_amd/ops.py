@@ -341,6 +341,14 @@ def softmax_rows(s: torch.Tensor, scale: float, out: Optional[torch.Tensor] = No
     return out
 
 
+def attention_entry(head_dim, causal, has_bias):
+    """The entry point ``attention`` calls: 2 = ``anyv2v_attention_bias_f16`` (a bias), 0 = ``anyv2v_attention_f16`` (head_dim 64 without the
+    causal mask), 1 = ``anyv2v_attention_small_f16`` (anything else).  The numbers are the planner's (csrc/attention_plan.h: AttnEntry)."""
+    if has_bias:
+        return 2
+    return 0 if head_dim == 64 and not causal else 1
+
+
 def attention(q, k, v, out, *, batch, heads, Sq, Sk, inner=1, q_strides, kv_strides, kv_div=1, qk_mod=0,
               scale=0.125, head_dim=64, naive=False, causal=False, bias=None):
     """Strided multi-head attention over token matrices; see anyv2v_hip.h for the addressing.  ``causal`` (CLIP text tower)
@@ -357,10 +365,11 @@ def attention(q, k, v, out, *, batch, heads, Sq, Sk, inner=1, q_strides, kv_stri
     d.kv_outer, d.kv_inner, d.kv_seq = kv_strides
     d.kv_div, d.qk_mod, d.scale = kv_div, qk_mod, scale
     d.flags = (1 if (naive or FORCE_NAIVE) else 0) | ATTN_FLAGS | (16 if causal else 0)
-    if bias is not None:
+    entry = attention_entry(head_dim, causal, bias is not None)
+    if entry == 2:
         assert bias.dtype == torch.float32 and bias.is_contiguous() and tuple(bias.shape) == (heads, Sq, Sk) and bias.device == q.device
         _lib.check(lib.anyv2v_attention_bias_f16(C.byref(d), head_dim, _p(bias), _stream()), "anyv2v_attention_bias_f16")
-    elif head_dim == 64 and not causal:
+    elif entry == 0:
         _lib.check(lib.anyv2v_attention_f16(C.byref(d), _stream()), "anyv2v_attention_f16")
     else:
         _lib.check(lib.anyv2v_attention_small_f16(C.byref(d), head_dim, _stream()), "anyv2v_attention_small_f16")

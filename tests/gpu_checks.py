@@ -927,13 +927,16 @@ class _PlainOperands:
     """Operands of the plain launch of an edge row: fresh tensors (ragged widths padded to ``ld % 8 == 0``)."""
     framed = False
 
+    def __init__(self, device=None):
+        self.device = DEV if device is None else device      # "meta": the layout alone (tests/test_attention_plan_host.py)
+
     def inp(self, t, flat=False):
         return t if (t is None or flat) else _ld8(t)
 
     def out(self, M, C, dtype=torch.float16, init=None, cols=8):
         ld = (C + 7) // 8 * 8 + (0 if cols % 8 == 0 else 16)
         off = 0 if cols % 8 == 0 else cols
-        y = torch.zeros(M, ld, dtype=dtype, device=DEV)[:, off:off + C]
+        y = torch.zeros(M, ld, dtype=dtype, device=self.device)[:, off:off + C]
         if init is not None:
             y.copy_(init)
         return y
@@ -952,14 +955,15 @@ class _FramedOperands:
     """Operands of the framed launch: every input and output inside a poisoned frame; ``intact()`` checks the frames of the outputs."""
     framed = True
 
-    def __init__(self):
+    def __init__(self, device=None):
         self.outs = []
+        self.device = DEV if device is None else device
 
     def inp(self, t, flat=False):
         return None if t is None else _framed_like(t, flat)[1]
 
     def out(self, M, C, dtype=torch.float16, init=None, cols=8):
-        buf, view, frame = _framed(M, C, dtype, cols=cols, aligned=cols % 8 == 0)
+        buf, view, frame = _framed(M, C, dtype, cols=cols, aligned=cols % 8 == 0, device=self.device)
         self.outs.append((buf, frame))
         if init is not None:
             view.copy_(init)
@@ -1156,14 +1160,7 @@ def check_attention_forced_rescale():
     scores sit far BELOW the rest (maximum has to climb), far ABOVE the rest (everything after underflows), and scores that
     overflow fp32 exp2 against the old maximum (inf in the check).  Reference: fp32 SDPA on the same fp16 inputs."""
     out = []
-    for name, S, Sk, build in (
-        ("spike at key 70 (2nd tile, 1st step)", 256, 256, lambda q, k: _spike(q, k, [70], 6.0)),
-        ("spikes at keys 5, 200, 255 (every path of a tile)", 256, 256, lambda q, k: _spike(q, k, [5, 200, 255], 5.0)),
-        ("spike in the ragged tail (key 144 of 145)", 128, 145, lambda q, k: _spike(q, k, [144], 6.0)),
-        ("first 16 keys far below the rest", 128, 512, lambda q, k: _shift_first(q, k, -4.0)),
-        ("first 16 keys far above the rest", 128, 512, lambda q, k: _shift_first(q, k, 4.0)),
-        ("exp2 overflow against the old maximum (|s c| ~ 400)", 128, 320, lambda q, k: _spike(q, k, [100, 300], 40.0)),
-    ):
+    for name, S, Sk, build in forced_rescale_specs():
         b, h = 2, 2
         C = 64 * h
         q2 = rnd(b * S, C, scale=1.0, seed=1234)
@@ -1192,6 +1189,19 @@ def check_attention_forced_rescale():
     return out
 
 
+def forced_rescale_specs():
+    """(name, Sq, Sk, what to do to q / k) of ``check_attention_forced_rescale``: b2 h2 on the 4-wave flash kernel, and where Sq == Sk also
+    b3 h2 qk_mod 1 on the shared-softmax 4-wave kernel."""
+    return (
+        ("spike at key 70 (2nd tile, 1st step)", 256, 256, lambda q, k: _spike(q, k, [70], 6.0)),
+        ("spikes at keys 5, 200, 255 (every path of a tile)", 256, 256, lambda q, k: _spike(q, k, [5, 200, 255], 5.0)),
+        ("spike in the ragged tail (key 144 of 145)", 128, 145, lambda q, k: _spike(q, k, [144], 6.0)),
+        ("first 16 keys far below the rest", 128, 512, lambda q, k: _shift_first(q, k, -4.0)),
+        ("first 16 keys far above the rest", 128, 512, lambda q, k: _shift_first(q, k, 4.0)),
+        ("exp2 overflow against the old maximum (|s c| ~ 400)", 128, 320, lambda q, k: _spike(q, k, [100, 300], 40.0)),
+    )
+
+
 def _spike(q, k, keys, gain):
     """k[:, key] := gain * (a query row's direction): that row's score at `key` dwarfs the others (in place, views of fp16)."""
     for n, key in enumerate(keys):
@@ -1204,6 +1214,16 @@ def _shift_first(q, k, gain):
     first keys receive a large common component."""
     q[..., 0] = 6.0
     k[:, :16, :, 0] = gain * 6.0
+
+
+# The rows of ``check_attention`` that name a kernel: "PnP shared-softmax b.. h.. S.." (and its "aliasing form", flag bit3), the "8-wave
+# blocks" rows (and the 4-wave twin, flag bit2) and the "attn[flash] b.. h.. S.. Sk.." KV-loop sweep.  (b, h, S) / (b, h, S, Sk, kv_div, qk_mod)
+ATTN_PNP_SHARED_SHAPES = [(3, 1, 333), (6, 5, 1024), (48, 1, 130)]
+ATTN_8WAVE_SHAPES = {"shared-softmax": (48, 5, 4096), "shared-softmax, ragged": (96, 4, 2100), "plain": (13, 5, 4096)}
+ATTN_FLASH_KV_LOOP_SHAPES = [(2, 1, 20, 3, 1, 0), (2, 2, 130, 17, 1, 0), (1, 1, 33, 63, 1, 0),  # tiny ragged KV: whole steps masked
+                             (2, 1, 128, 64, 1, 0), (2, 2, 128, 128, 1, 0), (4, 1, 256, 145, 2, 0),
+                             (1, 2, 128, 200, 1, 0), (2, 1, 128, 320, 1, 0), (1, 1, 256, 384, 1, 0),
+                             (4, 2, 128, 448, 1, 2), (1, 5, 4096, 4096, 1, 0)]
 
 
 def check_attention(naive_too=True):
@@ -1233,7 +1253,7 @@ def check_attention(naive_too=True):
         out.append(_res(f"attn[{tag}] spatial PnP q/k injection", o, _sdpa(q, k, v).transpose(1, 2).reshape(b * S, C), KTOL))
         # shared-softmax PnP kernel (one S/P per source element, three V streams): ragged and multi-tile shapes, and
         # agreement with the aliasing form of the same launch (flag bit3), which runs the plain kernel per branch
-        for (b, h, S) in [(3, 1, 333), (6, 5, 1024), (48, 1, 130)]:
+        for (b, h, S) in ATTN_PNP_SHARED_SHAPES:
             C = 64 * h
             qkv = rnd(b * S, 3 * C, scale=1.0)
             o = torch.zeros(b * S, C, dtype=torch.float16, device=DEV)
@@ -1255,7 +1275,7 @@ def check_attention(naive_too=True):
         if not naive:
             # the 64x64-level launch itself (48 x 5 x 4096: the 8-wave / 3-stage form of the shared-softmax kernel): against the
             # aliasing form (plain kernel per branch) everywhere, against fp32 SDPA on one (source element, head)
-            b, h, S = 48, 5, 4096
+            b, h, S = ATTN_8WAVE_SHAPES["shared-softmax"]
             C = 64 * h
             qkv = rnd(b * S, 3 * C, scale=1.0, seed=77)
             o = torch.zeros(b * S, C, dtype=torch.float16, device=DEV)
@@ -1269,7 +1289,7 @@ def check_attention(naive_too=True):
                 ops.ATTN_FLAGS = saved
             out.append(_res(f"attn PnP shared-softmax == aliasing form b{b} h{h} S{S} (8-wave blocks)", o, o2.float(), 1e-6))
             # ... and with a ragged last block / last tile on both 8-wave kernels (2100 = 8 x 256 + 52 queries, 32 x 64 + 52 keys)
-            br, hr, Sr = 96, 4, 2100
+            br, hr, Sr = ATTN_8WAVE_SHAPES["shared-softmax, ragged"]
             Cr = 64 * hr
             qkvr = rnd(br * Sr, 3 * Cr, scale=1.0, seed=78)
             kwr = dict(batch=br, heads=hr, Sq=Sr, Sk=Sr, inner=1, q_strides=(Sr, 0, 1), kv_strides=(Sr, 0, 1), qk_mod=br // 3)
@@ -1363,7 +1383,7 @@ def check_attention(naive_too=True):
     out += check_attention_forced_rescale()
     # 8-wave (256-query) blocks: taken for launches with >= 1024 such blocks and Sq, Sk >= 1024; the same launch forced onto
     # 4-wave blocks (flag bit2) must give the same bits (a wave's instruction stream does not depend on the block shape)
-    b, h, S = 13, 5, 4096
+    b, h, S = ATTN_8WAVE_SHAPES["plain"]
     C = 64 * h
     qkv = rnd(b * S, 3 * C, scale=1.0, seed=2024)
     o8 = torch.zeros(b * S, C, dtype=torch.float16, device=DEV)
@@ -1392,10 +1412,7 @@ def check_attention(naive_too=True):
     ref = _sdpa(q, k, v).reshape(B_, HW, h, Fr, 64).permute(0, 3, 1, 2, 4).reshape(B_ * Fr * HW, C)
     out.append(_res("attn[flash] temporal F128 (frame stride)", o, ref, KTOL))
     # every KV-loop length 1 .. 7 tiles with ragged last tiles, shared K/V (kv_div), Q/K aliasing on the plain kernel
-    for (b, h, S, Sk, kv_div, qk_mod) in [(2, 1, 20, 3, 1, 0), (2, 2, 130, 17, 1, 0), (1, 1, 33, 63, 1, 0),  # tiny ragged KV: whole steps masked
-                                           (2, 1, 128, 64, 1, 0), (2, 2, 128, 128, 1, 0), (4, 1, 256, 145, 2, 0),
-                                           (1, 2, 128, 200, 1, 0), (2, 1, 128, 320, 1, 0), (1, 1, 256, 384, 1, 0),
-                                           (4, 2, 128, 448, 1, 2), (1, 5, 4096, 4096, 1, 0)]:
+    for (b, h, S, Sk, kv_div, qk_mod) in ATTN_FLASH_KV_LOOP_SHAPES:
         C = 64 * h
         q2 = rnd(b * S, C, scale=1.0)
         kv = rnd((b // kv_div) * Sk, 2 * C, scale=1.0)
@@ -1428,19 +1445,25 @@ def check_attention(naive_too=True):
 
 
 # ------------------------------------------------------------------------------------------------ CLIP towers (F1)
+def attention_small_mfma_specs():
+    """(B, heads, S, head_dim, causal, kernel) of ``check_attention_small_mfma``'s self-attention rows."""
+    W, L = "whole-sequence MFMA", "96-key loop"
+    # (head_dim 40 / 160: ConsistI2V's temporal attention at C = 320 / 1280 with 8 heads -- not multiples of 16 / five 32-column groups)
+    return [(2, 16, 257, 80, False, W), (3, 16, 77, 64, True, W), (1, 4, 200, 128, False, W), (2, 3, 50, 96, True, W),
+            (1, 2, 288, 64, True, W), (3, 8, 24, 40, False, W), (2, 8, 77, 160, False, W), (5, 8, 16, 160, True, W),
+            (2, 4, 90, 56, False, W),      # (head_dim 64 reaches this entry point with the causal mask only: S288 d64 ran the flash kernel without it)
+            # longer than 288 keys (or 96 at head_dim 160): the 96-key loop kernel with the online softmax -- SEINE's
+            # spatial attention (8 heads x 40 / 80 / 160 over 2560 / 640 / 160 tokens)
+            (1, 8, 2560, 40, False, L), (2, 8, 640, 80, False, L), (3, 8, 160, 160, False, L), (1, 2, 401, 56, True, L),
+            (2, 3, 289, 24, False, L), (1, 4, 1000, 128, True, L)]
+
+
 def check_attention_small_mfma():
     """Whole-sequence MFMA attention of the CLIP towers (``anyv2v_attention_small_f16``: head_dim a multiple of 8 up to 160, Sk <= 288) vs
     fp32 SDPA and vs the one-thread-per-query kernel it replaces: ViT-H/14 (257 tokens, 16 x 80), the text tower (77 tokens, 16 x 64,
     causal), head_dim 128, query counts that are not multiples of the 64-query block, column windows of a fused QKV matrix."""
     out = []
-    # (head_dim 40 / 160: ConsistI2V's temporal attention at C = 320 / 1280 with 8 heads -- not multiples of 16 / five 32-column groups)
-    for (B, h, S, d, causal) in [(2, 16, 257, 80, False), (3, 16, 77, 64, True), (1, 4, 200, 128, False), (2, 3, 50, 96, True),
-                                 (1, 2, 288, 64, False), (3, 8, 24, 40, False), (2, 8, 77, 160, False), (5, 8, 16, 160, True),
-                                 (2, 4, 90, 56, False),
-                                 # longer than 288 keys (or 96 at head_dim 160): the 96-key loop kernel with the online softmax -- SEINE's
-                                 # spatial attention (8 heads x 40 / 80 / 160 over 2560 / 640 / 160 tokens)
-                                 (1, 8, 2560, 40, False), (2, 8, 640, 80, False), (3, 8, 160, 160, False), (1, 2, 401, 56, True),
-                                 (2, 3, 289, 24, False), (1, 4, 1000, 128, True)]:
+    for (B, h, S, d, causal, _kernel) in attention_small_mfma_specs():
         H = h * d
         qkv = rnd(B * S, 3 * H, seed=S + d)
         o = torch.zeros(B * S, H, dtype=torch.float16, device=DEV)
@@ -3276,13 +3299,18 @@ def check_seine_pipeline():
     return out
 
 
+def attention_bias_specs():
+    """(heads, head_dim, frames, instantiation) of ``check_attention_bias_and_rotary_windows``."""
+    return ((3, 40, 6, "small<2,6,bias>"), (8, 80, 16, "small<3,6,bias>"), (8, 160, 16, "small<5,6,bias>"), (2, 20, 5, "naive+bias"))
+
+
 def check_attention_bias_and_rotary_windows():
     """``anyv2v_attention_bias_f16`` (additive score bias [heads, Sq, Sk], frame-strided sequences, qk_mod aliasing) and
     ``anyv2v_rotary_f16`` with one window per head vs PyTorch fp32."""
     out = []
     # (head_dim 40 / 80 / 160, 16 frames: SEINE's temporal attention at the released width -- the whole-sequence MFMA kernel with the
     # bias added to the score fragments; head_dim 20: the one-thread-per-query kernel)
-    for (heads, D, Fr) in ((3, 40, 6), (8, 80, 16), (8, 160, 16), (2, 20, 5)):
+    for (heads, D, Fr, _inst) in attention_bias_specs():
         B, HW = 3, 10
         C = heads * D
         qkv = rnd(B * Fr * HW, 3 * C, seed=D)
@@ -3633,41 +3661,169 @@ def _attn_operand(f, t):
     if not f.framed:
         return t
     M, Wd = t.shape
-    buf = torch.full((M + 128, Wd + 16), POISON16, dtype=torch.int16, device=DEV)
+    buf = torch.full((M + 128, Wd + 16), POISON16, dtype=torch.int16, device=t.device)
     view = buf.view(torch.float16)[64:64 + M, :Wd]
     view.copy_(t)
     return view
 
 
-def _attn_edge(name, *, batch, heads, Sq, Sk, d=64, inner=1, q_strides=None, kv_strides=None, kv_div=1, qk_mod=0, causal=False,
-               bias=None, naive=False, seed=0, tol=KTOL):
-    """One attention edge case.  Self-attention shapes read Q / K / V from one fused matrix [rows, 3 C]; the others Q from [rows, C] and
-    K / V from [kv rows, 2 C].  O is a framed [rows, C] window (8 guard columns each side, guard rows)."""
-    C = heads * d
-    q_strides = (Sq, 0, 1) if q_strides is None else q_strides
-    kv_strides = (Sk, 0, 1) if kv_strides is None else kv_strides
-    Mq = int(_attn_rows_of(batch, Sq, inner, q_strides).max()) + 1
-    Mk = int(_attn_rows_of((batch + kv_div - 1) // kv_div, Sk, inner, kv_strides).max()) + 1
-    fused = Mq == Mk and kv_div == 1 and q_strides == kv_strides
-    if fused:
-        qkv = rnd(Mq, 3 * C, seed=seed + 1)
-        srcs = lambda f: (lambda t: (t[:, :C], t[:, C:2 * C], t[:, 2 * C:]))(_attn_operand(f, qkv))
-        q2, k2, v2 = qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:]
+def attn_plan_words(q, k, v, o, *, batch, heads, Sq, Sk, inner=1, q_strides, kv_strides, kv_div=1, qk_mod=0, scale=0.125, head_dim=64,
+                    naive=False, causal=False, bias=None, flags=0):
+    """The launch ``ops.attention(q, k, v, o, ...)`` makes, as a line for tests/attention_plan_main.cpp: the entry point, the leading
+    dimensions and the operands' addresses modulo 16 (their offset in an allocation, which starts 16-byte aligned), read from the tensors
+    themselves -- on any device, "meta" included.  ``bias``: anything but None / False stands for a bias tensor."""
+    res = lambda t: (t.storage_offset() * t.element_size()) % 16
+    for t in (q, k, v, o):
+        assert t.dim() == 2 and t.stride(1) == 1
+    has_bias = bias is not None and bias is not False
+    fl = (1 if (naive or ops.FORCE_NAIVE) else 0) | ops.ATTN_FLAGS | flags | (16 if causal else 0)
+    return (f"entry={ops.attention_entry(head_dim, causal, has_bias)} head_dim={head_dim} bias={int(has_bias)} batch={batch} heads={heads} Sq={Sq} Sk={Sk} "
+            f"inner={inner} q_outer={q_strides[0]} q_inner={q_strides[1]} q_seq={q_strides[2]} kv_outer={kv_strides[0]} kv_inner={kv_strides[1]} "
+            f"kv_seq={kv_strides[2]} kv_div={kv_div} qk_mod={qk_mod} scale_milli={max(1, round(scale * 1000))} flags={fl} "
+            f"ldq={q.stride(0)} ldk={k.stride(0)} ldv={v.stride(0)} ldo={o.stride(0)} Q={res(q)} K={res(k)} V={res(v)} O={res(o)}")
+
+
+# What the planner (anyv2v_amd/csrc/attention_plan.cpp: av_attn_kernel_name) may answer for a launch that a check names by kernel:
+# tests/test_attention_plan_host.py plans every named launch of this file and fails when a name and a plan disagree.
+ATTN_KERNEL_INSTANTIATIONS = {
+    "4-wave flash": ("flash<2,1,4>",), "short one-wave": ("short<1>", "short<3>"), "short one-wave PnP": ("short<3>",),
+    "shared-softmax 4-wave": ("flash<2,3,4>",), "8-wave": ("flash<3,1,8>", "flash<3,3,8>"), "shared-softmax 8-wave": ("flash<3,3,8>",),
+    "whole-sequence MFMA": ("small<2,6>", "small<3,6>", "small<4,6>", "small<5,6>", "small<2,18>", "small<3,18>", "small<4,18>"),
+    "96-key loop": ("loop<2>", "loop<3>", "loop<4>", "loop<5>"),
+    "bias": ("small<2,6,bias>", "small<3,6,bias>", "small<4,6,bias>", "small<5,6,bias>", "naive+bias"), "generic": ("naive",),
+    "64-bit fallback": ("loop<2>",),
+}
+
+
+def _ae(name, kernel, instantiation, *, batch, heads, Sq, Sk, d=64, inner=1, q_strides=None, kv_strides=None, kv_div=1, qk_mod=0, causal=False,
+        bias=None, naive=False, seed=0, flags=0, tol=KTOL):
+    """One attention edge case: ``kernel`` as the row's tag names it, ``instantiation`` as the planner names it; ``bias`` = the seed of a bias."""
+    return dict(name=name, kernel=kernel, instantiation=instantiation, batch=batch, heads=heads, Sq=Sq, Sk=Sk, d=d, inner=inner,
+                q_strides=(Sq, 0, 1) if q_strides is None else q_strides, kv_strides=(Sk, 0, 1) if kv_strides is None else kv_strides,
+                kv_div=kv_div, qk_mod=qk_mod, causal=causal, bias=bias, naive=naive, seed=seed, flags=flags, tol=tol)
+
+
+def _attn_edge_kw(spec):
+    kw = {key: spec[key] for key in ("batch", "heads", "Sq", "Sk", "inner", "q_strides", "kv_strides", "kv_div", "qk_mod")}
+    d, causal = spec["d"], spec["causal"]
+    extra = {} if d == 64 and not causal and spec["bias"] is None else dict(scale=d ** -0.5, head_dim=d, causal=causal)
+    return kw, extra
+
+
+def _attn_edge_sources(spec, device=None):
+    """The source matrices of an edge case.  Self-attention shapes read Q / K / V from one fused matrix [rows, 3 C]; the others Q from
+    [rows, C] and K / V from [kv rows, 2 C].  -> (Mq, mats, windows): ``windows(f)`` = the (q, k, v) column windows of the matrices as the
+    operands ``f`` hold them.  On the device "meta" the matrices carry no data, the windows the same layout."""
+    C = spec["heads"] * spec["d"]
+    Mq = int(_xa_rows(spec["batch"], spec["Sq"], spec["inner"], spec["q_strides"]).max()) + 1
+    Mk = int(_xa_rows((spec["batch"] + spec["kv_div"] - 1) // spec["kv_div"], spec["Sk"], spec["inner"], spec["kv_strides"]).max()) + 1
+    seed = spec["seed"]
+    mat = lambda M, W, sd: rnd(M, W, seed=sd) if device is None else torch.empty(M, W, dtype=torch.float16, device=device)
+    if Mq == Mk and spec["kv_div"] == 1 and spec["q_strides"] == spec["kv_strides"]:
+        mats = (mat(Mq, 3 * C, seed + 1),)
+        windows = lambda f: (lambda t: (t[:, :C], t[:, C:2 * C], t[:, 2 * C:]))(_attn_operand(f, mats[0]))
     else:
-        qm, kv = rnd(Mq, C, seed=seed + 1), rnd(Mk, 2 * C, seed=seed + 2)
-        srcs = lambda f: (lambda a, b: (a, b[:, :C], b[:, C:]))(_attn_operand(f, qm), _attn_operand(f, kv))
-        q2, k2, v2 = qm, kv[:, :C], kv[:, C:]
-    kw = dict(batch=batch, heads=heads, Sq=Sq, Sk=Sk, inner=inner, q_strides=q_strides, kv_strides=kv_strides, kv_div=kv_div, qk_mod=qk_mod)
-    rows, ref = _attn_ref(q2, k2, v2, d=d, causal=causal, bias=bias, **kw)
+        mats = (mat(Mq, C, seed + 1), mat(Mk, 2 * C, seed + 2))
+        windows = lambda f: (lambda a, b: (a, b[:, :C], b[:, C:]))(_attn_operand(f, mats[0]), _attn_operand(f, mats[1]))
+    return Mq, mats, windows
+
+
+def _attn_edge_bias(spec):
+    if spec["bias"] is None:
+        return None
+    return torch.randn(spec["heads"], spec["Sq"], spec["Sk"], generator=torch.Generator().manual_seed(spec["bias"])).to(DEV)
+
+
+def _attn_edge(spec):
+    """One attention edge case (``_ae``).  O is a framed [rows, C] window (8 guard columns each side, guard rows)."""
+    C = spec["heads"] * spec["d"]
+    Mq, mats, windows = _attn_edge_sources(spec)
+    q2, k2, v2 = windows(_PlainOperands())
+    kw, extra = _attn_edge_kw(spec)
+    bias = _attn_edge_bias(spec)
+    rows, ref = _attn_ref(q2, k2, v2, d=spec["d"], causal=spec["causal"], bias=bias, **kw)
     want = torch.zeros(Mq, C, device=DEV)
     want[rows] = ref
-    extra = {} if d == 64 and not causal and bias is None else dict(scale=d ** -0.5, head_dim=d, causal=causal)
 
     def run(f):
-        q, k, v = srcs(f)
+        q, k, v = windows(f)
         o = f.out(Mq, C, init=torch.zeros(Mq, C, dtype=torch.float16, device=DEV))
-        return ops.attention(q, k, v, o, naive=naive, bias=None if bias is None else f.inp(bias, flat=True), **kw, **extra)
-    return _edge_rows(name, run, want, tol)
+        saved, ops.ATTN_FLAGS = ops.ATTN_FLAGS, ops.ATTN_FLAGS | spec["flags"]
+        try:
+            return ops.attention(q, k, v, o, naive=spec["naive"], bias=None if bias is None else f.inp(bias, flat=True), **kw, **extra)
+        finally:
+            ops.ATTN_FLAGS = saved
+    return _edge_rows(spec["name"], run, want, spec["tol"])
+
+
+def attention_edge_specs():
+    """The cases of ``check_edges_attention`` / ``check_edges_attention_8wave`` / ``check_edges_attention_small``, in their order:
+    -> dict(flash=[...], wave8=[...], small=[...]) of ``_ae`` specs."""
+    E = dict(flash=[], wave8=[], small=[])
+    for (b, h, Sq, Sk) in [(2, 2, 130, 145), (2, 1, 20, 3), (1, 1, 33, 63)]:
+        E["flash"].append(_ae(f"edge attn[flash] b{b} h{h} Sq{Sq} Sk{Sk}", "4-wave flash", "flash<2,1,4>", batch=b, heads=h, Sq=Sq, Sk=Sk, seed=Sq))
+    E["flash"].append(_ae("edge attn[flash] b4 h1 Sq256 Sk145 kv_div2", "4-wave flash", "flash<2,1,4>", batch=4, heads=1, Sq=256, Sk=145, kv_div=2, seed=5))
+    for flag in (0, 8):
+        E["flash"].append(_ae("edge attn PnP b3 h1 S130 " + ("shared-softmax kernel" if not flag else "aliasing form (flag bit3)"),
+                              "shared-softmax 4-wave" if not flag else "4-wave flash", "flash<2,3,4>" if not flag else "flash<2,1,4>",
+                              batch=3, heads=1, Sq=130, Sk=130, qk_mod=1, seed=6, flags=flag))
+    B_, HW, h = 3, 20, 2
+    for Fr in (8, 16, 40):
+        for inj in (False, True):
+            st = (Fr * HW, 1, HW)
+            kernel, inst = ("short one-wave", "short<3>" if inj else "short<1>") if Fr <= 16 else \
+                (("shared-softmax 4-wave", "flash<2,3,4>") if inj else ("4-wave flash", "flash<2,1,4>"))
+            E["flash"].append(_ae(f"edge attn temporal F{Fr} inject={inj}", kernel, inst, batch=B_ * HW, heads=h, Sq=Fr, Sk=Fr, inner=HW, q_strides=st,
+                                  kv_strides=st, qk_mod=HW if inj else 0, seed=Fr))
+    # 8-wave (256-query) blocks: b29 h4 S2100 gives 1044 blocks; the shared-softmax form needs qk_mod x heads x 9 >= 1024 of them
+    E["wave8"].append(_ae("edge attn[flash, 8-wave blocks] b29 h4 S2100", "8-wave", "flash<3,1,8>", batch=29, heads=4, Sq=2100, Sk=2100, seed=2099))
+    E["wave8"].append(_ae("edge attn[shared softmax, 8-wave blocks] b87 h4 S2100 qk_mod29", "shared-softmax 8-wave", "flash<3,3,8>", batch=87, heads=4,
+                          Sq=2100, Sk=2100, qk_mod=29, seed=2199))
+    sm = lambda tag, kernel, inst, B, h, S, d, causal: _ae(f"edge attention[{tag}] B{B} h{h} S{S} d{d} causal={causal}", kernel, inst, batch=B, heads=h, Sq=S,
+                                                           Sk=S, d=d, causal=causal, seed=S + d)
+    W, L = "whole-sequence MFMA", "96-key loop"
+    for (B, h, S, d, causal, inst) in [(3, 8, 24, 40, False, "small<2,6>"), (3, 16, 77, 64, True, "small<2,6>"), (2, 4, 90, 56, False, "small<2,6>"),
+                                       (2, 8, 77, 160, False, "small<5,6>"),
+                                       # every other instantiation, at the smallest ragged shapes and on both edges of the 96 / 288-key thresholds
+                                       (2, 2, 50, 80, False, "small<3,6>"), (2, 2, 90, 128, True, "small<4,6>"), (2, 2, 97, 56, False, "small<2,18>"),
+                                       (2, 3, 257, 80, False, "small<3,18>"), (2, 2, 288, 104, False, "small<4,18>")]:
+        E["small"].append(sm("small mfma", W, inst, B, h, S, d, causal))
+    for (B, h, S, d, causal, inst) in [(2, 3, 289, 24, False, "loop<2>"), (1, 2, 401, 56, True, "loop<2>"),
+                                       (1, 2, 289, 72, False, "loop<3>"), (1, 2, 289, 128, True, "loop<4>"), (2, 2, 97, 160, False, "loop<5>")]:
+        E["small"].append(sm("small loop", L, inst, B, h, S, d, causal))
+    # head_dim 24 up to 288 keys: neither MFMA kernel (one 32-column group) -> one thread per query
+    E["small"].append(_ae("edge attention one thread per query, B2 h3 S288 d24", "generic", "naive", batch=2, heads=3, Sq=288, Sk=288, d=24, seed=312))
+    for (B, h, Sq, Sk, d, inst) in [(2, 3, 20, 24, 40, "small<2,6,bias>"), (2, 2, 33, 130, 40, "naive+bias"),
+                                    # the MFMA form at exactly 96 keys on every instantiation, the generic kernel one key later
+                                    (2, 2, 100, 96, 40, "small<2,6,bias>"), (2, 2, 100, 96, 80, "small<3,6,bias>"), (2, 2, 100, 96, 128, "small<4,6,bias>"),
+                                    (2, 2, 100, 96, 160, "small<5,6,bias>"), (2, 2, 100, 97, 40, "naive+bias")]:
+        E["small"].append(_ae(f"edge attention + score bias B{B} h{h} Sq{Sq} Sk{Sk} d{d}", "bias", inst, batch=B, heads=h, Sq=Sq, Sk=Sk, d=d, bias=Sk,
+                              seed=Sk))
+    B_, Fr, HW, h, d = 2, 6, 10, 2, 4
+    st = (Fr * HW, 1, HW)
+    E["small"].append(_ae("edge attention one thread per query, head_dim 4 (temporal layout)", "generic", "naive", batch=B_ * HW, heads=h, Sq=Fr, Sk=Fr,
+                          d=d, inner=HW, q_strides=st, kv_strides=st, seed=4))
+    return E
+
+
+def attention_edge_plan_rows():
+    """(row name, line for tests/attention_plan_main.cpp, kernel named, instantiation named) of every launch of the attention edge checks:
+    the plain and the framed launch of each case (and the 8-wave cases' flag-bit2 twin), from the layout code of the launches."""
+    rows = []
+    for group, specs in attention_edge_specs().items():
+        for spec in specs:
+            Mq, _mats, windows = _attn_edge_sources(spec, device="meta")
+            kw, extra = _attn_edge_kw(spec)
+            for f in (_PlainOperands("meta"), _FramedOperands("meta")):
+                q, k, v = windows(f)
+                o = f.out(Mq, spec["heads"] * spec["d"])
+                words = lambda fl: attn_plan_words(q, k, v, o, naive=spec["naive"], bias=spec["bias"], flags=fl, **kw, **extra)
+                tag = f"{spec['name']} | {'framed' if f.framed else 'plain'}"
+                rows.append((tag, words(spec["flags"]), spec["kernel"], spec["instantiation"]))
+                if group == "wave8" and f.framed:
+                    four = {"flash<3,1,8>": ("4-wave flash", "flash<2,1,4>"), "flash<3,3,8>": ("shared-softmax 4-wave", "flash<2,3,4>")}[spec["instantiation"]]
+                    rows.append((tag + " | flag bit2", words(spec["flags"] | 4)) + four)
+    return rows
 
 
 def check_edges_attention():
@@ -3675,72 +3831,54 @@ def check_edges_attention():
     shared-softmax kernel and its aliasing form (flag bit3), the temporal layout through the short one-wave kernel (F <= 16) and the
     flash kernel (F = 40)."""
     out = []
-    for (b, h, Sq, Sk) in [(2, 2, 130, 145), (2, 1, 20, 3), (1, 1, 33, 63)]:
-        out += _attn_edge(f"edge attn[flash] b{b} h{h} Sq{Sq} Sk{Sk}", batch=b, heads=h, Sq=Sq, Sk=Sk, seed=Sq)
-    out += _attn_edge("edge attn[flash] b4 h1 Sq256 Sk145 kv_div2", batch=4, heads=1, Sq=256, Sk=145, kv_div=2, seed=5)
-    for flag in (0, 8):
-        saved, ops.ATTN_FLAGS = ops.ATTN_FLAGS, ops.ATTN_FLAGS | flag
-        try:
-            out += _attn_edge("edge attn PnP b3 h1 S130 " + ("shared-softmax kernel" if not flag else "aliasing form (flag bit3)"),
-                              batch=3, heads=1, Sq=130, Sk=130, qk_mod=1, seed=6)
-        finally:
-            ops.ATTN_FLAGS = saved
-    B_, HW, h = 3, 20, 2
-    for Fr in (8, 16, 40):
-        for inj in (False, True):
-            st = (Fr * HW, 1, HW)
-            out += _attn_edge(f"edge attn temporal F{Fr} inject={inj}", batch=B_ * HW, heads=h, Sq=Fr, Sk=Fr, inner=HW, q_strides=st,
-                              kv_strides=st, qk_mod=HW if inj else 0, seed=Fr)
+    for spec in attention_edge_specs()["flash"]:
+        out += _attn_edge(spec)
     return out
 
 
 def check_edges_attention_8wave():
-    """8-wave (256-query) blocks of the flash kernel: b29 h4 S2100 gives 1044 blocks, a ragged last block (52 queries) and a ragged last
-    key tile.  Framed against plain (bit-equal), framed against the 4-wave form (flag bit2, 1e-6), fp32 SDPA on two (batch, head) pairs."""
+    """8-wave (256-query) blocks of the flash kernel, plain and shared-softmax (three V / O streams): b29 h4 S2100 gives 1044 blocks, a
+    ragged last block (52 queries) and a ragged last key tile.  Framed against plain (bit-equal), framed against the 4-wave form (flag
+    bit2, 1e-6), fp32 SDPA on two batch elements (every head)."""
     out = []
-    b, h, S = 29, 4, 2100
-    C = 64 * h
-    qkv = rnd(b * S, 3 * C, seed=2100)
-    kw = dict(batch=b, heads=h, Sq=S, Sk=S, inner=1, q_strides=(S, 0, 1), kv_strides=(S, 0, 1))
-    name = f"edge attn[flash, 8-wave blocks] b{b} h{h} S{S}"
+    for spec in attention_edge_specs()["wave8"]:
+        b, h, S = spec["batch"], spec["heads"], spec["Sq"]
+        C = 64 * h
+        Mq, mats, windows = _attn_edge_sources(spec)
+        kw, extra = _attn_edge_kw(spec)
+        name = spec["name"]
 
-    def launch(f):
-        t = _attn_operand(f, qkv)
-        return ops.attention(t[:, :C], t[:, C:2 * C], t[:, 2 * C:], f.out(b * S, C), **kw)
-    yp = launch(_PlainOperands())
-    fr = _FramedOperands()
-    yf = launch(fr)
-    saved, ops.ATTN_FLAGS = ops.ATTN_FLAGS, ops.ATTN_FLAGS | 4
-    try:
-        y4 = launch(_FramedOperands())
-    finally:
-        ops.ATTN_FLAGS = saved
-    torch.cuda.synchronize()
-    for (i, hh) in [(0, 0), (28, 3)]:
-        q, k, v = (qkv[i * S:(i + 1) * S, j * C + 64 * hh:j * C + 64 * hh + 64][None, None] for j in range(3))
-        out.append(_res(f"{name}: framed, element {i} head {hh} vs fp32 SDPA", yf[i * S:(i + 1) * S, 64 * hh:64 * hh + 64], _sdpa(q, k, v)[0, 0], KTOL))
-    out.append(_res(f"{name}: framed == 4-wave blocks (flag bit2), framed", yf, y4.float(), 1e-6))
-    same, intact = bool(torch.equal(yf, yp)), fr.intact()
-    out.append(dict(name=f"{name}: framed == plain, bit for bit", err=0.0 if same else 1.0, tol=0.0, ok=same))
-    out.append(dict(name=f"{name}: frames of the outputs intact", err=0.0 if intact else 1.0, tol=0.0, ok=intact))
+        def launch(f):
+            q, k, v = windows(f)
+            return ops.attention(q, k, v, f.out(b * S, C), **kw, **extra)
+        yp = launch(_PlainOperands())
+        fr = _FramedOperands()
+        yf = launch(fr)
+        saved, ops.ATTN_FLAGS = ops.ATTN_FLAGS, ops.ATTN_FLAGS | 4
+        try:
+            y4 = launch(_FramedOperands())
+        finally:
+            ops.ATTN_FLAGS = saved
+        torch.cuda.synchronize()
+        q2, k2, v2 = windows(_PlainOperands())
+        for i in (0, b - 1):
+            rows, ref = _attn_ref(q2, k2, v2, only=[i], **kw)
+            out.append(_res(f"{name}: framed, element {i} vs fp32 SDPA", yf[rows], ref, KTOL))
+        out.append(_res(f"{name}: framed == 4-wave blocks (flag bit2), framed", yf, y4.float(), 1e-6))
+        same, intact = bool(torch.equal(yf, yp)), fr.intact()
+        out.append(dict(name=f"{name}: framed == plain, bit for bit", err=0.0 if same else 1.0, tol=0.0, ok=same))
+        out.append(dict(name=f"{name}: frames of the outputs intact", err=0.0 if intact else 1.0, tol=0.0, ok=intact))
+        del yp, yf, y4, fr, mats, windows, q2, k2, v2
     return out
 
 
 def check_edges_attention_small():
-    """``anyv2v_attention_small_f16``: the whole-sequence MFMA kernel, the 96-key loop kernel, the one-thread-per-query kernel (head_dim 4),
-    and the bias entry point on its MFMA (Sk <= 96) and generic (Sk = 130) kernels with the fp32 bias framed."""
+    """``anyv2v_attention_small_f16``: every instantiation of the whole-sequence MFMA kernel and of the 96-key loop kernel, the
+    one-thread-per-query kernel (head_dim 4; head_dim 24 at 288 keys), and the bias entry point on every MFMA instantiation (Sk <= 96)
+    and on the generic kernel (Sk = 97, 130) with the fp32 bias framed."""
     out = []
-    for (B, h, S, d, causal) in [(3, 8, 24, 40, False), (3, 16, 77, 64, True), (2, 4, 90, 56, False), (2, 8, 77, 160, False)]:
-        out += _attn_edge(f"edge attention[small mfma] B{B} h{h} S{S} d{d} causal={causal}", batch=B, heads=h, Sq=S, Sk=S, d=d, causal=causal, seed=S + d)
-    for (B, h, S, d, causal) in [(2, 3, 289, 24, False), (1, 2, 401, 56, True)]:
-        out += _attn_edge(f"edge attention[small loop] B{B} h{h} S{S} d{d} causal={causal}", batch=B, heads=h, Sq=S, Sk=S, d=d, causal=causal, seed=S + d)
-    for (B, h, Sq, Sk, d) in [(2, 3, 20, 24, 40), (2, 2, 33, 130, 40)]:
-        bias = torch.randn(h, Sq, Sk, generator=torch.Generator().manual_seed(Sk)).to(DEV)
-        out += _attn_edge(f"edge attention + score bias B{B} h{h} Sq{Sq} Sk{Sk} d{d}", batch=B, heads=h, Sq=Sq, Sk=Sk, d=d, bias=bias, seed=Sk)
-    B_, Fr, HW, h, d = 2, 6, 10, 2, 4
-    st = (Fr * HW, 1, HW)
-    out += _attn_edge("edge attention one thread per query, head_dim 4 (temporal layout)", batch=B_ * HW, heads=h, Sq=Fr, Sk=Fr, d=d, inner=HW,
-                      q_strides=st, kv_strides=st, seed=4)
+    for spec in attention_edge_specs()["small"]:
+        out += _attn_edge(spec)
     return out
 
 
@@ -4206,9 +4344,9 @@ def _xa_rows(batch, S, inner, strides):
     return ((i // inner) * outer + (i % inner) * inner_s)[:, None] + torch.arange(S)[None] * seq   # [batch, S]
 
 
-def _xa(name, kernel, *, batch, heads, Sq, Sk, d=64, inner=1, q_strides=None, kv_strides=None, kv_div=1, qk_mod=0, causal=False,
+def _xa(name, kernel, instantiation, *, batch, heads, Sq, Sk, d=64, inner=1, q_strides=None, kv_strides=None, kv_div=1, qk_mod=0, causal=False,
         bias=False, naive=False, seed=0):
-    return dict(name=name, kernel=kernel, batch=batch, heads=heads, Sq=Sq, Sk=Sk, d=d, inner=inner,
+    return dict(name=name, kernel=kernel, instantiation=instantiation, batch=batch, heads=heads, Sq=Sq, Sk=Sk, d=d, inner=inner,
                 q_strides=(Sq, 0, 1) if q_strides is None else q_strides, kv_strides=(Sk, 0, 1) if kv_strides is None else kv_strides,
                 kv_div=kv_div, qk_mod=qk_mod, causal=causal, bias=bias, naive=naive, seed=seed)
 
@@ -4217,29 +4355,43 @@ XA_KERNELS = ("4-wave flash", "short one-wave", "shared-softmax 4-wave", "8-wave
 
 
 def exact_attention_specs():
-    """The smallest shapes that reach each kernel of attention.hip (dispatch: anyv2v_attention_f16 / _small_f16 / _bias_f16)."""
+    """The smallest shapes that reach each kernel of attention.hip, and each of its template instantiations (dispatch:
+    anyv2v_amd/csrc/attention_plan.cpp; ``instantiation`` is the planner's name of what the launch runs -- tests/test_attention_plan_host.py
+    plans every spec and holds the union against the planner's own list)."""
     S = []
     t = lambda Fr, HW: dict(inner=HW, q_strides=(Fr * HW, 1, HW), kv_strides=(Fr * HW, 1, HW))   # temporal: a sequence's rows HW apart
-    S.append(_xa("b2 h2 S333", "4-wave flash", batch=2, heads=2, Sq=333, Sk=333, seed=1))
-    S.append(_xa("cross b6 h2 Sq100 Sk145 kv_div3", "4-wave flash", batch=6, heads=2, Sq=100, Sk=145, kv_div=3, seed=2))
-    S.append(_xa("temporal F40 (3 x 20 px) h2", "4-wave flash", batch=60, heads=2, Sq=40, Sk=40, seed=3, **t(40, 20)))
+    S.append(_xa("b2 h2 S333", "4-wave flash", "flash<2,1,4>", batch=2, heads=2, Sq=333, Sk=333, seed=1))
+    S.append(_xa("cross b6 h2 Sq100 Sk145 kv_div3", "4-wave flash", "flash<2,1,4>", batch=6, heads=2, Sq=100, Sk=145, kv_div=3, seed=2))
+    S.append(_xa("temporal F40 (3 x 20 px) h2", "4-wave flash", "flash<2,1,4>", batch=60, heads=2, Sq=40, Sk=40, seed=3, **t(40, 20)))
     for Fr in (16, 8):
-        S.append(_xa(f"temporal F{Fr} (3 x 20 px) h2", "short one-wave", batch=60, heads=2, Sq=Fr, Sk=Fr, seed=4 + Fr, **t(Fr, 20)))
-        S.append(_xa(f"temporal F{Fr} (3 x 20 px) h2 qk_mod (three streams)", "short one-wave", batch=60, heads=2, Sq=Fr, Sk=Fr, qk_mod=20,
+        S.append(_xa(f"temporal F{Fr} (3 x 20 px) h2", "short one-wave", "short<1>", batch=60, heads=2, Sq=Fr, Sk=Fr, seed=4 + Fr, **t(Fr, 20)))
+        S.append(_xa(f"temporal F{Fr} (3 x 20 px) h2 qk_mod (three streams)", "short one-wave", "short<3>", batch=60, heads=2, Sq=Fr, Sk=Fr, qk_mod=20,
                      seed=5 + Fr, **t(Fr, 20)))
-    S.append(_xa("b3 h1 S333 qk_mod1 (three streams)", "shared-softmax 4-wave", batch=3, heads=1, Sq=333, Sk=333, qk_mod=1, seed=30))
-    S.append(_xa("plain b64 h4 Sq1024 Sk2100 kv_div64", "8-wave", batch=64, heads=4, Sq=1024, Sk=2100, kv_div=64, seed=31))
-    S.append(_xa("shared-softmax b96 h4 S2100 qk_mod32", "8-wave", batch=96, heads=4, Sq=2100, Sk=2100, qk_mod=32, seed=32))
-    for (B, h, Sn, d, causal) in [(2, 3, 257, 80, False), (2, 2, 77, 160, False), (3, 8, 24, 40, False), (3, 4, 77, 64, True)]:
-        S.append(_xa(f"B{B} h{h} S{Sn} d{d} causal={causal}", "whole-sequence MFMA", batch=B, heads=h, Sq=Sn, Sk=Sn, d=d, causal=causal, seed=Sn + d))
-    for (B, h, Sn, d, causal) in [(2, 2, 401, 40, False), (2, 2, 160, 160, False), (1, 2, 401, 56, True)]:
-        S.append(_xa(f"B{B} h{h} S{Sn} d{d} causal={causal}", "96-key loop", batch=B, heads=h, Sq=Sn, Sk=Sn, d=d, causal=causal, seed=Sn + d + 1))
-    S.append(_xa("8 x 80, 16 frames (2 x 6 px): MFMA form", "bias", batch=12, heads=8, Sq=16, Sk=16, d=80, bias=True, seed=40, **t(16, 6)))
-    S.append(_xa("2 x 20, 5 frames (2 x 6 px): generic kernel", "bias", batch=12, heads=2, Sq=5, Sk=5, d=20, bias=True, seed=41, **t(5, 6)))
-    S.append(_xa("naive=True b2 h2 S333", "generic", batch=2, heads=2, Sq=333, Sk=333, naive=True, seed=1))
-    S.append(_xa("naive=True B3 h8 S24 d40", "generic", batch=3, heads=8, Sq=24, Sk=24, d=40, naive=True, seed=64))
-    S.append(_xa("naive=True B3 h4 S77 d64 causal", "generic", batch=3, heads=4, Sq=77, Sk=77, d=64, causal=True, naive=True, seed=141))
+    S.append(_xa("b3 h1 S333 qk_mod1 (three streams)", "shared-softmax 4-wave", "flash<2,3,4>", batch=3, heads=1, Sq=333, Sk=333, qk_mod=1, seed=30))
+    S.append(_xa("plain b64 h4 Sq1024 Sk2100 kv_div64", "8-wave", "flash<3,1,8>", batch=64, heads=4, Sq=1024, Sk=2100, kv_div=64, seed=31))
+    S.append(_xa("shared-softmax b96 h4 S2100 qk_mod32", "8-wave", "flash<3,3,8>", batch=96, heads=4, Sq=2100, Sk=2100, qk_mod=32, seed=32))
+    for (B, h, Sn, d, causal, inst) in [(2, 3, 257, 80, False, "small<3,18>"), (2, 2, 77, 160, False, "small<5,6>"), (3, 8, 24, 40, False, "small<2,6>"),
+                                        (3, 4, 77, 64, True, "small<2,6>"),
+                                        # the other instantiations: ragged query blocks and key tails below 96 keys, both edges of 97 .. 288 keys
+                                        (2, 2, 50, 80, False, "small<3,6>"), (2, 2, 90, 128, True, "small<4,6>"), (2, 2, 97, 56, False, "small<2,18>"),
+                                        (2, 2, 288, 104, False, "small<4,18>")]:
+        S.append(_xa(f"B{B} h{h} S{Sn} d{d} causal={causal}", "whole-sequence MFMA", inst, batch=B, heads=h, Sq=Sn, Sk=Sn, d=d, causal=causal, seed=Sn + d))
+    for (B, h, Sn, d, causal, inst) in [(2, 2, 401, 40, False, "loop<2>"), (2, 2, 160, 160, False, "loop<5>"), (1, 2, 401, 56, True, "loop<2>"),
+                                        # just past 288 keys (97 at head_dim 160); head_dim 24 runs the loop kernel from 289 keys on
+                                        (1, 2, 289, 72, False, "loop<3>"), (1, 2, 289, 128, True, "loop<4>"), (2, 2, 97, 160, False, "loop<5>"),
+                                        (2, 3, 289, 24, False, "loop<2>")]:
+        S.append(_xa(f"B{B} h{h} S{Sn} d{d} causal={causal}", "96-key loop", inst, batch=B, heads=h, Sq=Sn, Sk=Sn, d=d, causal=causal, seed=Sn + d + 1))
+    S.append(_xa("8 x 80, 16 frames (2 x 6 px): MFMA form", "bias", "small<3,6,bias>", batch=12, heads=8, Sq=16, Sk=16, d=80, bias=True, seed=40, **t(16, 6)))
+    S.append(_xa("2 x 20, 5 frames (2 x 6 px): generic kernel", "bias", "naive+bias", batch=12, heads=2, Sq=5, Sk=5, d=20, bias=True, seed=41, **t(5, 6)))
+    for d, inst in ((40, "small<2,6,bias>"), (128, "small<4,6,bias>"), (160, "small<5,6,bias>")):    # the MFMA form's last key count
+        S.append(_xa(f"b2 h2 Sq100 Sk96 d{d}: MFMA form", "bias", inst, batch=2, heads=2, Sq=100, Sk=96, d=d, bias=True, seed=42 + d))
+    S.append(_xa("b2 h2 Sq100 Sk97 d40: generic kernel", "bias", "naive+bias", batch=2, heads=2, Sq=100, Sk=97, d=40, bias=True, seed=43))
+    S.append(_xa("naive=True b2 h2 S333", "generic", "naive", batch=2, heads=2, Sq=333, Sk=333, naive=True, seed=1))
+    S.append(_xa("naive=True B3 h8 S24 d40", "generic", "naive", batch=3, heads=8, Sq=24, Sk=24, d=40, naive=True, seed=64))
+    S.append(_xa("naive=True B3 h4 S77 d64 causal", "generic", "naive", batch=3, heads=4, Sq=77, Sk=77, d=64, causal=True, naive=True, seed=141))
+    S.append(_xa("B2 h3 S288 d24 (one 32-column group, <= 288 keys)", "generic", "naive", batch=2, heads=3, Sq=288, Sk=288, d=24, seed=312))
     assert len({s["name"] + s["kernel"] for s in S}) == len(S) and {s["kernel"] for s in S} == set(XA_KERNELS)
+    assert all(s["instantiation"] in ATTN_KERNEL_INSTANTIATIONS[s["kernel"]] for s in S)
     return S
 
 
@@ -4356,23 +4508,48 @@ def exact_attention_bad(case, got):
     return torch.where(want == 0, got != 0, (_fp16_ulps(got, want) > 1) | (got == 0))
 
 
-def _xa_launch(case):
-    spec = case["spec"]
-    h, d = spec["heads"], spec["d"]
-    C = h * d
-    q, k, v = case["q"], case["k"], case["v"]
-    if q.shape[0] == k.shape[0] and spec["kv_div"] == 1 and spec["q_strides"] == spec["kv_strides"]:
-        t = torch.cat([q, k, v], 1).to(DEV)          # self-attention: column windows of one fused QKV matrix
+def _xa_operands(spec, Mq, Mk, device):
+    """The (uninitialised) operands of an exact launch: (q, k, v, o)."""
+    C = spec["heads"] * spec["d"]
+    new = lambda M, W: torch.empty(M, W, dtype=torch.float16, device=device)
+    if Mq == Mk and spec["kv_div"] == 1 and spec["q_strides"] == spec["kv_strides"]:
+        t = new(Mq, 3 * C)                           # self-attention: column windows of one fused QKV matrix
         q, k, v = t[:, :C], t[:, C:2 * C], t[:, 2 * C:]
     else:
-        t = torch.cat([k, v], 1).to(DEV)             # Q of its own, K / V column windows of one matrix
-        q, k, v = q.to(DEV), t[:, :C], t[:, C:]
-    o = torch.full((q.shape[0], C), float("nan"), dtype=torch.float16, device=DEV)
-    extra = {} if d == 64 and not spec["causal"] and not spec["bias"] else dict(scale=case["scale"], head_dim=d, causal=spec["causal"])
-    ops.attention(q, k, v, o, batch=spec["batch"], heads=h, Sq=spec["Sq"], Sk=spec["Sk"], inner=spec["inner"], q_strides=spec["q_strides"],
-                  kv_strides=spec["kv_strides"], kv_div=spec["kv_div"], qk_mod=spec["qk_mod"], naive=spec["naive"],
-                  bias=None if case["bias"] is None else case["bias"].to(DEV), **extra)
+        t = new(Mk, 2 * C)                           # Q of its own, K / V column windows of one matrix
+        q, k, v = new(Mq, C), t[:, :C], t[:, C:]
+    return q, k, v, new(Mq, C)
+
+
+def _xa_kw(spec):
+    d = spec["d"]
+    kw = dict(batch=spec["batch"], heads=spec["heads"], Sq=spec["Sq"], Sk=spec["Sk"], inner=spec["inner"], q_strides=spec["q_strides"],
+              kv_strides=spec["kv_strides"], kv_div=spec["kv_div"], qk_mod=spec["qk_mod"], naive=spec["naive"])
+    if not (d == 64 and not spec["causal"] and not spec["bias"]):
+        kw.update(scale=d ** -0.5, head_dim=d, causal=spec["causal"])
+    return kw
+
+
+def _xa_launch(case):
+    spec = case["spec"]
+    q, k, v, o = _xa_operands(spec, case["q"].shape[0], case["k"].shape[0], DEV)
+    q.copy_(case["q"])
+    k.copy_(case["k"])
+    v.copy_(case["v"])
+    o.fill_(float("nan"))
+    ops.attention(q, k, v, o, bias=None if case["bias"] is None else case["bias"].to(DEV), **_xa_kw(spec))
     return o[case["rows"].to(DEV)]
+
+
+def exact_attention_plan_rows():
+    """(row name, line for tests/attention_plan_main.cpp, kernel named, instantiation named) of every launch of ``check_attention_exact``."""
+    rows = []
+    for spec in exact_attention_specs():
+        Mq, Mk = _xa_layout(spec)[5:7]
+        q, k, v, o = _xa_operands(spec, Mq, Mk, "meta")
+        rows.append((f"exact | {spec['kernel']}: {spec['name']}", attn_plan_words(q, k, v, o, bias=spec["bias"], **_xa_kw(spec)), spec["kernel"],
+                     spec["instantiation"]))
+    return rows
 
 
 def check_attention_exact(kernels=XA_KERNELS):
@@ -4978,6 +5155,164 @@ def check_attention_negative_kv_seq():
     ops.attention(q, k[Sk - 1:], v[Sk - 1:], o, kv_strides=(Sk, 0, -1), **kw)
     torch.cuda.synchronize()
     return [_res(f"attention b{b} h{h} Sq{Sq} Sk{Sk}, kv_seq = -1 (64-bit fallback) vs reference", o[rows], ref, KTOL)]
+
+
+def check_attention_wide_exit_to_generic():
+    """The exit of ``anyv2v_attention_f16`` that leaves the flash kernels for the one-thread-per-query kernel: a layout their 32-bit tile
+    offsets cannot hold (kv_seq = -1) with more batch elements than the loop kernel's grid takes (65536 > 65535).  Two queries and two keys
+    per element; flag bit1 keeps the short one-wave kernel, which comes first at <= 16 positions, out of the way."""
+    b, h, Sq, Sk = WIDE_GENERIC_SHAPE
+    C = 64 * h
+    q, k, v = rnd(b * Sq, C, seed=11), rnd(b * Sk, C, seed=12), rnd(b * Sk, C, seed=13)
+    kw = dict(batch=b, heads=h, Sq=Sq, Sk=Sk, inner=1, q_strides=(Sq, 0, 1))
+    rows, ref = _attn_ref(q, k, v, kv_strides=(Sk, 0, 1), **kw)
+    o = _poison((b * Sq, C), torch.float16)
+    saved, ops.ATTN_FLAGS = ops.ATTN_FLAGS, ops.ATTN_FLAGS | 2
+    try:
+        ops.attention(q, k[Sk - 1:], v[Sk - 1:], o, kv_strides=(Sk, 0, -1), **kw)
+    finally:
+        ops.ATTN_FLAGS = saved
+    torch.cuda.synchronize()
+    return [_res(f"attention b{b} h{h} Sq{Sq} Sk{Sk}, kv_seq = -1, batch > 65535 (generic kernel) vs reference", o[rows], ref, KTOL)]
+
+
+WIDE_GENERIC_SHAPE = (65536, 1, 2, 2)   # batch, heads, Sq, Sk
+
+
+def forced_rescale_8wave_specs():
+    """The smallest 8-wave shapes of ``exact_attention_specs`` with spiked keys (second tile, middle, ragged last tile), as in
+    ``check_attention_forced_rescale``: (name, instantiation, launch shape, spiked keys, gain, batch elements compared)."""
+    return (("plain b64 h4 Sq1024 Sk2100 kv_div64", "flash<3,1,8>", dict(batch=64, heads=4, Sq=1024, Sk=2100, kv_div=64, qk_mod=0), [70, 1029, 2099], 6.0, (0, 63)),
+            ("shared-softmax b96 h4 S2100 qk_mod32", "flash<3,3,8>", dict(batch=96, heads=4, Sq=2100, Sk=2100, kv_div=1, qk_mod=32), [70, 1029, 2099], 6.0, (0, 95)))
+
+
+def _rescale8_strides(shape):
+    return dict(inner=1, q_strides=(shape["Sq"], 0, 1), kv_strides=(shape["Sk"], 0, 1))
+
+
+def check_attention_forced_rescale_8wave():
+    """``check_attention_forced_rescale`` on the 8-wave instantiations of the flash kernel: keys whose score for one query row dwarfs the
+    rest force the textbook path (true maximum, rescale of O and l, re-exponentiation) after the first step.  Reference: fp32 SDPA on the
+    same fp16 inputs, two batch elements (every head)."""
+    out = []
+    for name, inst, shape, keys, gain, only in forced_rescale_8wave_specs():
+        b, h, Sq, Sk = shape["batch"], shape["heads"], shape["Sq"], shape["Sk"]
+        C = 64 * h
+        n_kv = b // shape["kv_div"]
+        g = torch.Generator(device=DEV).manual_seed(Sq + Sk)
+        new = lambda M, W: torch.randn(M, W, device=DEV, generator=g).half()
+        if Sq == Sk and shape["kv_div"] == 1:
+            t = new(b * Sq, 3 * C)
+            q, k, v = t[:, :C], t[:, C:2 * C], t[:, 2 * C:]
+        else:
+            t = new(n_kv * Sk, 2 * C)
+            q, k, v = new(b * Sq, C), t[:, :C], t[:, C:]
+        qv, kvw = q.view(b, Sq, h, 64), k.view(n_kv, Sk, h, 64)
+        for n, key in enumerate(keys):      # in turn for the compared elements: a key of the K the element reads follows one of the query rows it reads
+            src = only[n % len(only)] % shape["qk_mod"] if shape["qk_mod"] else only[n % len(only)]
+            kvw[src // shape["kv_div"], key] = (gain * qv[src, (7 + 13 * n) % Sq].float()).half()
+        o = torch.zeros(b * Sq, C, dtype=torch.float16, device=DEV)
+        kw = dict(shape, **_rescale8_strides(shape))
+        ops.attention(q, k, v, o, **kw)
+        rows, ref = _attn_ref(q, k, v, only=list(only), **kw)
+        out.append(_res(f"attn[{inst}] forced rescale: spikes at keys {keys}, {name}, elements {only} vs fp32 SDPA", o[rows], ref, KTOL))
+        del t, q, k, v, o, ref
+    return out
+
+
+def named_attention_plan_rows():
+    """(row name, line for tests/attention_plan_main.cpp, kernel named, instantiation named or None) of the launches that the random-data
+    checks name by kernel: ``check_attention_small_mfma``, ``check_attention_forced_rescale`` (and its 8-wave twin),
+    ``check_attention_bias_and_rotary_windows``, the kernel-naming rows of ``check_attention``, ``check_attention_negative_kv_seq`` and
+    ``check_attention_wide_exit_to_generic``.  The operands are the column windows those checks cut, on the device "meta"."""
+    rows = []
+    new = lambda M, W: torch.empty(M, W, dtype=torch.float16, device="meta")
+
+    def fused(Mq, C):
+        t = new(Mq, 3 * C)
+        return t[:, :C], t[:, C:2 * C], t[:, 2 * C:], new(Mq, C)
+
+    def q_kv(Mq, Mk, C):
+        t = new(Mk, 2 * C)
+        return new(Mq, C), t[:, :C], t[:, C:], new(Mq, C)
+
+    def add(name, kernel, inst, tensors, **kw):
+        rows.append((name, attn_plan_words(*tensors, **kw), kernel, inst))
+    sp = lambda S, Sk=None: dict(inner=1, q_strides=(S, 0, 1), kv_strides=(S if Sk is None else Sk, 0, 1))
+    for (B, h, S, d, causal, kernel) in attention_small_mfma_specs():
+        add(f"small mfma | B{B} h{h} S{S} d{d} causal={causal}", kernel, None, fused(B * S, h * d), batch=B, heads=h, Sq=S, Sk=S, scale=d ** -0.5,
+            head_dim=d, causal=causal, **sp(S))
+    Bc, Fr, HW, h, d = 2, 16, 48, 8, 40          # its temporal layout row: 16 queries x 24 keys
+    add("small mfma | temporal layout 8 x 40", "whole-sequence MFMA", "small<2,6>", q_kv(Bc * Fr * HW, Bc * HW * (Fr + 8), h * d), batch=Bc * HW, heads=h,
+        Sq=Fr, Sk=Fr + 8, inner=HW, q_strides=(Fr * HW, 1, HW), kv_strides=(HW * (Fr + 8), Fr + 8, 1), scale=d ** -0.5, head_dim=d)
+    for name, S, Sk, _build in forced_rescale_specs():
+        add(f"forced rescale | flash: {name}", "4-wave flash", "flash<2,1,4>", q_kv(2 * S, 2 * Sk, 128), batch=2, heads=2, Sq=S, Sk=Sk, **sp(S, Sk))
+        if S == Sk:
+            add(f"forced rescale | shared softmax: {name}", "shared-softmax 4-wave", "flash<2,3,4>", fused(3 * S, 128), batch=3, heads=2, Sq=S, Sk=S,
+                qk_mod=1, **sp(S))
+    for name, inst, shape, _keys, _gain, _only in forced_rescale_8wave_specs():
+        b, Sq, Sk, C = shape["batch"], shape["Sq"], shape["Sk"], 64 * shape["heads"]
+        tensors = fused(b * Sq, C) if Sq == Sk and shape["kv_div"] == 1 else q_kv(b * Sq, b // shape["kv_div"] * Sk, C)
+        add(f"forced rescale 8-wave | {name}", "8-wave", inst, tensors, **shape, **_rescale8_strides(shape))
+    for (heads, D, Fr, inst) in attention_bias_specs():
+        B, HW = 3, 10
+        for qk_mod in (0, B * HW // 3):
+            add(f"score bias | {heads} x {D}, {Fr} frames, qk_mod {qk_mod}", "bias", inst, fused(B * Fr * HW, heads * D), batch=B * HW, heads=heads, Sq=Fr,
+                Sk=Fr, inner=HW, q_strides=(Fr * HW, 1, HW), kv_strides=(Fr * HW, 1, HW), qk_mod=qk_mod, scale=D ** -0.5, head_dim=D, bias=True)
+    for (b, h, S) in ATTN_PNP_SHARED_SHAPES:
+        for flag, kernel, inst in ((0, "shared-softmax 4-wave", "flash<2,3,4>"), (8, "4-wave flash", "flash<2,1,4>")):
+            add(f"check_attention | PnP shared-softmax b{b} h{h} S{S} flags {flag}", kernel, inst, fused(b * S, 64 * h), batch=b, heads=h, Sq=S, Sk=S,
+                qk_mod=b // 3, flags=flag, **sp(S))
+    for key, qk, plans in (("shared-softmax", True, ((0, "shared-softmax 8-wave", "flash<3,3,8>"), (8, "8-wave", "flash<3,1,8>"))),
+                           ("shared-softmax, ragged", True, ((0, "shared-softmax 8-wave", "flash<3,3,8>"), (8, "8-wave", "flash<3,1,8>"))),
+                           ("plain", False, ((0, "8-wave", "flash<3,1,8>"), (4, "4-wave flash", "flash<2,1,4>")))):
+        b, h, S = ATTN_8WAVE_SHAPES[key]
+        for flag, kernel, inst in plans:
+            add(f"check_attention | 8-wave blocks, {key} b{b} h{h} S{S} flags {flag}", kernel, inst, fused(b * S, 64 * h), batch=b, heads=h, Sq=S, Sk=S,
+                qk_mod=b // 3 if qk else 0, flags=flag, **sp(S))
+    for (b, h, S, Sk, kv_div, qk_mod) in ATTN_FLASH_KV_LOOP_SHAPES:
+        add(f"check_attention | attn[flash] b{b} h{h} S{S} Sk{Sk} kv_div{kv_div} qk_mod{qk_mod}", "4-wave flash", "flash<2,1,4>",
+            q_kv(b * S, (b // kv_div) * Sk, 64 * h), batch=b, heads=h, Sq=S, Sk=Sk, kv_div=kv_div, qk_mod=qk_mod, **sp(S, Sk))
+    # kv_seq = -1: K / V handed over at their last key (row Sk - 1 of a [b Sk, C] matrix)
+    b, h, Sq, Sk = 2, 2, 130, 70
+    last = lambda Mk, C: new(Mk, C)[Sk - 1:]
+    add("negative kv_seq | b2 h2 Sq130 Sk70", "64-bit fallback", "loop<2>", (new(b * Sq, 64 * h), last(b * Sk, 64 * h), last(b * Sk, 64 * h), new(b * Sq, 64 * h)),
+        batch=b, heads=h, Sq=Sq, Sk=Sk, inner=1, q_strides=(Sq, 0, 1), kv_strides=(Sk, 0, -1))
+    b, h, Sq, Sk = WIDE_GENERIC_SHAPE
+    for flag, kernel, inst in ((2, "generic", "naive"), (0, "short one-wave", "short<1>")):     # without bit1 the short kernel takes two positions first
+        add(f"wide exit to the generic kernel | b{b} h{h} Sq{Sq} Sk{Sk} flags {flag}", kernel, inst,
+            (new(b * Sq, 64 * h), last(b * Sk, 64 * h), last(b * Sk, 64 * h), new(b * Sq, 64 * h)), batch=b, heads=h, Sq=Sq, Sk=Sk, inner=1,
+            q_strides=(Sq, 0, 1), kv_strides=(Sk, 0, -1), flags=flag)
+    return rows
+
+
+def far_attention_plan_rows():
+    """(row name, line for tests/attention_plan_main.cpp, kernel named, instantiation named or None, fallback) of every launch of
+    ``check_far_attention``: the near launch of each spec and each far one, with the leading dimension and strides ``far_attention_layout``
+    gives the far operand (a far buffer's pointer lies a multiple of 16 bytes into its allocation)."""
+    rows = []
+    for spec in far_attention_specs():
+        b, h, Sq, Sk, d = spec["batch"], spec["heads"], spec["Sq"], spec["Sk"], spec["d"]
+        C = h * d
+        kw = dict(batch=b, heads=h, Sq=Sq, Sk=Sk, inner=1, qk_mod=spec["qk_mod"], naive=spec["naive"], bias=spec["bias"], flags=spec["flags"])
+        if not (d == 64 and not spec["causal"] and not spec["bias"]):
+            kw.update(scale=d ** -0.5, head_dim=d, causal=spec["causal"])
+        near = dict(q_strides=(Sq, 0, 1), kv_strides=(Sk, 0, 1))
+        mat = lambda M, ld=C: torch.empty_strided((M, C), (ld, 1), dtype=torch.float16, device="meta")
+        base = f"far | {spec['kernel']}: {spec['name']}"
+        rows.append((base + " | near", attn_plan_words(mat(b * Sq), mat(b * Sk), mat(b * Sk), mat(b * Sq), **kw, **near), spec["kernel"], None, False))
+        for which, via in spec["fars"]:
+            L = far_attention_layout(spec, which, via)
+            assert L["geo"]["lead"] % 16 == 0
+            n_rows = int(L["rows"].max()) + 1
+            t = dict(Q=mat(b * Sq), K=mat(b * Sk), V=mat(b * Sk), O=mat(b * Sq))
+            for nm in ("Q", "O") if L["pair_q"] else ("K", "V"):
+                t[nm] = mat(n_rows, L["ld"] if nm == which else C)
+            st = dict(near)
+            st["q_strides" if L["pair_q"] else "kv_strides"] = L["strides"]
+            rows.append((f"{base} | {which} far via {via}", attn_plan_words(t["Q"], t["K"], t["V"], t["O"], **kw, **st),
+                         "64-bit fallback" if L["fallback"] else spec["kernel"], None, L["fallback"]))
+    return rows
 
 
 FAR_ATTN_KERNELS = ("4-wave flash", "8-wave", "shared-softmax 4-wave", "shared-softmax 8-wave", "short one-wave", "whole-sequence MFMA", "96-key loop",

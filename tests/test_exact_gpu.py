@@ -5,7 +5,7 @@ bit whatever the summation order, every row's tolerance is 0 and its ``err`` is 
 the rounding contract of the epilogue, fp16(fp16(acc + bias + rowvec) + R), on every family and then each family against the naive
 kernel; the attention rows show that every key position is read once, from its own V row, and counted once in the denominator.  The
 builders and their conditions are checked on the CPU by tests/test_exact_host.py, the family each GEMM launch names by
-tests/test_gemm_plan_host.py.
+tests/test_gemm_plan_host.py, the kernel instantiation each attention launch names by tests/test_attention_plan_host.py.
 """
 import os
 

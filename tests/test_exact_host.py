@@ -163,7 +163,10 @@ def test_selection_is_exactly_one_hot_and_reaches_every_key(spec, pattern):
         assert tuple(case["bias"].shape) == (h, Sq, Sk) and not torch.equal(pi[0, 0], pi[0, 1])   # another permutation per head
 
 
-@pytest.mark.parametrize("spec,pattern", SELECTION[:3] + SELECTION[-2:], ids=_ids(SELECTION[:3] + SELECTION[-2:]))
+SHIFTED = SELECTION[:3] + [c for c in SELECTION if c[0]["kernel"] == "generic"][-3:]   # flash kernels; generic with and without the naive flag
+
+
+@pytest.mark.parametrize("spec,pattern", SHIFTED, ids=_ids(SHIFTED))
 def test_a_v_row_shifted_by_one_key_fails_the_selection(spec, pattern):
     case = gc.exact_attention_case(spec, pattern)
     rq, rkv, i, iq, n_kv, Mq, Mk = gc._xa_layout(spec)
@@ -187,3 +190,7 @@ def test_every_kernel_has_its_shapes():
     assert {s["kernel"] for s in ATTN_SPECS} == set(gc.XA_KERNELS)
     assert all("selection" in gc.exact_attention_patterns(s) for s in ATTN_SPECS)
     assert {s["kernel"] for s, p in ATTN_CASES if p == "causal edge"} == {"whole-sequence MFMA", "96-key loop", "generic"}
+    # every instantiation behind a kernel's name has a shape of its own (tests/test_attention_plan_host.py plans each spec and holds
+    # ``instantiation`` against the planner's answer, and this set against the planner's list)
+    for kernel in gc.XA_KERNELS:
+        assert {s["instantiation"] for s in ATTN_SPECS if s["kernel"] == kernel} == set(gc.ATTN_KERNEL_INSTANTIATIONS[kernel]), kernel

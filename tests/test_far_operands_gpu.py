@@ -54,6 +54,10 @@ def test_attention_with_a_negative_key_stride_takes_the_64_bit_kernels():
     _assert_all(gc.check_attention_negative_kv_seq())
 
 
+def test_attention_beyond_the_flash_limit_with_more_than_65535_batch_elements_takes_the_generic_kernel():
+    _assert_all(gc.check_attention_wide_exit_to_generic())
+
+
 @pytest.mark.parametrize("entry", gc.FAR_NORM_ENTRIES)
 def test_far_norms_on_a_source_past_2_31_elements(entry):
     _assert_all(gc.check_far_norm(entry))

@@ -116,6 +116,10 @@ def test_attention():
     _assert_all(gc.check_attention())
 
 
+def test_attention_forced_rescale_on_the_8_wave_blocks():
+    _assert_all(gc.check_attention_forced_rescale_8wave())
+
+
 def test_attention_small_mfma_clip_shapes():
     _assert_all(gc.check_attention_small_mfma())
 
