@@ -64,6 +64,10 @@ ANYV2V_GEMM_SWH = 1 << 28
 ANYV2V_GEMM_PROBE_KORDER_SHIFT = 29
 
 
+# anyv2v_guidance_stats_f16: the fixed grid and the record size (ANYV2V_GUIDANCE_STATS_* of include/anyv2v_hip.h)
+GUIDANCE_STATS_BLOCKS, GUIDANCE_STATS_THREADS, GUIDANCE_STATS_RECORD = 64, 256, 8
+
+
 class FFDesc(C.Structure):
     _fields_ = [
         ("X", C.c_void_p), ("W1", C.c_void_p), ("b1", C.c_void_p), ("W2", C.c_void_p), ("b2", C.c_void_p), ("R", C.c_void_p),
@@ -118,6 +122,8 @@ SYMBOLS = {
     "anyv2v_tile_blend_f16": (C.c_int, [_VP, _I64, _I32, _I32, _VP, _VP, _VP, _VP, _I32, _I32, _VP, _I32, _I32, _I32, _VP]),
     "anyv2v_rotary_f16":(C.c_int, [_VP, _I32, _I64, _I32, _I32, _I32, _I32, _I32, _I32, C.c_float, _VP]),
     "anyv2v_cfg_ddim_step_f16": (C.c_int, [_VP, _I32, _I32, _I32, _F32, _VP, _VP, _VP, _I32, _I32, _I32, _VP]),
+    "anyv2v_guidance_stats_f16": (C.c_int, [_VP, _I32, _I32, _I32, _F32, _VP, _I32, _I32, _I32, _VP]),
+    "anyv2v_cfg_ddim_step_ex_f16": (C.c_int, [_VP, _I32, _I32, _I32, _F32, _I32, _VP, _VP, _F32, _VP, _VP, _VP, _I32, _I32, _I32, _VP]),
     "anyv2v_ddim_step_f16": (C.c_int, [_VP, _VP, _VP, _F32, _F32, _F32, _F32, _I64, _VP]),
     "anyv2v_guided_step_f16": (C.c_int, [_VP, _I64, _I32, _I32, _I32, _F32, _F32, _I32, _F32, _F32, _F32, _F32, _VP, _VP, _VP]),
     "anyv2v_guided_step_noise_f16": (C.c_int, [_VP, _I64, _I32, _I32, _I32, _F32, _F32, _I32, _F32, _F32, _F32, _F32, _VP, _VP, _VP, _F32, _VP]),

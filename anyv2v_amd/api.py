@@ -20,7 +20,7 @@ from typing import List, Optional
 import torch
 from PIL import Image
 
-from .config import OmegaConf
+from .config import OmegaConf, sampler_options
 from .pipeline import I2VGenXLPipeline
 from .run_group_ddim_inversion import ddim_inversion
 from .run_group_pnp_edit import init_pnp
@@ -48,7 +48,8 @@ def read_frames(video_path: str) -> List[Image.Image]:
 class AnyV2V_I2VGenXL:
     def __init__(self, model_path: str = MODEL_ID, device="cuda:0", tmp_dir: str = "_demo_temp", pipe: Optional[I2VGenXLPipeline] = None,
                  random_init_seed: Optional[int] = None, synthetic_encoders: bool = False) -> None:
-        # default inversion / edit configuration of the demo (gradio_demo.py:60-78)
+        # default inversion / edit configuration of the demo (gradio_demo.py:60-78); ``pnp_config`` also takes the optional keys
+        # ``eta`` / ``guidance_rescale`` (``config.sampler_options``; e.g. ``obj.config.pnp_config.eta = 0.5``), absent = off
         self.config = OmegaConf.create({
             "inverse_config": {"image_size": [512, 512], "n_frames": 16, "cfg": 1.0, "target_fps": 8, "ddim_inv_prompt": "",
                                "prompt": "", "negative_prompt": ""},
@@ -121,11 +122,13 @@ class AnyV2V_I2VGenXL:
         cfg.pnp_config.ddim_init_latents_t_idx = ddim_init_latents_t_idx
         init_pnp(self.pipe, self.ddim_scheduler, cfg.pnp_config)
         self.pipe.register_modules(scheduler=self.ddim_scheduler)
+        eta, rescale = sampler_options(cfg.pnp_config)
+        self.pipe.enable_guidance_rescale(rescale)
         edited_video = self.pipe.sample_with_pnp(
             prompt=video_prompt, image=edited_1st_frame, height=cfg.inverse_config.image_size[1],
             width=cfg.inverse_config.image_size[0], num_frames=cfg.inverse_config.n_frames,
             num_inference_steps=cfg.pnp_config.n_steps, guidance_scale=guidance_scale, negative_prompt=video_negative_prompt,
-            target_fps=cfg.pnp_config.target_fps, latents=mixed_latents, generator=generator, return_dict=True,
+            eta=eta, target_fps=cfg.pnp_config.target_fps, latents=mixed_latents, generator=generator, return_dict=True,
             ddim_init_latents_t_idx=ddim_init_latents_t_idx, ddim_inv_latents_path=trajectory,
             ddim_inv_prompt=cfg.inverse_config.ddim_inv_prompt, ddim_inv_1st_frame=first_frame).frames[0]
         edited_video = [f.resize(tuple(cfg.inverse_config.image_size), resample=Image.LANCZOS) for f in edited_video]

@@ -90,6 +90,22 @@ class Config:
         return f"Config({self.to_container(resolve=False)!r})"
 
 
+def sampler_options(config) -> tuple:
+    """(eta, guidance_rescale) of a PnP-edit configuration (template YAML merged with a JSON entry, or a front-end's ``pnp_config``):
+    two OPTIONAL keys the reference's files do not have -- ``eta`` (stochastic DDIM, 0 <= eta <= 1) and ``guidance_rescale`` (Lin et
+    al.'s rescale, 0 <= phi <= 1).  Absent (or null) means off, and a job whose files name neither runs and writes exactly what it
+    did before the keys existed."""
+    def one(key):
+        v = config.get(key, None) if hasattr(config, "get") else getattr(config, key, None)   # (a ``Config`` or any plain namespace)
+        if v is None:
+            return 0.0
+        v = float(v)
+        if not 0.0 <= v <= 1.0:
+            raise ValueError(f"{key}={v}: 0 <= {key} <= 1")
+        return v
+    return one("eta"), one("guidance_rescale")
+
+
 def _rebind(cfg: Config, root: Config):
     object.__setattr__(cfg, "_root", root)
     for v in cfg._data.values():

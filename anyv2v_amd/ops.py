@@ -519,6 +519,51 @@ def cfg_ddim_step(vtok: torch.Tensor, b_unc: int, b_cond: int, guidance: float, 
     return out
 
 
+GUIDANCE_STATS_FLOATS = _lib.GUIDANCE_STATS_BLOCKS * _lib.GUIDANCE_STATS_RECORD
+
+
+def _branches_inside(vtok: torch.Tensor, branches, F: int, HW: int):
+    assert all(0 <= b and (b + 1) * F * HW <= vtok.shape[0] for b in branches), \
+        f"branch {tuple(branches)} of {F} x {HW} pixels lies outside the {vtok.shape[0]} token rows"
+
+
+def guidance_stats(vtok: torch.Tensor, b_unc: int, b_cond: int, guidance: float, lat_shape, out: Optional[torch.Tensor] = None):
+    """Records of the guidance rescale (``anyv2v_guidance_stats_f16``): sums about a pivot of the text branch ``vtok[b_cond]`` and of
+    the guided prediction, over one clip ``lat_shape`` = [1, C, F, H, W].  -> fp32 [GUIDANCE_STATS_FLOATS], for ``cfg_ddim_step_ex``."""
+    lib = _lib.load()
+    _rowmajor(vtok, "V")
+    _, Cc, F, H, W = lat_shape
+    _branches_inside(vtok, (b_unc, b_cond), F, H * W)
+    if out is None:
+        out = torch.empty(GUIDANCE_STATS_FLOATS, dtype=torch.float32, device=vtok.device)
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() >= GUIDANCE_STATS_FLOATS and out.device == vtok.device
+    _lib.check(lib.anyv2v_guidance_stats_f16(_p(vtok), vtok.stride(0), b_unc, b_cond, float(guidance), _p(out), Cc, F, H * W, _stream()),
+               "anyv2v_guidance_stats_f16")
+    return out
+
+
+def cfg_ddim_step_ex(vtok: torch.Tensor, b_unc: int, b_cond: int, guidance: float, row: torch.Tensor, lat: torch.Tensor,
+                     out: torch.Tensor, *, prediction: int = 0, stats: Optional[torch.Tensor] = None, phi: float = 0.0,
+                     noise: Optional[torch.Tensor] = None):
+    """``cfg_ddim_step`` with guidance rescale and stochastic DDIM (``anyv2v_cfg_ddim_step_ex_f16``).  row: 8 device floats {sa_t, sb_t,
+    c_x0, c_eps, sigma, phi, n, 0} (``DDIMScheduler.coefficient_table(..., eta=, phi=, n=)``); ``stats`` from ``guidance_stats`` when
+    ``phi`` > 0 (the host's copy of row[5]); ``noise``: fp16, planar like ``lat``, or None when sigma is 0 for the whole run."""
+    lib = _lib.load()
+    _rowmajor(vtok, "V")
+    assert lat.is_contiguous() and out.is_contiguous() and lat.dtype == out.dtype == torch.float16 and lat.shape[0] == 1 and out.shape == lat.shape
+    assert row.dtype == torch.float32 and row.is_contiguous() and row.numel() >= 8 and row.device == vtok.device
+    _, Cc, F, H, W = lat.shape
+    _branches_inside(vtok, (b_cond,) if b_unc < 0 else (b_unc, b_cond), F, H * W)
+    if stats is not None:
+        assert stats.dtype == torch.float32 and stats.is_contiguous() and stats.numel() >= GUIDANCE_STATS_FLOATS and stats.device == vtok.device
+    if noise is not None:
+        assert noise.dtype == torch.float16 and noise.is_contiguous() and noise.numel() == lat.numel() and noise.device == vtok.device
+    _lib.check(lib.anyv2v_cfg_ddim_step_ex_f16(_p(vtok), vtok.stride(0), b_unc, b_cond, float(guidance), int(prediction), _p(row), _p(stats),
+                                               float(phi), _p(noise), _p(lat), _p(out), Cc, F, H * W, _stream()),
+               "anyv2v_cfg_ddim_step_ex_f16")
+    return out
+
+
 def ddim_step(v: torch.Tensor, x: torch.Tensor, sa_t: float, sb_t: float, sa_p: float, sb_p: float, out=None):
     lib = _lib.load()
     v = v.to(torch.float16).contiguous()

@@ -93,8 +93,14 @@ class _StepEngine:
     step is overwritten by the caller with the source trajectory before each step.
     """
 
-    def __init__(self, pipe, sample, cond, b_unc, b_cond, guidance, dup_slots, shared_stem=False, batch_hint=None, lat_slots=None):
+    def __init__(self, pipe, sample, cond, b_unc, b_cond, guidance, dup_slots, shared_stem=False, batch_hint=None, lat_slots=None,
+                 stochastic=False, rescale=0.0):
         self.pipe, self.unet = pipe, pipe.unet
+        # sampler options (``_SamplerOptions``): with either one on, the step is ``ops.cfg_ddim_step_ex`` on an 8-float coefficient row
+        # (+ ``ops.guidance_stats`` in front of it under the rescale); with both off, nothing below differs from the default engine
+        self.stochastic, self.rescale = bool(stochastic), float(rescale)
+        self.options = self.stochastic or self.rescale > 0.0
+        assert not (self.options and lat_slots is not None), "the batched inversion has no sampler options"
         # (num, den): this engine runs a subset of another engine's branches ([negative, editing] of a three-branch edit step) and
         # must make the same launch choices -- ops.batch_hint
         self.batch_hint = batch_hint
@@ -105,7 +111,12 @@ class _StepEngine:
         # several clips inverted in one batch (``invert_clips``): every slot is a latent of its own, stepped without guidance
         self.lat_slots = None if lat_slots is None else list(lat_slots)
         self.dup_slots = list(dup_slots)
-        self.coef = torch.zeros(4, dtype=torch.float32, device=sample.device)
+        self.coef = torch.zeros(8 if self.options else 4, dtype=torch.float32, device=sample.device)
+        # static operands of the captured step: the variance noise of THIS step (copied in before every replay -- drawn outside the
+        # graph, from the caller's generator) and the records of the rescale statistics
+        self.noise = torch.zeros_like(sample[:1]) if self.stochastic else None
+        self.gstats = (torch.zeros(ops.GUIDANCE_STATS_FLOATS, dtype=torch.float32, device=sample.device)
+                       if self.rescale > 0.0 and b_unc >= 0 else None)   # (no guidance, no rescale: pipeline_video_editing.py:685)
         self.graphs: Dict[tuple, torch.cuda.CUDAGraph] = {}
         # (a frame-parallel forward contains collectives: run eagerly -- at 128 frames launch overhead is irrelevant)
         # (likewise with foreign hooks on the seams B1 / B2: torch-style code that may sync, e.g. ``t in cuda_tensor``)
@@ -176,17 +187,29 @@ class _StepEngine:
         L = self.lat_slot
         lat = self.sample[L:L + 1]
         off = 1 if vtok.shape[0] != self.sample.shape[0] * self.sample.shape[2] * self.sample.shape[3] * self.sample.shape[4] else 0
-        ops.cfg_ddim_step(vtok, self.b_unc - off if self.b_unc >= 0 else self.b_unc, self.b_cond - off, self.guidance, self.coef, lat, lat)
+        b_unc, b_cond = self.b_unc - off if self.b_unc >= 0 else self.b_unc, self.b_cond - off
+        if self.options:
+            if self.gstats is not None:
+                ops.guidance_stats(vtok, b_unc, b_cond, self.guidance, lat.shape, out=self.gstats)
+            ops.cfg_ddim_step_ex(vtok, b_unc, b_cond, self.guidance, self.coef, lat, lat, prediction=self.pipe.scheduler.prediction,
+                                 stats=self.gstats, phi=self.rescale if self.gstats is not None else 0.0, noise=self.noise)
+        else:
+            ops.cfg_ddim_step(vtok, b_unc, b_cond, self.guidance, self.coef, lat, lat)
         for s in self.dup_slots:
             self.sample[s].copy_(self.sample[L])
 
-    def step(self, t_row: torch.Tensor, coef_row: torch.Tensor, key: tuple):
+    def step(self, t_row: torch.Tensor, coef_row: torch.Tensor, key: tuple, noise: Optional[torch.Tensor] = None):
+        """``noise``: this step's variance noise (a stochastic engine needs a fresh draw for every step)."""
         with ops.workspace_slot(getattr(self.pipe, "ws_slot", 0)):
-            self._step(t_row, coef_row, key)
+            self._step(t_row, coef_row, key, noise)
 
-    def _step(self, t_row: torch.Tensor, coef_row: torch.Tensor, key: tuple):
+    def _step(self, t_row: torch.Tensor, coef_row: torch.Tensor, key: tuple, noise=None):
         self.ctx.t_buf.copy_(t_row, non_blocking=True)
         self.coef.copy_(coef_row, non_blocking=True)
+        if self.stochastic:
+            if noise is None:
+                raise ValueError("a stochastic step engine needs the step's variance noise: replaying the buffer would repeat the last draw")
+            self.noise.copy_(noise.reshape(self.noise.shape), non_blocking=True)
         if not self.use_graphs:
             self._body()
             return
@@ -229,6 +252,7 @@ class I2VGenXLPipeline:
         self.unet, self.scheduler = unet, scheduler
         self.vae_scale_factor = 8
         self._guidance_scale = 1.0
+        self._guidance_rescale = 0.0   # ``enable_guidance_rescale``
         self._device = torch.device("cpu")
         self._engines: Dict[tuple, _StepEngine] = {}  # step engines (static buffers + HIP graphs) kept across clips, LRU
         # pacing hooks of the clip pipeline (run_group_anyv2v): ``pace_record(i, n)`` is called when edit step i of n is about to be
@@ -291,6 +315,7 @@ class I2VGenXLPipeline:
         p = type(self)(vae=self.vae, text_encoder=self.text_encoder, tokenizer=self.tokenizer, image_encoder=self.image_encoder,
                        feature_extractor=self.feature_extractor, unet=self.unet, scheduler=self.scheduler)
         p._device, p.ws_slot = self._device, int(ws_slot)
+        p._guidance_rescale = self._guidance_rescale
         return p
 
     def to(self, device):
@@ -498,12 +523,50 @@ class I2VGenXLPipeline:
     def _forward_sampler_options(self, eta, cross_attention_kwargs):
         """``__call__`` / ``sample_with_pnp`` (``pipeline_i2vgen_xl.py:798,868`` / ``:1095,1173``): ``eta`` goes to ``scheduler.step`` when
         that takes it -- the forward DDIM scheduler does (stochastic DDIM), the inverse one does not (``invert`` drops it, as here).
-        The fused guidance + DDIM step of the step engines is the deterministic one; AnyV2V never sets either option, and silently
-        ignoring them would change the sample."""
+        This is the check of the DEFAULT step engine, whose fused guidance + DDIM step is the deterministic one: an ``eta`` that reaches it
+        would be silently ignored and change the sample, so it is refused.  ``_sampler_options`` routes ``eta`` > 0 to a stochastic engine
+        before it gets here."""
         if eta not in (None, 0, 0.0) and isinstance(self.scheduler, DDIMScheduler):
             raise ValueError(f"eta={eta}: the step engines run deterministic DDIM (eta = 0) only")
         if cross_attention_kwargs:
             raise ValueError("cross_attention_kwargs (LoRA scale, ...) are not supported by the native attention processors")
+
+    def enable_guidance_rescale(self, guidance_rescale: float):
+        """Lin et al.'s guidance rescale (``rescale_noise_cfg``, ``consisti2v/consisti2v/pipelines/pipeline_video_editing.py:50-61``) in
+        ``__call__`` and ``sample_with_pnp``: the guided prediction is scaled by phi std(text) / std(guided) + (1 - phi) before the
+        scheduler step (inside the step engine's fused kernel).  A setter, not a call argument: the reference's I2VGen-XL signatures have
+        none.  0 switches it off; ``invert`` and ``invert_clips`` never rescale."""
+        phi = float(guidance_rescale)
+        if not 0.0 <= phi <= 1.0:   # (also refuses NaN)
+            raise ValueError(f"guidance_rescale={guidance_rescale}: 0 <= guidance_rescale <= 1")
+        if phi > 0.0 and getattr(self.unet, "frame_parallel", None) is not None:
+            raise NotImplementedError("guidance rescale on a frame-parallel clip: the statistics span all frames and would need a collective")
+        self._guidance_rescale = phi
+
+    def disable_guidance_rescale(self):
+        self._guidance_rescale = 0.0
+
+    def _sampler_options(self, eta, cross_attention_kwargs):
+        """-> (stochastic, eta, phi) for the step engines of ``__call__`` / ``sample_with_pnp``.  ``eta`` counts when the scheduler is the
+        forward ``DDIMScheduler`` (as ``prepare_extra_step_kwargs``: the inverse scheduler's ``step`` takes none); 0 <= eta <= 1."""
+        phi = float(getattr(self, "_guidance_rescale", 0.0))
+        forward = isinstance(self.scheduler, DDIMScheduler)
+        if forward and eta is not None and not 0.0 <= float(eta) <= 1.0:
+            raise ValueError(f"eta={eta}: stochastic DDIM takes 0 <= eta <= 1")
+        stochastic = bool(forward and eta is not None and float(eta) > 0.0)
+        if phi > 0.0 and not forward:
+            raise NotImplementedError(f"guidance rescale runs in the forward DDIM step engines, not with {type(self.scheduler).__name__}")
+        if (stochastic or phi > 0.0) and getattr(self.unet, "frame_parallel", None) is not None:
+            raise NotImplementedError(f"eta={eta} / guidance_rescale={phi} on a frame-parallel clip: the rescale statistics span all frames "
+                                      "(they would need a collective) and every rank would have to draw the same noise")
+        self._forward_sampler_options(0.0 if stochastic else eta, cross_attention_kwargs)
+        return stochastic, (float(eta) if stochastic else 0.0), phi
+
+    def _variance_noise(self, stochastic, like, generator):
+        """One draw per step, where diffusers' ``DDIMScheduler.step`` draws its ``variance_noise`` (``randn_tensor`` with the shape and
+        dtype of the guided prediction, from the caller's ``generator``), handed to the engine's static buffer OUTSIDE the captured graph:
+        a draw recorded inside a graph -- or a buffer filled once -- would replay the same noise at every step."""
+        return self.scheduler.draw_noise(like, generator) if stochastic else None
 
     # ------------------------------------------------------------------ conditioning assembly
     def _conditioning(self, prompt, image, height, width, num_frames, negative_prompt, prompt_embeds,
@@ -541,6 +604,9 @@ class I2VGenXLPipeline:
                kw.get("b_cond"), float(kw.get("guidance")), tuple(kw.get("dup_slots")), bool(kw.get("shared_stem", False)),
                _use_graphs(), pnp_utils.has_foreign_hooks(self.unet), id(self.unet), kw.get("lat_slots"),
                getattr(self.unet, "freeu", None))   # (a captured graph holds the FreeU launches of the setting it was captured under)
+        if kw.get("stochastic") or kw.get("rescale"):
+            # ... and the launches of its sampler options; with both off the key is the default engine's, unchanged
+            key += (("sampler", bool(kw.get("stochastic")), float(kw.get("rescale") or 0.0)),)
         eng = self._engines.pop(key, None)
         if eng is None or not eng.rebind(sample, cond):
             eng = _StepEngine(self, sample, cond, **kw)
@@ -686,7 +752,7 @@ class I2VGenXLPipeline:
         pe, npe, ie, il = self._conditioning(prompt, image, height, width, num_frames, negative_prompt, prompt_embeds,
                                              negative_prompt_embeds, target_fps, clip_skip, image_embeddings, image_latents)
         self._single_clip(pe, num_videos_per_prompt)
-        self._forward_sampler_options(eta, cross_attention_kwargs)
+        stochastic, eta, phi = self._sampler_options(eta, cross_attention_kwargs)
         cfg_on = self.do_classifier_free_guidance
         pnp_utils.clear_time(self)  # plain CFG sampling (DDIM reconstruction) runs hook-free
         if cfg_on:
@@ -703,13 +769,15 @@ class I2VGenXLPipeline:
         sample = latents.repeat(nb, 1, 1, 1, 1).contiguous()
         cond = dict(encoder_hidden_states=ehs.contiguous(), fps=fps, image_latents=il_all.contiguous(),
                     image_embeddings=ie_all.contiguous())
+        opts = dict(stochastic=stochastic, rescale=phi) if (stochastic or phi > 0.0) else {}
         eng = self._engine("cfg", sample, cond, b_unc=0 if cfg_on else -1, b_cond=nb - 1, guidance=guidance_scale,
-                           dup_slots=range(nb - 1), shared_stem=cfg_on)
+                           dup_slots=range(nb - 1), shared_stem=cfg_on, **opts)
         sample = eng.sample
         t_table = torch.tensor(ts, dtype=torch.float32, device=device)[:, None].expand(-1, nb).contiguous()
-        coef_table = self.scheduler.coefficient_table(ts, device)
+        coef_table = self.scheduler.coefficient_table(ts, device, eta=eta, phi=phi, n=latents.numel()) if opts else \
+            self.scheduler.coefficient_table(ts, device)
         for i, t in enumerate(ts):
-            eng.step(t_table[i], coef_table[i], key=("cfg",))
+            eng.step(t_table[i], coef_table[i], key=("cfg",), noise=self._variance_noise(stochastic, sample[nb - 1:nb], generator))
             if latents_trace is not None:
                 latents_trace[t] = sample[nb - 1:nb].clone()
         return self._finish(sample[nb - 1:nb].clone(), output_type, decode_chunk_size, return_dict)
@@ -737,7 +805,8 @@ class I2VGenXLPipeline:
         pe, npe, ie, il = self._conditioning(prompt, image, height, width, num_frames, negative_prompt, prompt_embeds,
                                              negative_prompt_embeds, target_fps, clip_skip, image_embeddings, image_latents)
         self._single_clip(pe, num_videos_per_prompt)
-        self._forward_sampler_options(eta, cross_attention_kwargs)
+        stochastic, eta, phi = self._sampler_options(eta, cross_attention_kwargs)
+        opts = dict(stochastic=stochastic, rescale=phi) if (stochastic or phi > 0.0) else {}
         # source (ddim inversion) branch: its own prompt, first frame, positive image embedding (:1027-1091)
         if ddim_inv_prompt_embeds is None:
             ddim_inv_prompt_embeds = _clip_text(self._need("text_encoder"), self._need("tokenizer"), ddim_inv_prompt,
@@ -771,7 +840,7 @@ class I2VGenXLPipeline:
         # the source branch's prediction is never read (:1136,1160-1162): its forward may stop behind the last hook site (exact)
         drop_tail = cfg_on and nb == 3 and os.environ.get("ANYV2V_DROP_SRC_TAIL", "1") == "1"
         eng = self._engine("pnp-droptail" if drop_tail else "pnp", sample, cond, b_unc=1 if cfg_on else -1, b_cond=nb - 1,
-                           guidance=guidance_scale, dup_slots=range(1, nb - 1), shared_stem=cfg_on)
+                           guidance=guidance_scale, dup_slots=range(1, nb - 1), shared_stem=cfg_on, **opts)
         eng.drop_src_tail = drop_tail
         sample = eng.sample
         # source trajectory resident in HBM (in-memory hand-off from invert(), or read once from the reference's files)
@@ -780,14 +849,17 @@ class I2VGenXLPipeline:
         else:
             traj = LatentTrajectory.load(ddim_inv_latents_path, device=device, timesteps=ts)
         t_table = torch.tensor(ts, dtype=torch.float32, device=device)[:, None].expand(-1, nb).contiguous()
-        coef_table = self.scheduler.coefficient_table(ts, device)
+        coef_table = self.scheduler.coefficient_table(ts, device, eta=eta, phi=phi, n=latents.numel()) if opts else \
+            self.scheduler.coefficient_table(ts, device)
         # Exact work elimination (SURVEY A.5 probe "branches 1,2 of a B=3 forward equal a B=2 forward"): on a step that lies
         # outside every injection schedule nothing reads the source branch, so the step runs on the [negative, editing]
         # slots only.  Both engines share the `sample` storage, so they can alternate freely.
         skip_src = cfg_on and nb == 3 and os.environ.get("ANYV2V_SRC_SKIP", "1") == "1"
         eng_nosrc = None
         nosrc_bound = False
-        # multi-edit job: record / replay what the injected sites read from the source branch (SourceFeatureCache)
+        # multi-edit job: record / replay what the injected sites read from the source branch (SourceFeatureCache).  The sampler
+        # options (eta, guidance rescale) leave it valid: the source branch is fed from the inversion trajectory (``sample[0]`` below)
+        # and never sees the edit latent, its noise or its rescaled prediction, so what it records does not depend on them.
         cache = self.source_cache if (skip_src and not pnp_utils.has_foreign_hooks(self.unet)
                                       and getattr(self.unet, "frame_parallel", None) is None) else None
         sites = pnp_utils.injection_sites(self) if cache is not None else []
@@ -812,6 +884,7 @@ class I2VGenXLPipeline:
                 self.pace_record(i, len(ts))
             pnp_utils.register_time(self, t)  # host-side only: python int, no device sync (:1143)
             state = pnp_utils.injection_state(self)
+            noise = self._variance_noise(stochastic, sample[nb - 1:nb], generator)   # one draw per step, whichever engine runs it
             if any(state) and nb != 3:
                 # the hooks slice the batch in thirds (pnp_utils.py:111,166,272); with guidance_scale <= 1 the reference
                 # builds a 2-way batch and silently injects the wrong rows -- refuse instead
@@ -822,9 +895,9 @@ class I2VGenXLPipeline:
                     cond2 = {k: v[1:].contiguous() for k, v in cond.items()}
                     if eng.nosrc is None or not eng.nosrc.rebind(sample[1:], cond2):
                         eng.nosrc = _StepEngine(self, sample[1:], cond2, b_unc=0, b_cond=1, guidance=guidance_scale,
-                                                dup_slots=[0], shared_stem=True, batch_hint=(3, 2))
+                                                dup_slots=[0], shared_stem=True, batch_hint=(3, 2), **opts)
                     eng_nosrc, nosrc_bound = eng.nosrc, True
-                eng_nosrc.step(t_table[i, 1:], coef_table[i], key=("pnp-nosrc",))
+                eng_nosrc.step(t_table[i, 1:], coef_table[i], key=("pnp-nosrc",), noise=noise)
             elif cache is not None and cache.has(t, state):
                 # replay: the source features of this step are in HBM -- [negative, editing] only
                 names = [n for (n, _, _), on in zip(sites, state) if on]
@@ -832,12 +905,12 @@ class I2VGenXLPipeline:
                     cond2 = {k: v[1:].contiguous() for k, v in cond.items()}
                     if eng.nosrc is None or not eng.nosrc.rebind(sample[1:], cond2):
                         eng.nosrc = _StepEngine(self, sample[1:], cond2, b_unc=0, b_cond=1, guidance=guidance_scale,
-                                                dup_slots=[0], shared_stem=True, batch_hint=(3, 2))
+                                                dup_slots=[0], shared_stem=True, batch_hint=(3, 2), **opts)
                     eng_nosrc, nosrc_bound = eng.nosrc, True
                 for n in names:
                     eng.site_bufs[n].copy_(cache.steps[(int(t), state)][n], non_blocking=True)
                 set_io("replay", names)
-                eng_nosrc.step(t_table[i, 1:], coef_table[i], key=("pnp-replay",) + state)
+                eng_nosrc.step(t_table[i, 1:], coef_table[i], key=("pnp-replay",) + state, noise=noise)
                 set_io(None, ())
                 cache.replayed_steps += 1
             else:
@@ -845,11 +918,11 @@ class I2VGenXLPipeline:
                 if cache is not None:
                     names = [n for (n, _, _), on in zip(sites, state) if on]
                     set_io("record", names)
-                    eng.step(t_table[i], coef_table[i], key=("pnp-record",) + state)
+                    eng.step(t_table[i], coef_table[i], key=("pnp-record",) + state, noise=noise)
                     set_io(None, ())
                     cache.recorded_steps += bool(cache.store(t, state, {n: eng.site_bufs[n] for n in names}))
                 else:
-                    eng.step(t_table[i], coef_table[i], key=("pnp",) + state)
+                    eng.step(t_table[i], coef_table[i], key=("pnp",) + state, noise=noise)
             if latents_trace is not None:
                 latents_trace[t] = sample[nb - 1:nb].clone()
         return self._finish(sample[nb - 1:nb].clone(), output_type, decode_chunk_size, return_dict)

@@ -4,6 +4,9 @@ files, one pipeline (weights loaded once), the inversion trajectory of each clip
 front-ends (``gradio_demo.py:58-222``, ``predict.py:43-258``); its two CLI stages communicate through ``ddim_latents_{t}.pt``.
 Every file of both stages is still written (same names, same formats), so the outputs are interchangeable with the two-step
 run; an edit entry whose inversion was skipped here (directory already complete) reads the files as stage 2 alone would.
+The edit template / entries take the optional sampler keys of stage 2 (``eta``, ``guidance_rescale``; ``config.sampler_options``): the
+inversion ignores them, and an edit that draws variance noise draws it inside its own seeded entry, so the two-stream order below
+still writes what the serial order writes.
 
     python -m anyv2v_amd.run_group_anyv2v --inversion_template configs/group_ddim_inversion/template.yaml \\
         --inversion_configs_json configs/group_ddim_inversion/group_config.json \\

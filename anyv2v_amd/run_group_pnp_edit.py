@@ -19,7 +19,7 @@ from pathlib import Path
 import torch
 from PIL import Image
 
-from .config import OmegaConf
+from .config import OmegaConf, sampler_options
 from .encoders import attach_synthetic_encoders
 from .parallel import FrameParallel, gather_latents, init_distributed, seed_for_entry, shard_entries
 from .pipeline import I2VGenXLPipeline
@@ -47,10 +47,12 @@ def init_pnp(pipe, scheduler, config):
 
 
 def output_suffix(config, ddim_init_latents_t_idx) -> str:
-    """``run_group_pnp_edit.py:154-167``."""
+    """``run_group_pnp_edit.py:154-167``; the optional sampler keys (``config.sampler_options``) add to the name only when they are on,
+    so two entries that differ in them alone do not overwrite each other and every other directory keeps the reference's name."""
+    eta, rescale = sampler_options(config)
     return ("ddim_init_latents_t_idx_" + str(ddim_init_latents_t_idx) + "_nsteps_" + str(config.n_steps) + "_cfg_"
             + str(config.cfg) + "_pnpf" + str(config.pnp_f_t) + "_pnps" + str(config.pnp_spatial_attn_t) + "_pnpt"
-            + str(config.pnp_temp_attn_t))
+            + str(config.pnp_temp_attn_t) + (f"_eta{eta}" if eta > 0 else "") + (f"_rescale{rescale}" if rescale > 0 else ""))
 
 
 class Stage2:
@@ -154,10 +156,12 @@ class Stage2:
         init_pnp(pipe, ddim_scheduler, config)
         pipe.register_modules(scheduler=ddim_scheduler)
         pipe.auto_vae_tiling(config.image_size[1], config.image_size[0])
+        eta, rescale = sampler_options(config)   # optional keys ``eta`` / ``guidance_rescale``; absent: (0, 0), the default engines
+        pipe.enable_guidance_rescale(rescale)
         edited_latents = pipe.sample_with_pnp(
             prompt=config.editing_prompt, image=edited_1st_frame, height=config.image_size[1], width=config.image_size[0],
             num_frames=config.n_frames, num_inference_steps=config.n_steps, guidance_scale=config.cfg,
-            negative_prompt=config.editing_negative_prompt, target_fps=config.target_fps, latents=mixed_latents,
+            negative_prompt=config.editing_negative_prompt, eta=eta, target_fps=config.target_fps, latents=mixed_latents,
             generator=torch.manual_seed(config.seed), return_dict=True, ddim_init_latents_t_idx=t_idx,
             ddim_inv_latents_path=traj, ddim_inv_prompt=config.ddim_inv_prompt, ddim_inv_1st_frame=src_1st_frame,
             output_type="latent").frames

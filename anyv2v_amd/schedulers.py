@@ -142,9 +142,30 @@ class _DDIMBase:
     def eta_coefficients(self, timestep: int, eta: float):
         raise NotImplementedError(f"eta > 0 is the forward DDIM scheduler's option, not {type(self).__name__}'s")
 
-    def coefficient_table(self, timesteps, device) -> torch.Tensor:
-        """[len(timesteps), 4] fp32 device table {sqrt(a_t), sqrt(1-a_t), sqrt(a_p), sqrt(1-a_p)} for the fused step."""
-        rows = [self.coefficients(int(t)) for t in timesteps]
+    def coefficient_table(self, timesteps, device, eta=None, phi: float = 0.0, n: int = 0) -> torch.Tensor:
+        """[len(timesteps), 4] fp32 device table {sqrt(a_t), sqrt(1-a_t), sqrt(a_p), sqrt(1-a_p)} for the fused step.
+
+        With a sampler option (``eta`` > 0: stochastic DDIM; ``phi`` > 0: guidance rescale over the ``n`` elements of one clip's
+        prediction) the ``eta`` form [len(timesteps), 8] of ``ops.cfg_ddim_step_ex``: {sa_t, sb_t, c_x0, c_eps, sigma, phi, n, 0} from
+        ``eta_coefficients``.  With both off (``eta`` None or 0, ``phi`` 0) the table is the 4-column one, unchanged."""
+        eta = 0.0 if eta is None else float(eta)
+        phi = float(phi)
+        if not 0.0 <= eta <= 1.0:
+            raise ValueError(f"eta={eta}: stochastic DDIM takes 0 <= eta <= 1")
+        if not 0.0 <= phi <= 1.0:
+            raise ValueError(f"guidance_rescale={phi}: the rescale factor is a mix of two predictions, 0 <= guidance_rescale <= 1")
+        if eta == 0.0 and phi == 0.0:
+            rows = [self.coefficients(int(t)) for t in timesteps]
+            return torch.tensor(rows, dtype=torch.float32, device=device)
+        if phi > 0.0 and n < 2:
+            raise ValueError(f"guidance_rescale={phi} needs the element count of one clip's prediction (n >= 2), got n={n}")
+        rows = [tuple(self.eta_coefficients(int(t), eta)) + (phi, float(n), 0.0) for t in timesteps]
+        for t, r in zip(timesteps, rows):
+            # (the row lives on the device, where the kernel's entry point cannot see it: the singular cases are refused here)
+            if (self.prediction == ops.PRED_EPSILON and r[0] == 0.0) or (self.prediction == ops.PRED_SAMPLE and r[1] == 0.0):
+                raise ValueError(f"prediction type {self.config.prediction_type!r} is singular at timestep {int(t)}")
+            if not all(math.isfinite(c) for c in r):
+                raise ValueError(f"non-finite step coefficients at timestep {int(t)}: {r}")
         return torch.tensor(rows, dtype=torch.float32, device=device)
 
     def step(self, model_output, timestep, sample, eta: float = 0.0, use_clipped_model_output=False, generator=None,

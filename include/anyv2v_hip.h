@@ -340,6 +340,35 @@ int anyv2v_cfg_ddim_step_f16(const void* Vtok, int32_t ldv, int32_t b_unc, int32
                              const float* coef, const void* lat, void* out, int32_t C, int32_t F, int32_t HW,
                              void* stream);
 
+/* Statistics for the guidance rescale (Lin et al. 3.4; rescale_noise_cfg, consisti2v/consisti2v/pipelines/pipeline_video_editing.py:50-61,
+ * replaces its two `.std()` reductions, :55-56) of ONE clip's prediction, read from the same tokens anyv2v_cfg_ddim_step_f16 reads:
+ * the text branch e_txt = Vtok[b_cond] and the guided prediction g = fp16(e_unc + fp16(G * fp16(e_txt - e_unc))), n = C F HW elements
+ * each.  A fixed grid of ANYV2V_GUIDANCE_STATS_BLOCKS blocks x ANYV2V_GUIDANCE_STATS_THREADS threads strides over the F HW pixels;
+ * block b writes record b, ANYV2V_GUIDANCE_STATS_RECORD floats {S_txt, Q_txt, S_cfg, Q_cfg, K_txt, K_cfg, 0, 0} with S = sum(x - K),
+ * Q = sum((x - K)^2) in fp32 about the pivot K = the tensor's first element.  No atomics, nothing depends on the device: the
+ * records are bit-reproducible.  records: ANYV2V_GUIDANCE_STATS_BLOCKS * ANYV2V_GUIDANCE_STATS_RECORD floats, 16-byte aligned; b_unc >= 0. */
+#define ANYV2V_GUIDANCE_STATS_BLOCKS 64
+#define ANYV2V_GUIDANCE_STATS_THREADS 256
+#define ANYV2V_GUIDANCE_STATS_RECORD 8
+int anyv2v_guidance_stats_f16(const void* Vtok, int32_t ldv, int32_t b_unc, int32_t b_cond, float guidance, float* records,
+                              int32_t C, int32_t F, int32_t HW, void* stream);
+
+/* anyv2v_cfg_ddim_step_f16 with the sampler options of the reference's call (pipeline_i2vgen_xl.py:868,1173 `scheduler.step(noise_pred,
+ * t, latents, **extra_step_kwargs)` with eta > 0 -- seine/diffusion/gaussian_diffusion.py:583-599 is the in-tree statement of that
+ * step -- and pipeline_video_editing.py:685-688 `rescale_noise_cfg(noise_pred, noise_pred_text, guidance_rescale)`):
+ *   g  as above (b_unc < 0: e_txt);   g' = fp16(g * s), s = phi * std_txt / std_cfg + (1 - phi), when phi > 0 and b_unc >= 0, else g
+ *   x0 / eps from g' by `prediction` (0 v_prediction, 1 epsilon, 2 sample; as anyv2v_guided_step_f16)
+ *   out = fp16(c_x0 * x0 + c_eps * eps + sigma * noise)          one rounding
+ * row: 8 floats on the device {sa_t, sb_t, c_x0, c_eps, sigma, phi, n, 0} (n = C F HW), rewritten per step by the host.  Every block
+ * folds the records of anyv2v_guidance_stats_f16 in fp64, in record order, into the unbiased standard deviations (n - 1, torch.std).
+ * `phi` is the host's copy of row[5], checked here (0 <= phi <= 1; phi > 0 with guidance needs `records` and n >= 2); records may be
+ * NULL when phi == 0, noise (planar fp16 like lat) may be NULL when sigma is 0 for the whole run.  The caller keeps epsilon prediction
+ * away from sa_t = 0 and sample prediction from sb_t = 0 (the row lives on the device).  With phi = 0 and sigma = 0 and v-prediction
+ * the result equals anyv2v_cfg_ddim_step_f16's bit for bit.  lat/out: [1, C, F, H, W] fp16; out may alias lat. */
+int anyv2v_cfg_ddim_step_ex_f16(const void* Vtok, int32_t ldv, int32_t b_unc, int32_t b_cond, float guidance, int32_t prediction,
+                                const float* row, const float* records, float phi, const void* noise, const void* lat, void* out,
+                                int32_t C, int32_t F, int32_t HW, void* stream);
+
 /* Plain elementwise DDIM / inverse-DDIM step (eta = 0, v-prediction) on same-layout tensors:
  * the generic `scheduler.step(model_output, t, sample).prev_sample` (pipeline_i2vgen_xl.py:868,1173,1418). */
 int anyv2v_ddim_step_f16(const void* V, const void* X, void* Y, float sa_t, float sb_t, float sa_p, float sb_p,
