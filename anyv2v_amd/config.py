@@ -106,6 +106,28 @@ def sampler_options(config) -> tuple:
     return one("eta"), one("guidance_rescale")
 
 
+def masked_edit_options(config):
+    """(edit_mask_path, grow, feather) of a PnP-edit configuration, or None: three OPTIONAL keys the reference's files do not have --
+    ``edit_mask_path`` (one PNG, or a directory of ``%05d.png`` files; white = edit, black = keep the source), ``edit_mask_grow`` (latent
+    pixels, integer 0 .. 8) and ``edit_mask_feather`` (sigma in latent pixels, 0 .. 8) -- for ``I2VGenXLPipeline.enable_masked_edit``.
+    Without ``edit_mask_path`` (absent or null) the entry runs and writes exactly what it did before the keys existed; grow / feather
+    without a path are refused, not dropped."""
+    def one(key):
+        return config.get(key, None) if hasattr(config, "get") else getattr(config, key, None)
+    path, grow, feather = one("edit_mask_path"), one("edit_mask_grow"), one("edit_mask_feather")
+    if path is None:
+        if grow is not None or feather is not None:
+            raise ValueError("edit_mask_grow / edit_mask_feather without edit_mask_path: there is no mask to grow or feather")
+        return None
+    grow = 0 if grow is None else grow
+    feather = 0.0 if feather is None else float(feather)
+    if isinstance(grow, bool) or not 0 <= grow <= 8 or int(grow) != grow:   # (the range check also refuses NaN)
+        raise ValueError(f"edit_mask_grow={grow}: an integer, 0 <= edit_mask_grow <= 8")
+    if not 0.0 <= feather <= 8.0:   # (also refuses NaN)
+        raise ValueError(f"edit_mask_feather={feather}: 0 <= edit_mask_feather <= 8")
+    return str(path), int(grow), feather
+
+
 def _rebind(cfg: Config, root: Config):
     object.__setattr__(cfg, "_root", root)
     for v in cfg._data.values():

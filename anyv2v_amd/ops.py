@@ -564,6 +564,53 @@ def cfg_ddim_step_ex(vtok: torch.Tensor, b_unc: int, b_cond: int, guidance: floa
     return out
 
 
+def gaussian_taps(sigma: float):
+    """The feather's taps for ``latent_mask``: ``exp(-k^2 / (2 sigma^2)) / sum`` for k = -R .. R, R = ceil(3 sigma), computed in fp64 and
+    rounded to fp32 -> list of 2 R + 1 Python floats that are exactly fp32 values ([] for sigma = 0: no feather)."""
+    import math
+    sigma = float(sigma)
+    if not 0.0 <= sigma <= _lib.MASK_MAX_RADIUS / 3.0:   # (also refuses NaN)
+        raise ValueError(f"feather={sigma}: 0 <= feather <= {_lib.MASK_MAX_RADIUS // 3} latent pixels")
+    R = int(math.ceil(3.0 * sigma))
+    if R == 0:
+        return []
+    raw = [math.exp(-(k * k) / (2.0 * sigma * sigma)) for k in range(-R, R + 1)]
+    total = math.fsum(raw)
+    return [C.c_float(v / total).value for v in raw]
+
+
+def latent_mask(mask: torch.Tensor, grow: int = 0, sigma: float = 0.0, out: Optional[torch.Tensor] = None):
+    """Pixel mask [Fm, H, W] fp16 in [0, 1] -> latent mask [Fm, H / 8, W / 8] fp16 (``anyv2v_latent_mask_f16``): 8 x 8 mean, grown by
+    ``grow`` latent pixels (window maximum), feathered by a Gaussian of ``sigma`` latent pixels.  Once per clip, outside any graph."""
+    lib = _lib.load()
+    assert mask.dim() == 3 and mask.dtype == torch.float16 and mask.is_contiguous(), f"latent_mask: contiguous fp16 [Fm, H, W] expected, got {tuple(mask.shape)} {mask.dtype}"
+    Fm, H, W = mask.shape
+    taps = gaussian_taps(sigma)
+    R = len(taps) // 2
+    if out is None:
+        out = torch.empty((Fm, H // 8, W // 8), dtype=torch.float16, device=mask.device)
+    assert out.dtype == torch.float16 and out.is_contiguous() and tuple(out.shape) == (Fm, H // 8, W // 8) and out.device == mask.device
+    ws = torch.empty(2 * out.numel(), dtype=torch.float32, device=mask.device)
+    arr = (C.c_float * len(taps))(*taps) if taps else None
+    _lib.check(lib.anyv2v_latent_mask_f16(_p(mask), Fm, H, W, int(grow), arr, R, _p(ws), _p(out), _stream()), "anyv2v_latent_mask_f16")
+    return out
+
+
+def masked_blend(x: torch.Tensor, src: torch.Tensor, mask: torch.Tensor, out: Optional[torch.Tensor] = None):
+    """``out = mask == 0 ? src : mask == 1 ? x : fp16(fmaf(mask, x - src, src))`` (``anyv2v_masked_blend_f16``): x / src / out
+    [1, C, F, h, w] fp16, mask [Fm, h, w] fp16 with Fm 1 or F, broadcast over the channels.  ``out`` may be ``x`` (in place)."""
+    lib = _lib.load()
+    if out is None:
+        out = torch.empty_like(x)
+    for t in (x, src, out):
+        assert t.dtype == torch.float16 and t.is_contiguous() and t.dim() == 5 and t.shape[0] == 1 and t.shape == x.shape and t.device == x.device
+    _, Cc, F, H, W = x.shape
+    assert mask.dtype == torch.float16 and mask.is_contiguous() and mask.dim() == 3 and tuple(mask.shape[1:]) == (H, W) and mask.device == x.device, \
+        f"masked_blend: mask {tuple(mask.shape)} {mask.dtype} against latents {tuple(x.shape)}"
+    _lib.check(lib.anyv2v_masked_blend_f16(_p(x), _p(src), _p(mask), mask.shape[0], _p(out), Cc, F, H * W, _stream()), "anyv2v_masked_blend_f16")
+    return out
+
+
 def ddim_step(v: torch.Tensor, x: torch.Tensor, sa_t: float, sb_t: float, sa_p: float, sb_p: float, out=None):
     lib = _lib.load()
     v = v.to(torch.float16).contiguous()

@@ -94,8 +94,13 @@ class _StepEngine:
     """
 
     def __init__(self, pipe, sample, cond, b_unc, b_cond, guidance, dup_slots, shared_stem=False, batch_hint=None, lat_slots=None,
-                 stochastic=False, rescale=0.0):
+                 stochastic=False, rescale=0.0, blend=None):
         self.pipe, self.unet = pipe, pipe.unet
+        # masked edit (``enable_masked_edit``): static buffers (partner latent [1, 4, F, h, w], latent mask [Fm, h, w]) the captured step
+        # blends the latent slot against, behind the update.  The caller owns them -- the three-branch engine and its [negative, editing]
+        # twins step the SAME latent and share one pair -- and refills the partner before every step.  None: nothing is launched
+        self.blend = None if blend is None else tuple(blend)
+        assert not (self.blend is not None and lat_slots is not None), "the batched inversion has no masked edit"
         # sampler options (``_SamplerOptions``): with either one on, the step is ``ops.cfg_ddim_step_ex`` on an 8-float coefficient row
         # (+ ``ops.guidance_stats`` in front of it under the rescale); with both off, nothing below differs from the default engine
         self.stochastic, self.rescale = bool(stochastic), float(rescale)
@@ -195,17 +200,28 @@ class _StepEngine:
                                  stats=self.gstats, phi=self.rescale if self.gstats is not None else 0.0, noise=self.noise)
         else:
             ops.cfg_ddim_step(vtok, b_unc, b_cond, self.guidance, self.coef, lat, lat)
+        if self.blend is not None:
+            ops.masked_blend(lat, self.blend[0], self.blend[1], out=lat)   # in place, before the copies: every slot gets the blended latent
         for s in self.dup_slots:
             self.sample[s].copy_(self.sample[L])
 
-    def step(self, t_row: torch.Tensor, coef_row: torch.Tensor, key: tuple, noise: Optional[torch.Tensor] = None):
-        """``noise``: this step's variance noise (a stochastic engine needs a fresh draw for every step)."""
+    def step(self, t_row: torch.Tensor, coef_row: torch.Tensor, key: tuple, noise: Optional[torch.Tensor] = None,
+             partner: Optional[torch.Tensor] = None):
+        """``noise``: this step's variance noise (a stochastic engine needs a fresh draw for every step).  ``partner``: the latent a
+        masked edit keeps outside the mask after THIS step (the source at the level the step arrives at)."""
         with ops.workspace_slot(getattr(self.pipe, "ws_slot", 0)):
-            self._step(t_row, coef_row, key, noise)
+            if partner is None:
+                self._step(t_row, coef_row, key, noise)   # (the call of an engine without a mask, as it always was)
+            else:
+                self._step(t_row, coef_row, key + ("blend",), noise, partner)   # (the graph of a masked step holds the blend launch)
 
-    def _step(self, t_row: torch.Tensor, coef_row: torch.Tensor, key: tuple, noise=None):
+    def _step(self, t_row: torch.Tensor, coef_row: torch.Tensor, key: tuple, noise=None, partner=None):
         self.ctx.t_buf.copy_(t_row, non_blocking=True)
         self.coef.copy_(coef_row, non_blocking=True)
+        if getattr(self, "blend", None) is not None:
+            if partner is None:
+                raise ValueError("a masked step engine needs the step's partner latent: replaying the buffer would blend against the last step's")
+            self.blend[0].copy_(partner.reshape(self.blend[0].shape), non_blocking=True)
         if self.stochastic:
             if noise is None:
                 raise ValueError("a stochastic step engine needs the step's variance noise: replaying the buffer would repeat the last draw")
@@ -253,6 +269,7 @@ class I2VGenXLPipeline:
         self.vae_scale_factor = 8
         self._guidance_scale = 1.0
         self._guidance_rescale = 0.0   # ``enable_guidance_rescale``
+        self._masked_edit = None       # ``enable_masked_edit``: the mask and clean latent of the clip being edited
         self._device = torch.device("cpu")
         self._engines: Dict[tuple, _StepEngine] = {}  # step engines (static buffers + HIP graphs) kept across clips, LRU
         # pacing hooks of the clip pipeline (run_group_anyv2v): ``pace_record(i, n)`` is called when edit step i of n is about to be
@@ -546,6 +563,74 @@ class I2VGenXLPipeline:
     def disable_guidance_rescale(self):
         self._guidance_rescale = 0.0
 
+    def enable_masked_edit(self, mask, source_latents, grow: int = 0, feather: float = 0.0):
+        """Local editing: ``sample_with_pnp`` keeps the source clip outside ``mask``, bit for bit.  After every DDIM update the edit latent
+        is blended against the source at the same noise level -- the inversion trajectory's entry, after the last step ``source_latents``
+        (``encode_vae_video`` of the source frames: the trajectory does not hold the clean latent) -- by ``ops.masked_blend`` inside the
+        captured step ("Masked edit").  ``mask``: [Fm, H, W] or [H, W] at the PIXEL size of the call, Fm 1 (every frame) or
+        the frame count; bool, uint8 (image scale: 255 = edit) or float in [0, 1]; 1 = edit, 0 = keep.  ``grow``: latent pixels (0 .. 8) the
+        edit region is dilated by; ``feather``: sigma (0 .. 8 latent pixels) of the Gaussian that softens its border.  A property of the
+        clip, not of the pipeline: set it per edit and clear it (``disable_masked_edit``) afterwards; ``__call__`` and ``invert`` refuse to
+        run while it is set.  A setter, not a call argument: the reference's signatures have none."""
+        from . import _lib
+        if getattr(self.unet, "frame_parallel", None) is not None:
+            raise NotImplementedError("masked edit on a frame-parallel clip: every rank would need its frames of the mask and of the partner latents")
+        if not torch.is_tensor(mask) or mask.dim() not in (2, 3):
+            raise ValueError(f"edit mask: a [Fm, H, W] or [H, W] tensor expected, got {type(mask).__name__}"
+                             + (f" of shape {tuple(mask.shape)}" if torch.is_tensor(mask) else ""))
+        if mask.dtype == torch.bool:
+            m = mask.to(torch.float16)
+        elif mask.dtype == torch.uint8:
+            m = (mask.float() / 255.0).to(torch.float16)
+        elif mask.is_floating_point():
+            m = mask.float()
+            if not bool(((m >= 0.0) & (m <= 1.0)).all()):   # (false for NaN)
+                raise ValueError("edit mask: float values must lie in [0, 1] (1 = edit, 0 = keep the source)")
+            m = m.to(torch.float16)
+        else:
+            raise ValueError(f"edit mask: bool, uint8 or float expected, got {mask.dtype}")
+        m = (m[None] if m.dim() == 2 else m).contiguous()
+        if m.shape[1] % self.vae_scale_factor or m.shape[2] % self.vae_scale_factor or m.shape[0] < 1 or m.shape[1] < 8 or m.shape[2] < 8:
+            raise ValueError(f"edit mask: H x W = {m.shape[1]} x {m.shape[2]} must be positive multiples of {self.vae_scale_factor}")
+        if not torch.is_tensor(source_latents) or source_latents.dim() != 5 or source_latents.shape[0] != 1 or \
+                source_latents.shape[1] != 4 or tuple(source_latents.shape[3:]) != (m.shape[1] // 8, m.shape[2] // 8) or \
+                m.shape[0] not in (1, source_latents.shape[2]):
+            raise ValueError("source_latents: [1, 4, F, h, w] expected for a mask of "
+                             f"{tuple(m.shape)} (h = H / 8, w = W / 8, Fm = 1 or F), got "
+                             f"{tuple(source_latents.shape) if torch.is_tensor(source_latents) else type(source_latents).__name__}")
+        if isinstance(grow, bool) or not 0 <= grow <= _lib.MASK_MAX_GROW or int(grow) != grow:   # (the range check also refuses NaN)
+            raise ValueError(f"grow={grow}: an integer, 0 <= grow <= {_lib.MASK_MAX_GROW} latent pixels")
+        feather = float(feather)
+        if not 0.0 <= feather <= _lib.MASK_MAX_RADIUS / 3.0:   # (also refuses NaN)
+            raise ValueError(f"feather={feather}: 0 <= feather <= {_lib.MASK_MAX_RADIUS // 3} latent pixels")
+        self._masked_edit = dict(mask=m, source_latents=source_latents, grow=int(grow), feather=feather)
+
+    def disable_masked_edit(self):
+        self._masked_edit = None
+
+    def _refuse_masked_edit(self, what):
+        """``__call__`` / ``invert``: no source branch, no trajectory to blend against -- a mask left set would be silently dropped."""
+        if getattr(self, "_masked_edit", None) is not None:
+            raise ValueError(f"an edit mask is set (enable_masked_edit): {what} has no source to keep -- only sample_with_pnp blends; call "
+                             "disable_masked_edit() first")
+
+    def _masked_edit_buffers(self, height, width, num_frames, latents):
+        """-> (partner buffer, latent mask, clean source latent) for this ``sample_with_pnp`` call, or None without a mask.  The latent
+        mask is built here, once per clip (three small launches outside any graph)."""
+        me = getattr(self, "_masked_edit", None)
+        if me is None:
+            return None
+        if getattr(self.unet, "frame_parallel", None) is not None:
+            raise NotImplementedError("masked edit on a frame-parallel clip: every rank would need its frames of the mask and of the partner latents")
+        m, src = me["mask"], me["source_latents"]
+        if tuple(m.shape[1:]) != (height, width) or m.shape[0] not in (1, num_frames):
+            raise ValueError(f"edit mask {tuple(m.shape)} does not match the call: [Fm, H, W] = [1 or {num_frames}, {height}, {width}] expected")
+        if tuple(src.shape) != tuple(latents.shape):
+            raise ValueError(f"source_latents {tuple(src.shape)} do not match the call's latents {tuple(latents.shape)}")
+        device = latents.device
+        lm = ops.latent_mask(m.to(device), me["grow"], me["feather"])
+        return torch.zeros_like(latents), lm, src.to(device=device, dtype=torch.float16).contiguous()
+
     def _sampler_options(self, eta, cross_attention_kwargs):
         """-> (stochastic, eta, phi) for the step engines of ``__call__`` / ``sample_with_pnp``.  ``eta`` counts when the scheduler is the
         forward ``DDIMScheduler`` (as ``prepare_extra_step_kwargs``: the inverse scheduler's ``step`` takes none); 0 <= eta <= 1."""
@@ -607,6 +692,9 @@ class I2VGenXLPipeline:
         if kw.get("stochastic") or kw.get("rescale"):
             # ... and the launches of its sampler options; with both off the key is the default engine's, unchanged
             key += (("sampler", bool(kw.get("stochastic")), float(kw.get("rescale") or 0.0)),)
+        if kw.get("blend") is not None:
+            # ... and the blend launch of a masked edit, on buffers of this mask geometry; without a mask the key is unchanged
+            key += (("blend", tuple(kw["blend"][1].shape)),)
         eng = self._engines.pop(key, None)
         if eng is None or not eng.rebind(sample, cond):
             eng = _StepEngine(self, sample, cond, **kw)
@@ -641,6 +729,7 @@ class I2VGenXLPipeline:
         height = height or self.unet.config.sample_size * self.vae_scale_factor
         width = width or self.unet.config.sample_size * self.vae_scale_factor
         self.check_inputs(prompt, image, height, width, negative_prompt, prompt_embeds, negative_prompt_embeds)
+        self._refuse_masked_edit("invert")
         device = self._execution_device
         self._guidance_scale = guidance_scale
         pnp_utils.clear_time(self)  # inversion never injects (stage 1 of the reference runs without hooks)
@@ -698,6 +787,7 @@ class I2VGenXLPipeline:
         once per step for all of them and the low-resolution launches carry B times the rows: an inversion-bound job (the template's
         500 steps) gains what a B = 1 launch loses against a B = 3 one.  Returns one ``LatentTrajectory`` per clip; the numbers
         differ from ``invert`` at rounding level (other launch plans at other row counts), not bit for bit."""
+        self._refuse_masked_edit("invert_clips")
         device = self._execution_device
         self._guidance_scale = 1.0
         pnp_utils.clear_time(self)
@@ -747,6 +837,7 @@ class I2VGenXLPipeline:
         height = height or self.unet.config.sample_size * self.vae_scale_factor
         width = width or self.unet.config.sample_size * self.vae_scale_factor
         self.check_inputs(prompt, image, height, width, negative_prompt, prompt_embeds, negative_prompt_embeds)
+        self._refuse_masked_edit("__call__")
         device = self._execution_device
         self._guidance_scale = guidance_scale
         pe, npe, ie, il = self._conditioning(prompt, image, height, width, num_frames, negative_prompt, prompt_embeds,
@@ -837,12 +928,20 @@ class I2VGenXLPipeline:
         sample = latents.repeat(nb, 1, 1, 1, 1).contiguous()
         cond = dict(encoder_hidden_states=ehs.contiguous(), fps=fps, image_latents=il_all.contiguous(),
                     image_embeddings=ie_all.contiguous())
+        # masked edit (``enable_masked_edit``): the latent mask of this clip and the buffer of the per-step partner; one more engine option
+        masked = self._masked_edit_buffers(height, width, num_frames, latents)
+        if masked is not None:
+            opts = dict(opts, blend=masked[:2])
         # the source branch's prediction is never read (:1136,1160-1162): its forward may stop behind the last hook site (exact)
         drop_tail = cfg_on and nb == 3 and os.environ.get("ANYV2V_DROP_SRC_TAIL", "1") == "1"
         eng = self._engine("pnp-droptail" if drop_tail else "pnp", sample, cond, b_unc=1 if cfg_on else -1, b_cond=nb - 1,
                            guidance=guidance_scale, dup_slots=range(1, nb - 1), shared_stem=cfg_on, **opts)
         eng.drop_src_tail = drop_tail
         sample = eng.sample
+        if masked is not None and eng.blend[1] is not masked[1]:
+            # a cached engine: its graphs were captured on ITS buffers -- this clip's latent mask goes into them
+            eng.blend[1].copy_(masked[1])
+            opts["blend"] = eng.blend
         # source trajectory resident in HBM (in-memory hand-off from invert(), or read once from the reference's files)
         if isinstance(ddim_inv_latents_path, LatentTrajectory):
             traj = ddim_inv_latents_path
@@ -885,6 +984,10 @@ class I2VGenXLPipeline:
             pnp_utils.register_time(self, t)  # host-side only: python int, no device sync (:1143)
             state = pnp_utils.injection_state(self)
             noise = self._variance_noise(stochastic, sample[nb - 1:nb], generator)   # one draw per step, whichever engine runs it
+            # masked edit: after this step the edit latent sits at level ts[i + 1] -- its partner is the source at that level, the clean
+            # latent after the last step.  Copied into the static buffer outside the graph, whichever engine runs the step
+            extra = {} if masked is None else dict(partner=(
+                load_ddim_latents_at_t(ts[i + 1], traj).to(device=device, dtype=torch.float16) if i + 1 < len(ts) else masked[2]))
             if any(state) and nb != 3:
                 # the hooks slice the batch in thirds (pnp_utils.py:111,166,272); with guidance_scale <= 1 the reference
                 # builds a 2-way batch and silently injects the wrong rows -- refuse instead
@@ -897,7 +1000,7 @@ class I2VGenXLPipeline:
                         eng.nosrc = _StepEngine(self, sample[1:], cond2, b_unc=0, b_cond=1, guidance=guidance_scale,
                                                 dup_slots=[0], shared_stem=True, batch_hint=(3, 2), **opts)
                     eng_nosrc, nosrc_bound = eng.nosrc, True
-                eng_nosrc.step(t_table[i, 1:], coef_table[i], key=("pnp-nosrc",), noise=noise)
+                eng_nosrc.step(t_table[i, 1:], coef_table[i], key=("pnp-nosrc",), noise=noise, **extra)
             elif cache is not None and cache.has(t, state):
                 # replay: the source features of this step are in HBM -- [negative, editing] only
                 names = [n for (n, _, _), on in zip(sites, state) if on]
@@ -910,7 +1013,7 @@ class I2VGenXLPipeline:
                 for n in names:
                     eng.site_bufs[n].copy_(cache.steps[(int(t), state)][n], non_blocking=True)
                 set_io("replay", names)
-                eng_nosrc.step(t_table[i, 1:], coef_table[i], key=("pnp-replay",) + state, noise=noise)
+                eng_nosrc.step(t_table[i, 1:], coef_table[i], key=("pnp-replay",) + state, noise=noise, **extra)
                 set_io(None, ())
                 cache.replayed_steps += 1
             else:
@@ -918,11 +1021,11 @@ class I2VGenXLPipeline:
                 if cache is not None:
                     names = [n for (n, _, _), on in zip(sites, state) if on]
                     set_io("record", names)
-                    eng.step(t_table[i], coef_table[i], key=("pnp-record",) + state, noise=noise)
+                    eng.step(t_table[i], coef_table[i], key=("pnp-record",) + state, noise=noise, **extra)
                     set_io(None, ())
                     cache.recorded_steps += bool(cache.store(t, state, {n: eng.site_bufs[n] for n in names}))
                 else:
-                    eng.step(t_table[i], coef_table[i], key=("pnp",) + state, noise=noise)
+                    eng.step(t_table[i], coef_table[i], key=("pnp",) + state, noise=noise, **extra)
             if latents_trace is not None:
                 latents_trace[t] = sample[nb - 1:nb].clone()
         return self._finish(sample[nb - 1:nb].clone(), output_type, decode_chunk_size, return_dict)

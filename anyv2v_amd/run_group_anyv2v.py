@@ -6,7 +6,8 @@ Every file of both stages is still written (same names, same formats), so the ou
 run; an edit entry whose inversion was skipped here (directory already complete) reads the files as stage 2 alone would.
 The edit template / entries take the optional sampler keys of stage 2 (``eta``, ``guidance_rescale``; ``config.sampler_options``): the
 inversion ignores them, and an edit that draws variance noise draws it inside its own seeded entry, so the two-stream order below
-still writes what the serial order writes.
+still writes what the serial order writes.  The masked-edit keys (``edit_mask_path`` / ``_grow`` / ``_feather``; ``config.masked_edit_options``)
+are stage 2's as well: ``Stage2.entry`` encodes the source frames it loads into the clean latent the last blend needs, on its own stream.
 
     python -m anyv2v_amd.run_group_anyv2v --inversion_template configs/group_ddim_inversion/template.yaml \\
         --inversion_configs_json configs/group_ddim_inversion/group_config.json \\

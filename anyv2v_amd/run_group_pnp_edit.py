@@ -19,14 +19,14 @@ from pathlib import Path
 import torch
 from PIL import Image
 
-from .config import OmegaConf, sampler_options
+from .config import OmegaConf, masked_edit_options, sampler_options
 from .encoders import attach_synthetic_encoders
 from .parallel import FrameParallel, gather_latents, init_distributed, seed_for_entry, shard_entries
 from .pipeline import I2VGenXLPipeline
 from .pnp_utils import register_conv_injection, register_spatial_attention_pnp, register_temp_attention_pnp
 from .schedulers import DDIMScheduler
-from .utils import (LatentTrajectory, convert_video_to_frames, export_to_gif, export_to_video, load_ddim_latents_at_t, load_image,
-                    load_video_frames, seed_everything)
+from .utils import (LatentTrajectory, convert_video_to_frames, export_to_gif, export_to_video, load_ddim_latents_at_t, load_edit_mask,
+                    load_image, load_video_frames, seed_everything)
 
 MODEL_ID = "ali-vilab/i2vgen-xl"
 
@@ -50,9 +50,12 @@ def output_suffix(config, ddim_init_latents_t_idx) -> str:
     """``run_group_pnp_edit.py:154-167``; the optional sampler keys (``config.sampler_options``) add to the name only when they are on,
     so two entries that differ in them alone do not overwrite each other and every other directory keeps the reference's name."""
     eta, rescale = sampler_options(config)
+    masked = masked_edit_options(config)   # optional keys ``edit_mask_*``: a masked and an unmasked edit do not overwrite each other
+    mask_tag = "" if masked is None else ("_mask-" + os.path.splitext(os.path.basename(os.path.normpath(masked[0])))[0]
+                                          + (f"_grow{masked[1]}" if masked[1] > 0 else "") + (f"_feather{masked[2]}" if masked[2] > 0 else ""))
     return ("ddim_init_latents_t_idx_" + str(ddim_init_latents_t_idx) + "_nsteps_" + str(config.n_steps) + "_cfg_"
             + str(config.cfg) + "_pnpf" + str(config.pnp_f_t) + "_pnps" + str(config.pnp_spatial_attn_t) + "_pnpt"
-            + str(config.pnp_temp_attn_t) + (f"_eta{eta}" if eta > 0 else "") + (f"_rescale{rescale}" if rescale > 0 else ""))
+            + str(config.pnp_temp_attn_t) + (f"_eta{eta}" if eta > 0 else "") + (f"_rescale{rescale}" if rescale > 0 else "") + mask_tag)
 
 
 class Stage2:
@@ -148,6 +151,15 @@ class Stage2:
                     config.ddim_latents_path, device=device, timesteps=[int(t) for t in ddim_scheduler.timesteps[t_idx:]])
             traj = loaded_trajectories[tkey]
         ddim_latents_at_t = load_ddim_latents_at_t(ddim_scheduler.timesteps[t_idx], traj)
+        # masked edit (optional keys ``edit_mask_path`` / ``_grow`` / ``_feather``): the mask at the frames' size and the clean latent of the
+        # source frames loaded above -- the partner of the last step, which the trajectory does not hold.  Encoded under the template's
+        # seed BEFORE the entry is seeded below, so the draws of the edit itself are the ones of an unmasked entry.
+        masked = masked_edit_options(config)
+        if masked is not None:
+            mask = load_edit_mask(os.path.join(config.data_dir, masked[0]), config.n_frames, tuple(config.image_size))
+            seed_everything(template_config.seed)
+            source_latents = pipe.encode_vae_video(frame_list, device=pipe._execution_device, height=config.image_size[1],
+                                                   width=config.image_size[0])
         seed_everything(seed_for_entry(template_config.seed, entry_idx) if self.e_world > 1 else template_config.seed)
         random_latents = torch.randn(ddim_latents_at_t.shape, dtype=torch.float32).to(ddim_latents_at_t)  # drawn even if unused (:124)
         logger.info(f"Blending random_ratio (1 means random latent): {config.random_ratio}")
@@ -158,13 +170,18 @@ class Stage2:
         pipe.auto_vae_tiling(config.image_size[1], config.image_size[0])
         eta, rescale = sampler_options(config)   # optional keys ``eta`` / ``guidance_rescale``; absent: (0, 0), the default engines
         pipe.enable_guidance_rescale(rescale)
-        edited_latents = pipe.sample_with_pnp(
-            prompt=config.editing_prompt, image=edited_1st_frame, height=config.image_size[1], width=config.image_size[0],
-            num_frames=config.n_frames, num_inference_steps=config.n_steps, guidance_scale=config.cfg,
-            negative_prompt=config.editing_negative_prompt, eta=eta, target_fps=config.target_fps, latents=mixed_latents,
-            generator=torch.manual_seed(config.seed), return_dict=True, ddim_init_latents_t_idx=t_idx,
-            ddim_inv_latents_path=traj, ddim_inv_prompt=config.ddim_inv_prompt, ddim_inv_1st_frame=src_1st_frame,
-            output_type="latent").frames
+        if masked is not None:
+            pipe.enable_masked_edit(mask, source_latents, grow=masked[1], feather=masked[2])   # (refuses a frame-parallel clip)
+        try:
+            edited_latents = pipe.sample_with_pnp(
+                prompt=config.editing_prompt, image=edited_1st_frame, height=config.image_size[1], width=config.image_size[0],
+                num_frames=config.n_frames, num_inference_steps=config.n_steps, guidance_scale=config.cfg,
+                negative_prompt=config.editing_negative_prompt, eta=eta, target_fps=config.target_fps, latents=mixed_latents,
+                generator=torch.manual_seed(config.seed), return_dict=True, ddim_init_latents_t_idx=t_idx,
+                ddim_inv_latents_path=traj, ddim_inv_prompt=config.ddim_inv_prompt, ddim_inv_1st_frame=src_1st_frame,
+                output_type="latent").frames
+        finally:
+            pipe.disable_masked_edit()   # the mask belongs to this entry's clip, not to the pipeline
         self.my_latents[entry_idx] = edited_latents
         self.lat_shape = tuple(edited_latents.shape)
         rng = _RngState(device)

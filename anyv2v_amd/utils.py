@@ -193,6 +193,26 @@ def load_video_frames(frames_path, n_frames, image_size=(512, 512)):
     return paths, frames
 
 
+def load_edit_mask(mask_path, n_frames, image_size=(512, 512)):
+    """The edit mask of a masked PnP edit (``config.masked_edit_options``): one PNG (every frame) or a directory of ``%05d.png`` files
+    (one per frame) -> uint8 tensor [1 or n_frames, H, W], 255 = edit (white), 0 = keep the source.  The size must equal
+    ``image_size`` (width, height), as for the frames (``load_video_frames``): a resampled mask would move the border."""
+    if os.path.isdir(mask_path):
+        paths = [os.path.join(mask_path, "%05d.png" % i) for i in range(n_frames)]
+    else:
+        paths = [mask_path]
+    planes = []
+    for p in paths:
+        if not os.path.isfile(p):
+            raise ValueError(f"edit mask {p} not found")
+        img = Image.open(p).convert("L")
+        if img.size != tuple(image_size):
+            logger.error(f"Edit mask size {img.size} does not match config.image_size {image_size}")
+            raise ValueError(f"Edit mask size {img.size} does not match config.image_size {image_size}")
+        planes.append(torch.from_numpy(np.array(img, dtype=np.uint8)))
+    return torch.stack(planes)
+
+
 def isinstance_str(x: object, cls_name: str):
     """``consisti2v/utils.py:13-25`` / ``seine/utils.py``: does ``x`` have a class NAMED ``cls_name`` in its ancestry."""
     return any(c.__name__ == cls_name for c in type(x).__mro__)

@@ -369,6 +369,35 @@ int anyv2v_cfg_ddim_step_ex_f16(const void* Vtok, int32_t ldv, int32_t b_unc, in
                                 const float* row, const float* records, float phi, const void* noise, const void* lat, void* out,
                                 int32_t C, int32_t F, int32_t HW, void* stream);
 
+/* Masked PnP editing -- the source clip kept outside an edit mask.  Nothing in the reference does this; the technique is the latent
+ * blending of Blended Latent Diffusion (arXiv 2206.02779) and of diffusers' 4-channel inpaint loop, which these two entry points replace:
+ *   init_mask = torch.nn.functional.interpolate(mask, size=(height // vae_scale_factor, width // vae_scale_factor))
+ *   latents = (1 - init_mask) * init_latents_proper + init_mask * latents       (pipeline_stable_diffusion_inpaint.py, prepare_mask_latents
+ *                                                                                and the end of the denoising loop's body)
+ * with the inverted latent of the source (the resident trajectory) in the place of the re-noised `init_latents_proper`.
+ *
+ * anyv2v_latent_mask_f16: pixel mask [mask_frames, H, W] fp16 in [0, 1] (1 = edit, 0 = keep; clamped, NaN counts as 0) -> latent mask
+ * out [mask_frames, H / 8, W / 8] fp16.  Three stages in fp32, ONE rounding to fp16 at the end, one launch per stage that is on:
+ *   1. pool    the mean over each 8 x 8 block: the 64 values are summed exactly (integers in units of 2^-24) and the sum is rounded to
+ *              fp32 once -- the correctly rounded mean; a binary mask gives k / 64 exactly;
+ *   2. grow    (grow > 0) the maximum over the (2 grow + 1)^2 window, positions outside the image ignored; 0 <= grow <= ANYV2V_MASK_MAX_GROW;
+ *   3. feather (R > 0) separable Gaussian with replicate padding, out[y, x] = sum_j t[j] (sum_i t[i] in[y + j, x + i]) by fmaf in tap
+ *              order; taps: 2 R + 1 floats ON THE HOST (exp(-k^2 / (2 sigma^2)) / sum in fp64, rounded to fp32; R = ceil(3 sigma)),
+ *              checked here and handed to the kernel by value; 0 <= R <= ANYV2V_MASK_MAX_RADIUS.  A window wider than the image is fine.
+ * workspace: 2 * mask_frames * (H / 8) * (W / 8) floats on the device.  No atomics.  Runs once per clip, outside any captured graph.
+ *
+ * anyv2v_masked_blend_f16: x / src / out [1, C, F, HW] fp16, mask [mask_frames, HW] fp16 (mask_frames 1 or F; broadcast over C, and over
+ * F when 1); per element, with m the mask value:
+ *   m == 0 -> src      m == 1 -> x      (selects: the dropped operand may hold Inf / NaN)      else fp16(fmaf(m, x - src, src)) in fp32
+ * out may alias x (the step engines blend the latent slot in place), nothing else.  16-byte accesses when HW % 8 == 0 and all four
+ * pointers are 16-byte aligned, a scalar kernel otherwise -- chosen here, on the host. */
+#define ANYV2V_MASK_MAX_GROW 8
+#define ANYV2V_MASK_MAX_RADIUS 24
+int anyv2v_latent_mask_f16(const void* mask, int32_t mask_frames, int32_t H, int32_t W, int32_t grow, const float* taps, int32_t R,
+                           float* workspace, void* out, void* stream);
+int anyv2v_masked_blend_f16(const void* x, const void* src, const void* mask, int32_t mask_frames, void* out, int32_t C, int32_t F,
+                            int32_t HW, void* stream);
+
 /* Plain elementwise DDIM / inverse-DDIM step (eta = 0, v-prediction) on same-layout tensors:
  * the generic `scheduler.step(model_output, t, sample).prev_sample` (pipeline_i2vgen_xl.py:868,1173,1418). */
 int anyv2v_ddim_step_f16(const void* V, const void* X, void* Y, float sa_t, float sb_t, float sa_p, float sb_p,
@@ -410,7 +439,8 @@ const char* anyv2v_last_error(void);
  * _apply_pivot_f16 (the earlier pair is unchanged).  105: AnyV2VGemmDesc grew gn_stats / gn_stats_floats / gn_rows_per_group /
  * gn_groups (GroupNorm statistics from the GEMM epilogue), anyv2v_gemm_gn_stats_floats, anyv2v_gemm_gn_launches,
  * anyv2v_groupnorm_stats_floats, anyv2v_groupnorm_apply_stats_f16; nothing earlier changed (a 104 caller that zero-initialises its descriptors, as required,
- * must still be recompiled against this header because the structure grew).  anyv2v_freeu_f16 and anyv2v_tile_blend_f16 were added under 105: new entry points, no structure changed
+ * must still be recompiled against this header because the structure grew).  anyv2v_freeu_f16, anyv2v_tile_blend_f16, anyv2v_latent_mask_f16 and
+ * anyv2v_masked_blend_f16 were added under 105: new entry points, no structure changed
  * (a binding that needs them finds out when it resolves the symbol). */
 #define ANYV2V_ABI_VERSION 105
 int anyv2v_version(void);
