@@ -68,6 +68,8 @@ ANYV2V_GEMM_PROBE_KORDER_SHIFT = 29
 GUIDANCE_STATS_BLOCKS, GUIDANCE_STATS_THREADS, GUIDANCE_STATS_RECORD = 64, 256, 8
 # anyv2v_latent_mask_f16: the largest grow radius and feather radius (ANYV2V_MASK_MAX_* of include/anyv2v_hip.h)
 MASK_MAX_GROW, MASK_MAX_RADIUS = 8, 24
+# anyv2v_diff_map_finish_f16: the fixed grid of the clip mean, one fp32 record per block (ANYV2V_DIFF_MAP_* of include/anyv2v_hip.h)
+DIFF_MAP_BLOCKS, DIFF_MAP_THREADS = 64, 256
 
 
 class FFDesc(C.Structure):
@@ -128,6 +130,8 @@ SYMBOLS = {
     "anyv2v_cfg_ddim_step_ex_f16": (C.c_int, [_VP, _I32, _I32, _I32, _F32, _I32, _VP, _VP, _F32, _VP, _VP, _VP, _I32, _I32, _I32, _VP]),
     "anyv2v_latent_mask_f16": (C.c_int, [_VP, _I32, _I32, _I32, _I32, C.POINTER(C.c_float), _I32, _VP, _VP, _VP]),
     "anyv2v_masked_blend_f16": (C.c_int, [_VP, _VP, _VP, _I32, _VP, _I32, _I32, _I32, _VP]),
+    "anyv2v_diff_map_accum_f16": (C.c_int, [_VP, _I32, _I32, _I32, _I32, _VP, _I32, _VP, _VP]),
+    "anyv2v_diff_map_finish_f16": (C.c_int, [_VP, _I32, _I32, _I32, _F32, _F32, _VP, _VP, _VP, _VP]),
     "anyv2v_ddim_step_f16": (C.c_int, [_VP, _VP, _VP, _F32, _F32, _F32, _F32, _I64, _VP]),
     "anyv2v_guided_step_f16": (C.c_int, [_VP, _I64, _I32, _I32, _I32, _F32, _F32, _I32, _F32, _F32, _F32, _F32, _VP, _VP, _VP]),
     "anyv2v_guided_step_noise_f16": (C.c_int, [_VP, _I64, _I32, _I32, _I32, _F32, _F32, _I32, _F32, _F32, _F32, _F32, _VP, _VP, _VP, _F32, _VP]),

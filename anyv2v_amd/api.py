@@ -20,9 +20,10 @@ from typing import List, Optional
 import torch
 from PIL import Image
 
-from .config import OmegaConf, sampler_options
+from .config import OmegaConf, auto_mask_options, sampler_options
 from .pipeline import I2VGenXLPipeline
 from .run_group_ddim_inversion import ddim_inversion
+from .pnp_utils import clear_time
 from .run_group_pnp_edit import init_pnp
 from .schedulers import DDIMInverseScheduler, DDIMScheduler
 from .utils import export_to_video, load_image, wait_for_pending_writes
@@ -49,7 +50,8 @@ class AnyV2V_I2VGenXL:
     def __init__(self, model_path: str = MODEL_ID, device="cuda:0", tmp_dir: str = "_demo_temp", pipe: Optional[I2VGenXLPipeline] = None,
                  random_init_seed: Optional[int] = None, synthetic_encoders: bool = False) -> None:
         # default inversion / edit configuration of the demo (gradio_demo.py:60-78); ``pnp_config`` also takes the optional keys
-        # ``eta`` / ``guidance_rescale`` (``config.sampler_options``; e.g. ``obj.config.pnp_config.eta = 0.5``), absent = off
+        # ``eta`` / ``guidance_rescale`` (``config.sampler_options``; e.g. ``obj.config.pnp_config.eta = 0.5``) and ``edit_mask_auto`` with
+        # its tuning keys and ``edit_mask_grow`` / ``edit_mask_feather`` (``config.auto_mask_options``), absent = off
         self.config = OmegaConf.create({
             "inverse_config": {"image_size": [512, 512], "n_frames": 16, "cfg": 1.0, "target_fps": 8, "ddim_inv_prompt": "",
                                "prompt": "", "negative_prompt": ""},
@@ -120,17 +122,34 @@ class AnyV2V_I2VGenXL:
         cfg.pnp_config.pnp_spatial_attn_t = spatial_inj
         cfg.pnp_config.pnp_temp_attn_t = temp_inj
         cfg.pnp_config.ddim_init_latents_t_idx = ddim_init_latents_t_idx
-        init_pnp(self.pipe, self.ddim_scheduler, cfg.pnp_config)
         self.pipe.register_modules(scheduler=self.ddim_scheduler)
+        auto = auto_mask_options(cfg.pnp_config)
+        if auto is not None:
+            # automatic edit mask: from the trajectory in HBM (deterministic, one map), before this edit's hooks are registered
+            clear_time(self.pipe)
+            size = dict(height=cfg.inverse_config.image_size[1], width=cfg.inverse_config.image_size[0])
+            source_latents = self.pipe.encode_vae_video(frame_list, device=self.device, **size)
+            mask = self.pipe.generate_edit_mask(
+                prompt=video_prompt, image=edited_1st_frame, ddim_inv_prompt=cfg.inverse_config.ddim_inv_prompt, ddim_inv_1st_frame=first_frame,
+                ddim_inv_latents_path=trajectory, num_frames=cfg.inverse_config.n_frames, target_fps=cfg.pnp_config.target_fps,
+                num_inference_steps=num_inference_steps, num_maps_per_mask=auto["maps"], mask_encode_strength=auto["strength"],
+                mask_thresholding_ratio=auto["ratio"], threshold=auto["threshold"], **size)
+        init_pnp(self.pipe, self.ddim_scheduler, cfg.pnp_config)
         eta, rescale = sampler_options(cfg.pnp_config)
         self.pipe.enable_guidance_rescale(rescale)
-        edited_video = self.pipe.sample_with_pnp(
-            prompt=video_prompt, image=edited_1st_frame, height=cfg.inverse_config.image_size[1],
-            width=cfg.inverse_config.image_size[0], num_frames=cfg.inverse_config.n_frames,
-            num_inference_steps=cfg.pnp_config.n_steps, guidance_scale=guidance_scale, negative_prompt=video_negative_prompt,
-            eta=eta, target_fps=cfg.pnp_config.target_fps, latents=mixed_latents, generator=generator, return_dict=True,
-            ddim_init_latents_t_idx=ddim_init_latents_t_idx, ddim_inv_latents_path=trajectory,
-            ddim_inv_prompt=cfg.inverse_config.ddim_inv_prompt, ddim_inv_1st_frame=first_frame).frames[0]
+        if auto is not None:
+            self.pipe.enable_masked_edit(mask, source_latents, grow=auto["grow"], feather=auto["feather"])
+        try:
+            edited_video = self.pipe.sample_with_pnp(
+                prompt=video_prompt, image=edited_1st_frame, height=cfg.inverse_config.image_size[1],
+                width=cfg.inverse_config.image_size[0], num_frames=cfg.inverse_config.n_frames,
+                num_inference_steps=cfg.pnp_config.n_steps, guidance_scale=guidance_scale, negative_prompt=video_negative_prompt,
+                eta=eta, target_fps=cfg.pnp_config.target_fps, latents=mixed_latents, generator=generator, return_dict=True,
+                ddim_init_latents_t_idx=ddim_init_latents_t_idx, ddim_inv_latents_path=trajectory,
+                ddim_inv_prompt=cfg.inverse_config.ddim_inv_prompt, ddim_inv_1st_frame=first_frame).frames[0]
+        finally:
+            if auto is not None:
+                self.pipe.disable_masked_edit()   # the mask belongs to this clip
         edited_video = [f.resize(tuple(cfg.inverse_config.image_size), resample=Image.LANCZOS) for f in edited_video]
         output_path = os.path.join(tmp_dir, "edited_video.mp4")
         export_to_video(edited_video, output_path, fps=cfg.pnp_config.target_fps)

@@ -106,26 +106,75 @@ def sampler_options(config) -> tuple:
     return one("eta"), one("guidance_rescale")
 
 
-def masked_edit_options(config):
-    """(edit_mask_path, grow, feather) of a PnP-edit configuration, or None: three OPTIONAL keys the reference's files do not have --
-    ``edit_mask_path`` (one PNG, or a directory of ``%05d.png`` files; white = edit, black = keep the source), ``edit_mask_grow`` (latent
-    pixels, integer 0 .. 8) and ``edit_mask_feather`` (sigma in latent pixels, 0 .. 8) -- for ``I2VGenXLPipeline.enable_masked_edit``.
-    Without ``edit_mask_path`` (absent or null) the entry runs and writes exactly what it did before the keys existed; grow / feather
-    without a path are refused, not dropped."""
-    def one(key):
-        return config.get(key, None) if hasattr(config, "get") else getattr(config, key, None)
-    path, grow, feather = one("edit_mask_path"), one("edit_mask_grow"), one("edit_mask_feather")
-    if path is None:
-        if grow is not None or feather is not None:
-            raise ValueError("edit_mask_grow / edit_mask_feather without edit_mask_path: there is no mask to grow or feather")
-        return None
+def _option(config, key):
+    return config.get(key, None) if hasattr(config, "get") else getattr(config, key, None)   # (a ``Config`` or any plain namespace)
+
+
+def _auto_mask_on(config) -> bool:
+    v = _option(config, "edit_mask_auto")
+    if v is not None and not isinstance(v, bool):
+        raise ValueError(f"edit_mask_auto={v!r}: true or false")
+    return bool(v)
+
+
+def _grow_feather(grow, feather):
     grow = 0 if grow is None else grow
     feather = 0.0 if feather is None else float(feather)
     if isinstance(grow, bool) or not 0 <= grow <= 8 or int(grow) != grow:   # (the range check also refuses NaN)
         raise ValueError(f"edit_mask_grow={grow}: an integer, 0 <= edit_mask_grow <= 8")
     if not 0.0 <= feather <= 8.0:   # (also refuses NaN)
         raise ValueError(f"edit_mask_feather={feather}: 0 <= edit_mask_feather <= 8")
-    return str(path), int(grow), feather
+    return int(grow), feather
+
+
+def masked_edit_options(config):
+    """(edit_mask_path, grow, feather) of a PnP-edit configuration, or None: three OPTIONAL keys the reference's files do not have --
+    ``edit_mask_path`` (one PNG, or a directory of ``%05d.png`` files; white = edit, black = keep the source), ``edit_mask_grow`` (latent
+    pixels, integer 0 .. 8) and ``edit_mask_feather`` (sigma in latent pixels, 0 .. 8) -- for ``I2VGenXLPipeline.enable_masked_edit``.
+    Without ``edit_mask_path`` (absent or null) the entry runs and writes exactly what it did before the keys existed; grow / feather
+    without a path are refused, not dropped -- unless the mask is an automatic one (``auto_mask_options``), which they then shape."""
+    path, grow, feather = _option(config, "edit_mask_path"), _option(config, "edit_mask_grow"), _option(config, "edit_mask_feather")
+    if path is None:
+        if (grow is not None or feather is not None) and not _auto_mask_on(config):
+            raise ValueError("edit_mask_grow / edit_mask_feather without edit_mask_path: there is no mask to grow or feather")
+        return None
+    if _auto_mask_on(config):
+        raise ValueError("edit_mask_auto together with edit_mask_path: the mask is either generated or loaded")
+    grow, feather = _grow_feather(grow, feather)
+    return str(path), grow, feather
+
+
+AUTO_MASK_DEFAULTS = dict(maps=10, strength=0.5, ratio=3.0, threshold=0.5)   # ``I2VGenXLPipeline.generate_edit_mask``'s (diffusers' generate_mask)
+
+
+def auto_mask_options(config):
+    """The automatic edit mask of a PnP-edit configuration (``I2VGenXLPipeline.generate_edit_mask``), or None: OPTIONAL keys the reference's
+    files do not have -- ``edit_mask_auto`` (bool) switches it on, ``edit_mask_auto_maps`` (noise draws, integer >= 1),
+    ``edit_mask_auto_strength`` (0 < s <= 1: how far the source is noised), ``edit_mask_auto_ratio`` (> 0) and ``edit_mask_auto_threshold``
+    (in (0, 1)) tune it; ``edit_mask_grow`` / ``edit_mask_feather`` shape the generated mask as they shape a loaded one.
+    -> dict(maps, strength, ratio, threshold, grow, feather).  Absent, null or false: None, and the entry runs and writes exactly what it
+    did before the keys existed; the tuning keys without ``edit_mask_auto``, and ``edit_mask_auto`` with ``edit_mask_path``, are refused."""
+    import math
+    vals = {k: _option(config, "edit_mask_auto_" + k) for k in AUTO_MASK_DEFAULTS}
+    if not _auto_mask_on(config):
+        given = [k for k, v in vals.items() if v is not None]
+        if given:
+            raise ValueError(f"edit_mask_auto_{given[0]} without edit_mask_auto: there is no automatic mask to tune")
+        return None
+    if _option(config, "edit_mask_path") is not None:
+        raise ValueError("edit_mask_auto together with edit_mask_path: the mask is either generated or loaded")
+    maps = AUTO_MASK_DEFAULTS["maps"] if vals["maps"] is None else vals["maps"]
+    if isinstance(maps, bool) or not isinstance(maps, (int, float)) or not 1 <= maps < 2 ** 31 or int(maps) != maps:   # (refuses NaN)
+        raise ValueError(f"edit_mask_auto_maps={maps}: an integer >= 1")
+    num = {k: float(AUTO_MASK_DEFAULTS[k] if vals[k] is None else vals[k]) for k in ("strength", "ratio", "threshold")}
+    if not 0.0 < num["strength"] <= 1.0:
+        raise ValueError(f"edit_mask_auto_strength={num['strength']}: 0 < edit_mask_auto_strength <= 1")
+    if not (num["ratio"] > 0.0 and math.isfinite(num["ratio"])):
+        raise ValueError(f"edit_mask_auto_ratio={num['ratio']}: finite and > 0")
+    if not 0.0 < num["threshold"] < 1.0:
+        raise ValueError(f"edit_mask_auto_threshold={num['threshold']}: 0 < edit_mask_auto_threshold < 1")
+    grow, feather = _grow_feather(_option(config, "edit_mask_grow"), _option(config, "edit_mask_feather"))
+    return dict(maps=int(maps), grow=grow, feather=feather, **num)
 
 
 def _rebind(cfg: Config, root: Config):

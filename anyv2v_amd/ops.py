@@ -611,6 +611,40 @@ def masked_blend(x: torch.Tensor, src: torch.Tensor, mask: torch.Tensor, out: Op
     return out
 
 
+def diff_map_accum(vtok: torch.Tensor, C_: int, F: int, HW: int, acc: torch.Tensor, first):
+    """``acc[p] = first ? s[p] : acc[p] + s[p]``, ``s[p] = sum_c |vtok[F HW + p, c] - vtok[p, c]|`` (``anyv2v_diff_map_accum_f16``): vtok is
+    the UNet's token-layout output of the batch [source, edit], acc fp32 with F * HW elements.  ``first``: a bool, or a one-element int32
+    DEVICE tensor read by the kernel -- the form a captured graph needs to serve the first map and the following ones."""
+    lib = _lib.load()
+    _rowmajor(vtok, "V")
+    assert vtok.shape[0] >= 2 * F * HW and vtok.shape[1] >= C_, f"diff_map_accum: {tuple(vtok.shape)} tokens for 2 x {F} x {HW} pixels of {C_} channels"
+    assert acc.dtype == torch.float32 and acc.is_contiguous() and acc.numel() == F * HW and acc.device == vtok.device
+    flag = None
+    if torch.is_tensor(first):
+        assert first.dtype == torch.int32 and first.numel() == 1 and first.device == vtok.device
+        flag, first = first, 0
+    _lib.check(lib.anyv2v_diff_map_accum_f16(_p(vtok), vtok.stride(0), int(C_), int(F), int(HW), _p(acc), int(bool(first)), _p(flag), _stream()),
+               "anyv2v_diff_map_accum_f16")
+    return acc
+
+
+def diff_map_finish(acc: torch.Tensor, F: int, h: int, w: int, ratio: float, threshold: float, out=None):
+    """fp32 accumulator [F h w] -> (map fp16 [F, h, w], pixel mask bool [F, 8 h, 8 w]) (``anyv2v_diff_map_finish_f16``):
+    ``map = fp16(clamp(ratio acc / mean(acc), 0, 1))`` with one mean over the clip (0 when the mean is 0), ``mask = map > fp16(threshold)``
+    with every latent pixel replicated over its 8 x 8 block.  ``out`` = (map, uint8 or bool mask) to write into given tensors."""
+    lib = _lib.load()
+    assert acc.dtype == torch.float32 and acc.is_contiguous() and acc.numel() == F * h * w and acc.is_cuda
+    if out is None:
+        out = (torch.empty((F, h, w), dtype=torch.float16, device=acc.device), torch.empty((F, 8 * h, 8 * w), dtype=torch.bool, device=acc.device))
+    m, pm = out
+    assert m.dtype == torch.float16 and m.is_contiguous() and tuple(m.shape) == (F, h, w) and m.device == acc.device
+    assert pm.dtype in (torch.bool, torch.uint8) and pm.is_contiguous() and tuple(pm.shape) == (F, 8 * h, 8 * w) and pm.device == acc.device
+    rec = torch.empty(_lib.DIFF_MAP_BLOCKS, dtype=torch.float32, device=acc.device)
+    _lib.check(lib.anyv2v_diff_map_finish_f16(_p(acc), int(F), int(h), int(w), float(ratio), float(threshold), _p(rec), _p(m), _p(pm), _stream()),
+               "anyv2v_diff_map_finish_f16")
+    return m, pm
+
+
 def ddim_step(v: torch.Tensor, x: torch.Tensor, sa_t: float, sb_t: float, sa_p: float, sb_p: float, out=None):
     lib = _lib.load()
     v = v.to(torch.float16).contiguous()

@@ -42,6 +42,15 @@ def _use_graphs() -> bool:
     return os.environ.get("ANYV2V_NO_GRAPH", "0") != "1"
 
 
+def edit_mask_timestep(timesteps, num_inference_steps: int, mask_encode_strength: float) -> int:
+    """The timestep ``generate_edit_mask`` noises the source to, as diffusers' ``get_timesteps`` of the DiffEdit pipeline: with
+    ``num_inference_steps`` set on the forward scheduler, ``init = min(int(steps * strength), steps)`` and ``t = timesteps[steps - init]``;
+    a strength so small that ``init`` is 0 takes the last (least noisy) timestep."""
+    steps = int(num_inference_steps)
+    init = min(int(steps * float(mask_encode_strength)), steps)
+    return int(timesteps[min(steps - init, steps - 1)])
+
+
 class SourceFeatureCache:
     """Job-level exact saving for several edits of ONE clip (``configs/group_pnp_edit/group_config.json`` holds 8 edits of one
     clip): the source branch of ``sample_with_pnp`` is only a feature generator -- its v-prediction is discarded
@@ -631,6 +640,141 @@ class I2VGenXLPipeline:
         lm = ops.latent_mask(m.to(device), me["grow"], me["feather"])
         return torch.zeros_like(latents), lm, src.to(device=device, dtype=torch.float16).contiguous()
 
+    @torch.no_grad()
+    def generate_edit_mask(self, prompt=None, image=None, ddim_inv_prompt=None, ddim_inv_1st_frame=None, source_latents=None,
+                           ddim_inv_latents_path: Union[str, LatentTrajectory, None] = None, height: Optional[int] = 704,
+                           width: Optional[int] = 1280, num_frames: int = 16, target_fps: Optional[int] = 16, num_inference_steps: int = 50,
+                           num_maps_per_mask: int = 10, mask_encode_strength: float = 0.5, mask_thresholding_ratio: float = 3.0,
+                           threshold: float = 0.5, generator=None, clip_skip: Optional[int] = 1, trace: Optional[dict] = None,
+                           prompt_embeds=None, image_embeddings=None, image_latents=None, ddim_inv_prompt_embeds=None,
+                           ddim_inv_image_embeddings=None, ddim_inv_image_latents=None):
+        """The edit mask of a masked PnP edit from the model itself (DiffEdit, arXiv 2210.11427; parameter names and defaults of diffusers'
+        ``StableDiffusionDiffEditPipeline.generate_mask``): the source latents are noised to a middle timestep, the UNet predicts once
+        under the source conditioning (``ddim_inv_prompt`` / ``ddim_inv_1st_frame``, the "ddim_inv" set of ``sample_with_pnp``) and once
+        under the edit conditioning (``prompt`` / ``image``), the channel sum of the absolute difference is accumulated over
+        ``num_maps_per_mask`` noise draws, normalised by ITS MEAN OVER THE CLIP, scaled by ``mask_thresholding_ratio``, clamped and
+        thresholded ("Automatic edit mask").  -> bool [F, H, W] on the device, each latent pixel over its 8 x 8 block: the
+        ``mask`` of ``enable_masked_edit``, which the CALLER hands over -- this method does not touch the setting.
+
+        Exactly one of ``source_latents`` ([1, 4, F, h, w] clean latents, noised by ``scheduler.add_noise`` with one ``scheduler.draw_noise``
+        from ``generator`` per map) and ``ddim_inv_latents_path`` (a ``LatentTrajectory`` or its directory: the deterministic variant --
+        x_t is the inversion's entry at the scheduled timestep nearest to the chosen one, ONE map, no noise).  No classifier-free
+        guidance: two branches [source, edit] of the same x_t.  With HIP graphs one captured graph (forward + accumulate) is replayed
+        for every map; ``ANYV2V_NO_GRAPH=1`` runs the same launches eagerly.  ``trace``: a dict that receives ``map`` (fp16 [F, h, w]),
+        ``timestep``, ``acc`` (fp32 [F, h, w]) and ``x_t`` (one per map)."""
+        import copy
+        import math
+        height = height or self.unet.config.sample_size * self.vae_scale_factor
+        width = width or self.unet.config.sample_size * self.vae_scale_factor
+        if getattr(self.unet, "frame_parallel", None) is not None:
+            raise NotImplementedError("generate_edit_mask on a frame-parallel clip: the clip mean spans all frames and would need a collective")
+        if pnp_utils.has_foreign_hooks(self.unet):
+            raise ValueError("generate_edit_mask: foreign hooks are plugged into the UNet; they slice the batch in thirds and this forward has "
+                             "two branches [source, edit]")
+        if any(pnp_utils.injection_state(self)):
+            raise ValueError("generate_edit_mask: PnP injection is left registered for the current timestep; the hooks assume the 3-way batch "
+                             "[source, negative, editing] and this forward has two branches -- call pnp_utils.clear_time(pipe) first")
+        if isinstance(prompt, (list, tuple)) or isinstance(ddim_inv_prompt, (list, tuple)):
+            raise ValueError("generate_edit_mask: got a list of prompts: one clip per call")
+        if (source_latents is None) == (ddim_inv_latents_path is None):
+            raise ValueError("generate_edit_mask: exactly one of source_latents (noise draws) and ddim_inv_latents_path (the inversion "
+                             "trajectory, deterministic) must be given")
+        if height % 8 != 0 or width % 8 != 0 or height < 8 or width < 8:
+            raise ValueError(f"`height` and `width` have to be divisible by 8 but are {height} and {width}.")
+        N = num_maps_per_mask
+        if isinstance(N, bool) or not isinstance(N, int) or N < 1:
+            raise ValueError(f"num_maps_per_mask={N}: an integer >= 1")
+        strength, ratio, threshold = float(mask_encode_strength), float(mask_thresholding_ratio), float(threshold)
+        if not 0.0 < strength <= 1.0:   # (also refuses NaN)
+            raise ValueError(f"mask_encode_strength={mask_encode_strength}: 0 < mask_encode_strength <= 1")
+        if not (ratio > 0.0 and math.isfinite(ratio)):
+            raise ValueError(f"mask_thresholding_ratio={mask_thresholding_ratio}: finite and > 0")
+        if not 0.0 < threshold < 1.0:
+            raise ValueError(f"threshold={threshold}: 0 < threshold < 1")
+        if not isinstance(self.scheduler, DDIMScheduler):
+            raise ValueError(f"generate_edit_mask takes its timestep from the forward DDIMScheduler, not {type(self.scheduler).__name__}")
+        device = self._execution_device
+        F_, h, w = int(num_frames), height // self.vae_scale_factor, width // self.vae_scale_factor
+        shape = (1, 4, F_, h, w)
+        sched = copy.copy(self.scheduler)   # (a copy: the pipeline's own timesteps stay as the caller set them)
+        sched.set_timesteps(int(num_inference_steps))
+        t = edit_mask_timestep(sched.timesteps, int(num_inference_steps), strength)
+        if source_latents is not None:
+            if not torch.is_tensor(source_latents) or tuple(source_latents.shape) != shape:
+                raise ValueError(f"source_latents: {list(shape)} expected for this call, got "
+                                 f"{tuple(source_latents.shape) if torch.is_tensor(source_latents) else type(source_latents).__name__}")
+            x0, traj_x = source_latents.to(device=device, dtype=torch.float16).contiguous(), None
+        else:
+            traj = ddim_inv_latents_path if isinstance(ddim_inv_latents_path, LatentTrajectory) else \
+                LatentTrajectory.load(ddim_inv_latents_path, device=device)
+            if len(traj) == 0:
+                raise ValueError(f"generate_edit_mask: no inverted latents in {ddim_inv_latents_path}")
+            t = min(traj.keys(), key=lambda k: (abs(int(k) - t), int(k)))   # the scheduled timestep nearest to t (a tie: the lower one)
+            traj_x = load_ddim_latents_at_t(t, traj)
+            if tuple(traj_x.shape) != shape:
+                raise ValueError(f"the inversion trajectory's latents {tuple(traj_x.shape)} do not match the call: {list(shape)} expected")
+            x0, traj_x, N = None, traj_x.to(device=device, dtype=torch.float16).contiguous(), 1
+        # conditioning: the edit's by ``_conditioning`` without a negative branch (no guidance here), the source's as in ``sample_with_pnp``
+        saved, self._guidance_scale = self._guidance_scale, 1.0
+        try:
+            pe, _npe, ie, il = self._conditioning(prompt, image, height, width, F_, None, prompt_embeds, None, target_fps, clip_skip,
+                                                  image_embeddings, image_latents)
+        finally:
+            self._guidance_scale = saved
+        self._single_clip(pe, 1)
+        spe, sie, sil = self._source_conditioning(ddim_inv_prompt, ddim_inv_1st_frame, height, width, F_, clip_skip, ddim_inv_prompt_embeds,
+                                                  ddim_inv_image_embeddings, ddim_inv_image_latents)
+        for name, a, b in (("prompt embeddings", spe, pe), ("image embeddings", sie, ie), ("image latents", sil, il)):
+            if tuple(a.shape) != tuple(b.shape):
+                raise ValueError(f"generate_edit_mask: the source's {name} {tuple(a.shape)} do not match the edit's {tuple(b.shape)}")
+        if tuple(il.shape) != shape:
+            raise ValueError(f"image latents {tuple(il.shape)} do not match the call: {list(shape)} expected")
+        ehs, ie_all, il_all = torch.cat([spe, pe]).contiguous(), torch.cat([sie, ie]).contiguous(), torch.cat([sil, il]).contiguous()
+        fps = torch.tensor([target_fps] * 2, device=device)
+        unet = self.unet
+        if not unet._packed:
+            unet.pack()
+        sample = torch.zeros((2,) + shape[1:], dtype=torch.float16, device=device)   # static: both slots hold the same x_t
+        acc = torch.empty(F_ * h * w, dtype=torch.float32, device=device)             # (never read before the first map overwrites it)
+        first = torch.ones(1, dtype=torch.int32, device=device)                       # the accumulate launch's device flag
+        use_graphs, graph, xs = _use_graphs() and sample.is_cuda, None, []
+        with ops.workspace_slot(getattr(self, "ws_slot", 0)):
+            ctx = unet._prepare_clip(2, F_, h, w, ehs, fps, il_all, ie_all)
+            ctx.shared_stem = False   # (the two branches differ in their image latents)
+            ctx.t_buf.fill_(float(t))
+
+            def body():
+                vtok = unet._forward_core(ctx, sample)   # the raw prediction, whatever ``prediction_type`` the model has
+                ops.diff_map_accum(vtok, shape[1], F_, h * w, acc, first)
+
+            for k in range(N):
+                # x_t OUTSIDE the graph, in torch: one draw per map from the caller's generator (a draw recorded inside a graph would
+                # replay the same noise), and the same rounded x_t into both batch slots
+                x = traj_x if traj_x is not None else sched.add_noise(x0, sched.draw_noise(x0, generator), torch.tensor([t]))
+                sample[0].copy_(x[0])
+                sample[1].copy_(x[0])
+                first.fill_(1 if k == 0 else 0)
+                if trace is not None:
+                    xs.append(x.clone())
+                if not use_graphs:
+                    body()
+                    continue
+                if graph is None:
+                    unet._forward_core(ctx, sample)   # warm up eagerly on the side (pure), then capture
+                    torch.cuda.synchronize()
+                    graph = torch.cuda.CUDAGraph()
+                    with capture_hip_graph(graph):
+                        body()
+                graph.replay()
+            soft, pixel = ops.diff_map_finish(acc, F_, h, w, ratio, threshold)
+        if graph is not None:
+            torch.cuda.current_stream().synchronize()   # once per clip: the graph and its pool go back before the edit's engines capture
+            release_graphs([graph])
+            del graph
+        if trace is not None:
+            trace.update(map=soft, timestep=int(t), acc=acc.view(F_, h, w).clone(), x_t=xs)
+        return pixel
+
     def _sampler_options(self, eta, cross_attention_kwargs):
         """-> (stochastic, eta, phi) for the step engines of ``__call__`` / ``sample_with_pnp``.  ``eta`` counts when the scheduler is the
         forward ``DDIMScheduler`` (as ``prepare_extra_step_kwargs``: the inverse scheduler's ``step`` takes none); 0 <= eta <= 1."""
@@ -669,6 +813,23 @@ class I2VGenXLPipeline:
         return (prompt_embeds.to(device, torch.float16), None if negative_prompt_embeds is None else
                 negative_prompt_embeds.to(device, torch.float16), image_embeddings.to(device, torch.float16),
                 image_latents.to(device, torch.float16))
+
+    def _source_conditioning(self, ddim_inv_prompt, ddim_inv_1st_frame, height, width, num_frames, clip_skip, ddim_inv_prompt_embeds=None,
+                             ddim_inv_image_embeddings=None, ddim_inv_image_latents=None):
+        """The source (ddim inversion) branch of ``sample_with_pnp``: its own prompt, first frame, positive image embedding (:1027-1091)
+        -> (prompt embedding, image embedding, image latents), fp16 on the device."""
+        device = self._execution_device
+        if ddim_inv_prompt_embeds is None:
+            ddim_inv_prompt_embeds = _clip_text(self._need("text_encoder"), self._need("tokenizer"), ddim_inv_prompt,
+                                                device, clip_skip)
+        if ddim_inv_image_embeddings is None:
+            ddim_inv_image_embeddings = _clip_image(self._need("image_encoder"), self._need("feature_extractor"),
+                                                    ddim_inv_1st_frame, width, device)
+        if ddim_inv_image_latents is None:
+            first = self._need("vae").encode_image(ddim_inv_1st_frame, device, height, width)
+            ddim_inv_image_latents = self.prepare_image_latents_from_first_frame_latent(first, num_frames)
+        return (ddim_inv_prompt_embeds.to(device, torch.float16), ddim_inv_image_embeddings.to(device, torch.float16),
+                ddim_inv_image_latents.to(device, torch.float16))
 
     def enable_source_cache(self, on: bool = True):
         """Several edits of one clip (a group job, the front-end called repeatedly): keep the source branch's injected features of
@@ -898,19 +1059,8 @@ class I2VGenXLPipeline:
         self._single_clip(pe, num_videos_per_prompt)
         stochastic, eta, phi = self._sampler_options(eta, cross_attention_kwargs)
         opts = dict(stochastic=stochastic, rescale=phi) if (stochastic or phi > 0.0) else {}
-        # source (ddim inversion) branch: its own prompt, first frame, positive image embedding (:1027-1091)
-        if ddim_inv_prompt_embeds is None:
-            ddim_inv_prompt_embeds = _clip_text(self._need("text_encoder"), self._need("tokenizer"), ddim_inv_prompt,
-                                                device, clip_skip)
-        if ddim_inv_image_embeddings is None:
-            ddim_inv_image_embeddings = _clip_image(self._need("image_encoder"), self._need("feature_extractor"),
-                                                    ddim_inv_1st_frame, width, device)
-        if ddim_inv_image_latents is None:
-            first = self._need("vae").encode_image(ddim_inv_1st_frame, device, height, width)
-            ddim_inv_image_latents = self.prepare_image_latents_from_first_frame_latent(first, num_frames)
-        spe = ddim_inv_prompt_embeds.to(device, torch.float16)
-        sie = ddim_inv_image_embeddings.to(device, torch.float16)
-        sil = ddim_inv_image_latents.to(device, torch.float16)
+        spe, sie, sil = self._source_conditioning(ddim_inv_prompt, ddim_inv_1st_frame, height, width, num_frames, clip_skip,
+                                                  ddim_inv_prompt_embeds, ddim_inv_image_embeddings, ddim_inv_image_latents)
         cfg_on = self.do_classifier_free_guidance
         if cfg_on:  # order: [ddim_inversion, negative, editing] (:1044,1093-1094)
             ehs = torch.cat([spe, npe, pe])

@@ -19,11 +19,11 @@ from pathlib import Path
 import torch
 from PIL import Image
 
-from .config import OmegaConf, masked_edit_options, sampler_options
+from .config import AUTO_MASK_DEFAULTS, OmegaConf, auto_mask_options, masked_edit_options, sampler_options
 from .encoders import attach_synthetic_encoders
 from .parallel import FrameParallel, gather_latents, init_distributed, seed_for_entry, shard_entries
 from .pipeline import I2VGenXLPipeline
-from .pnp_utils import register_conv_injection, register_spatial_attention_pnp, register_temp_attention_pnp
+from .pnp_utils import clear_time, register_conv_injection, register_spatial_attention_pnp, register_temp_attention_pnp
 from .schedulers import DDIMScheduler
 from .utils import (LatentTrajectory, convert_video_to_frames, export_to_gif, export_to_video, load_ddim_latents_at_t, load_edit_mask,
                     load_image, load_video_frames, seed_everything)
@@ -53,6 +53,10 @@ def output_suffix(config, ddim_init_latents_t_idx) -> str:
     masked = masked_edit_options(config)   # optional keys ``edit_mask_*``: a masked and an unmasked edit do not overwrite each other
     mask_tag = "" if masked is None else ("_mask-" + os.path.splitext(os.path.basename(os.path.normpath(masked[0])))[0]
                                           + (f"_grow{masked[1]}" if masked[1] > 0 else "") + (f"_feather{masked[2]}" if masked[2] > 0 else ""))
+    auto = auto_mask_options(config)       # optional keys ``edit_mask_auto*``: the generated mask's parameters, where they are not the defaults
+    if auto is not None:
+        mask_tag = ("_mask-auto" + "".join(f"_{k}{auto[k]}" for k in AUTO_MASK_DEFAULTS if auto[k] != AUTO_MASK_DEFAULTS[k])
+                    + (f"_grow{auto['grow']}" if auto["grow"] > 0 else "") + (f"_feather{auto['feather']}" if auto["feather"] > 0 else ""))
     return ("ddim_init_latents_t_idx_" + str(ddim_init_latents_t_idx) + "_nsteps_" + str(config.n_steps) + "_cfg_"
             + str(config.cfg) + "_pnpf" + str(config.pnp_f_t) + "_pnps" + str(config.pnp_spatial_attn_t) + "_pnpt"
             + str(config.pnp_temp_attn_t) + (f"_eta{eta}" if eta > 0 else "") + (f"_rescale{rescale}" if rescale > 0 else "") + mask_tag)
@@ -155,11 +159,29 @@ class Stage2:
         # source frames loaded above -- the partner of the last step, which the trajectory does not hold.  Encoded under the template's
         # seed BEFORE the entry is seeded below, so the draws of the edit itself are the ones of an unmasked entry.
         masked = masked_edit_options(config)
+        auto = auto_mask_options(config)
         if masked is not None:
             mask = load_edit_mask(os.path.join(config.data_dir, masked[0]), config.n_frames, tuple(config.image_size))
             seed_everything(template_config.seed)
             source_latents = pipe.encode_vae_video(frame_list, device=pipe._execution_device, height=config.image_size[1],
                                                    width=config.image_size[0])
+        elif auto is not None:
+            # automatic mask (optional keys ``edit_mask_auto*``): generated here, under the template's seed like the encode above, from the
+            # trajectory when ``run_group_anyv2v`` handed it over in HBM (deterministic, one map), else from noise draws on the clean
+            # latents.  The hooks of the previous entry are inert while it runs; ``init_pnp`` below registers this entry's.
+            seed_everything(template_config.seed)
+            source_latents = pipe.encode_vae_video(frame_list, device=pipe._execution_device, height=config.image_size[1],
+                                                   width=config.image_size[0])
+            clear_time(pipe)
+            pipe.register_modules(scheduler=ddim_scheduler)
+            pipe.auto_vae_tiling(config.image_size[1], config.image_size[0])
+            src = dict(ddim_inv_latents_path=traj) if handed is not None else dict(source_latents=source_latents)
+            mask = pipe.generate_edit_mask(
+                prompt=config.editing_prompt, image=edited_1st_frame, ddim_inv_prompt=config.ddim_inv_prompt, ddim_inv_1st_frame=src_1st_frame,
+                height=config.image_size[1], width=config.image_size[0], num_frames=config.n_frames, target_fps=config.target_fps,
+                num_inference_steps=config.n_steps, num_maps_per_mask=auto["maps"], mask_encode_strength=auto["strength"],
+                mask_thresholding_ratio=auto["ratio"], threshold=auto["threshold"], generator=torch.manual_seed(template_config.seed), **src)
+            masked = (None, auto["grow"], auto["feather"])
         seed_everything(seed_for_entry(template_config.seed, entry_idx) if self.e_world > 1 else template_config.seed)
         random_latents = torch.randn(ddim_latents_at_t.shape, dtype=torch.float32).to(ddim_latents_at_t)  # drawn even if unused (:124)
         logger.info(f"Blending random_ratio (1 means random latent): {config.random_ratio}")
@@ -202,6 +224,9 @@ class Stage2:
         logger.info(f"Saved gif to: {os.path.join(output_dir, f'{name}.gif')}")
         for i, frame in enumerate(edited_video):
             frame.save(os.path.join(output_dir, f"{name}_{i:05d}.png"))
+        if auto is not None:   # the generated mask, one frame per file in the format ``load_edit_mask`` reads (white = edited)
+            for i, plane in enumerate((mask.to(torch.uint8) * 255).cpu().numpy()):
+                Image.fromarray(plane, mode="L").save(os.path.join(output_dir, f"mask_{i:05d}.png"))
         torch.save(edited_latents.cpu(), os.path.join(output_dir, "edited_latents.pt"))
 
     def finish(self):

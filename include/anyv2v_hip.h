@@ -398,6 +398,36 @@ int anyv2v_latent_mask_f16(const void* mask, int32_t mask_frames, int32_t H, int
 int anyv2v_masked_blend_f16(const void* x, const void* src, const void* mask, int32_t mask_frames, void* out, int32_t C, int32_t F,
                             int32_t HW, void* stream);
 
+/* Automatic edit masks for the masked edit -- where do the UNet's predictions under the source and under the edit conditioning differ?
+ * Nothing in the reference does this; the method is DiffEdit's (Couairon et al., arXiv 2210.11427), these two entry points replace the
+ * tail of diffusers' StableDiffusionDiffEditPipeline.generate_mask:
+ *   mask_guidance_map = torch.abs(noise_pred_target - noise_pred_source).reshape(b, num_maps_per_mask, *shape).mean([1, 2])
+ * followed by its normalisation by the map's mean, the scaling by mask_thresholding_ratio, the clamp to [0, 1] and the threshold -- here as
+ *   map = clamp(ratio * map / mean(map), 0, 1);   mask = map > threshold
+ * with ONE mean over the whole clip (a frame in which nothing changes comes out empty), for a video UNet's [F, h, w] maps.  The factor
+ * 1 / (N C) of the two means cancels in the normalisation, so the accumulator holds plain sums.
+ *
+ * anyv2v_diff_map_accum_f16: Vtok [2 F HW, ldv] fp16, the UNet's token-layout output of the batch [source, edit]: rows [0, F HW) the
+ * source branch, rows [F HW, 2 F HW) the edit branch, the C channels in the first columns of a row (columns C .. ldv - 1 are never read).
+ *   s[p] = sum_c |V_tgt[p, c] - V_src[p, c]|    the difference and its absolute value exact in fp32, channels added in the order 0 .. C - 1
+ *   acc[p] = first ? s[p] : acc[p] + s[p]       fp32 [F HW]
+ * `first` (0 / 1) is the host's flag; first_dev, when not NULL, points at ONE int32 on the device that is read instead -- a captured graph
+ * then serves the first map and every further one.  One thread per pixel, no atomics, each element written once per launch.
+ *
+ * anyv2v_diff_map_finish_f16: acc fp32 [F, h, w] -> map fp16 [F, h, w] and pixel_mask uint8 [F, 8 h, 8 w] (0 / 1: torch.bool's layout).
+ *   mean = sum(acc) / (F h w): a fixed grid of ANYV2V_DIFF_MAP_BLOCKS x ANYV2V_DIFF_MAP_THREADS threads writes one fp32 partial sum per
+ *          block into `records` (ANYV2V_DIFF_MAP_BLOCKS floats); every consumer folds them in fp64 in record order -- bit-reproducible;
+ *   map  = fp16(clamp(acc * fp32(ratio / mean), 0, 1)), one rounding to fp16; mean == 0 (identical conditionings): map = 0, no NaN;
+ *   mask = map > fp16(threshold), compared on the ROUNDED map, each latent pixel replicated over its 8 x 8 pixel block.
+ * ratio finite and > 0, threshold in (0, 1).  16-byte accesses when w % 8 == 0 and acc / map / pixel_mask are 16-byte aligned, a scalar
+ * kernel otherwise -- chosen here, on the host.  Two launches (partial sums, finish), no atomics. */
+#define ANYV2V_DIFF_MAP_BLOCKS 64
+#define ANYV2V_DIFF_MAP_THREADS 256
+int anyv2v_diff_map_accum_f16(const void* Vtok, int32_t ldv, int32_t C, int32_t F, int32_t HW, float* acc, int32_t first,
+                              const int32_t* first_dev, void* stream);
+int anyv2v_diff_map_finish_f16(const float* acc, int32_t F, int32_t h, int32_t w, float ratio, float threshold, float* records, void* map,
+                               void* pixel_mask, void* stream);
+
 /* Plain elementwise DDIM / inverse-DDIM step (eta = 0, v-prediction) on same-layout tensors:
  * the generic `scheduler.step(model_output, t, sample).prev_sample` (pipeline_i2vgen_xl.py:868,1173,1418). */
 int anyv2v_ddim_step_f16(const void* V, const void* X, void* Y, float sa_t, float sb_t, float sa_p, float sb_p,
@@ -439,8 +469,8 @@ const char* anyv2v_last_error(void);
  * _apply_pivot_f16 (the earlier pair is unchanged).  105: AnyV2VGemmDesc grew gn_stats / gn_stats_floats / gn_rows_per_group /
  * gn_groups (GroupNorm statistics from the GEMM epilogue), anyv2v_gemm_gn_stats_floats, anyv2v_gemm_gn_launches,
  * anyv2v_groupnorm_stats_floats, anyv2v_groupnorm_apply_stats_f16; nothing earlier changed (a 104 caller that zero-initialises its descriptors, as required,
- * must still be recompiled against this header because the structure grew).  anyv2v_freeu_f16, anyv2v_tile_blend_f16, anyv2v_latent_mask_f16 and
- * anyv2v_masked_blend_f16 were added under 105: new entry points, no structure changed
+ * must still be recompiled against this header because the structure grew).  anyv2v_freeu_f16, anyv2v_tile_blend_f16, anyv2v_latent_mask_f16,
+ * anyv2v_masked_blend_f16, anyv2v_diff_map_accum_f16 and anyv2v_diff_map_finish_f16 were added under 105: new entry points, no structure changed
  * (a binding that needs them finds out when it resolves the symbol). */
 #define ANYV2V_ABI_VERSION 105
 int anyv2v_version(void);
