@@ -70,6 +70,9 @@ GUIDANCE_STATS_BLOCKS, GUIDANCE_STATS_THREADS, GUIDANCE_STATS_RECORD = 64, 256, 
 MASK_MAX_GROW, MASK_MAX_RADIUS = 8, 24
 # anyv2v_diff_map_finish_f16: the fixed grid of the clip mean, one fp32 record per block (ANYV2V_DIFF_MAP_* of include/anyv2v_hip.h)
 DIFF_MAP_BLOCKS, DIFF_MAP_THREADS = 64, 256
+# anyv2v_pixel_alpha_f16 / anyv2v_composite_stats_u8: the largest pixel grow and feather radius, the fixed grid of the colour statistics and
+# the int64 entries of a block's record (ANYV2V_COMPOSITE_* of include/anyv2v_hip.h)
+COMPOSITE_MAX_GROW, COMPOSITE_MAX_RADIUS, COMPOSITE_STATS_BLOCKS, COMPOSITE_STATS_RECORD = 64, 48, 256, 16
 
 
 class FFDesc(C.Structure):
@@ -132,6 +135,9 @@ SYMBOLS = {
     "anyv2v_masked_blend_f16": (C.c_int, [_VP, _VP, _VP, _I32, _VP, _I32, _I32, _I32, _VP]),
     "anyv2v_diff_map_accum_f16": (C.c_int, [_VP, _I32, _I32, _I32, _I32, _VP, _I32, _VP, _VP]),
     "anyv2v_diff_map_finish_f16": (C.c_int, [_VP, _I32, _I32, _I32, _F32, _F32, _VP, _VP, _VP, _VP]),
+    "anyv2v_pixel_alpha_f16": (C.c_int, [_VP, _I32, _I32, _I32, _I32, C.POINTER(C.c_float), _I32, _VP, _VP, _VP]),
+    "anyv2v_composite_stats_u8": (C.c_int, [_VP, _VP, _VP, _I32, _I32, _I32, _I32, _VP, _VP]),
+    "anyv2v_composite_u8": (C.c_int, [_VP, _VP, _VP, _I32, _VP, _VP, _I32, _I32, _I32, _VP]),
     "anyv2v_ddim_step_f16": (C.c_int, [_VP, _VP, _VP, _F32, _F32, _F32, _F32, _I64, _VP]),
     "anyv2v_guided_step_f16": (C.c_int, [_VP, _I64, _I32, _I32, _I32, _F32, _F32, _I32, _F32, _F32, _F32, _F32, _VP, _VP, _VP]),
     "anyv2v_guided_step_noise_f16": (C.c_int, [_VP, _I64, _I32, _I32, _I32, _F32, _F32, _I32, _F32, _F32, _F32, _F32, _VP, _VP, _VP, _F32, _VP]),

@@ -20,7 +20,7 @@ from typing import List, Optional
 import torch
 from PIL import Image
 
-from .config import OmegaConf, auto_mask_options, sampler_options
+from .config import OmegaConf, auto_mask_options, composite_options, sampler_options
 from .pipeline import I2VGenXLPipeline
 from .run_group_ddim_inversion import ddim_inversion
 from .pnp_utils import clear_time
@@ -51,7 +51,8 @@ class AnyV2V_I2VGenXL:
                  random_init_seed: Optional[int] = None, synthetic_encoders: bool = False) -> None:
         # default inversion / edit configuration of the demo (gradio_demo.py:60-78); ``pnp_config`` also takes the optional keys
         # ``eta`` / ``guidance_rescale`` (``config.sampler_options``; e.g. ``obj.config.pnp_config.eta = 0.5``) and ``edit_mask_auto`` with
-        # its tuning keys and ``edit_mask_grow`` / ``edit_mask_feather`` (``config.auto_mask_options``), absent = off
+        # its tuning keys and ``edit_mask_grow`` / ``edit_mask_feather`` (``config.auto_mask_options``), and ``edit_mask_composite`` with its
+        # shaping keys (``config.composite_options``: the source frames pasted back outside the generated mask), absent = off
         self.config = OmegaConf.create({
             "inverse_config": {"image_size": [512, 512], "n_frames": 16, "cfg": 1.0, "target_fps": 8, "ddim_inv_prompt": "",
                                "prompt": "", "negative_prompt": ""},
@@ -124,6 +125,7 @@ class AnyV2V_I2VGenXL:
         cfg.pnp_config.ddim_init_latents_t_idx = ddim_init_latents_t_idx
         self.pipe.register_modules(scheduler=self.ddim_scheduler)
         auto = auto_mask_options(cfg.pnp_config)
+        comp = composite_options(cfg.pnp_config)   # (refused without ``edit_mask_auto``: this class loads no mask file)
         if auto is not None:
             # automatic edit mask: from the trajectory in HBM (deterministic, one map), before this edit's hooks are registered
             clear_time(self.pipe)
@@ -146,7 +148,14 @@ class AnyV2V_I2VGenXL:
                 num_inference_steps=cfg.pnp_config.n_steps, guidance_scale=guidance_scale, negative_prompt=video_negative_prompt,
                 eta=eta, target_fps=cfg.pnp_config.target_fps, latents=mixed_latents, generator=generator, return_dict=True,
                 ddim_init_latents_t_idx=ddim_init_latents_t_idx, ddim_inv_latents_path=trajectory,
-                ddim_inv_prompt=cfg.inverse_config.ddim_inv_prompt, ddim_inv_1st_frame=first_frame).frames[0]
+                ddim_inv_prompt=cfg.inverse_config.ddim_inv_prompt, ddim_inv_1st_frame=first_frame,
+                **({} if comp is None else dict(output_type="latent"))).frames
+            if comp is None:
+                edited_video = edited_video[0]
+            else:   # the decode the call above would have made, and the source frames pasted back outside the mask
+                frames_u8 = self.pipe.composite_over_source(self.pipe.decode_latents(edited_video, decode_chunk_size=1), frame_list, mask, grow=auto["grow"],
+                                                            feather=auto["feather"], **comp)
+                edited_video = [Image.fromarray(fr) for fr in frames_u8.cpu().numpy()]
         finally:
             if auto is not None:
                 self.pipe.disable_masked_edit()   # the mask belongs to this clip

@@ -177,6 +177,37 @@ def auto_mask_options(config):
     return dict(maps=int(maps), grow=grow, feather=feather, **num)
 
 
+COMPOSITE_DEFAULTS = dict(grow_px=0, feather_px=0.0, match_color=False)   # ``I2VGenXLPipeline.composite_over_source``'s
+
+
+def composite_options(config):
+    """The pixel-space composite of a masked PnP-edit configuration (``I2VGenXLPipeline.composite_over_source``), or None: OPTIONAL keys the
+    reference's files do not have -- ``edit_mask_composite`` (bool) switches it on, ``edit_mask_composite_grow`` (pixels, integer 0 .. 64),
+    ``edit_mask_composite_feather`` (sigma in pixels, 0 .. 16) and ``edit_mask_match_color`` (bool) shape it.
+    -> dict(grow_px, feather_px, match_color).  Absent, null or false: None, and the entry runs and writes exactly what it did before the
+    keys existed; the shaping keys without ``edit_mask_composite``, and ``edit_mask_composite`` without a mask (``edit_mask_path`` or
+    ``edit_mask_auto``), are refused, not dropped."""
+    on, match = _option(config, "edit_mask_composite"), _option(config, "edit_mask_match_color")
+    for key, v in (("edit_mask_composite", on), ("edit_mask_match_color", match)):
+        if v is not None and not isinstance(v, bool):
+            raise ValueError(f"{key}={v!r}: true or false")
+    grow, feather = _option(config, "edit_mask_composite_grow"), _option(config, "edit_mask_composite_feather")
+    if not on:
+        for key, v in (("edit_mask_composite_grow", grow), ("edit_mask_composite_feather", feather), ("edit_mask_match_color", match)):
+            if v is not None:
+                raise ValueError(f"{key} without edit_mask_composite: there is no composite to shape")
+        return None
+    if _option(config, "edit_mask_path") is None and not _auto_mask_on(config):
+        raise ValueError("edit_mask_composite without edit_mask_path or edit_mask_auto: there is no mask to composite by")
+    grow = 0 if grow is None else grow
+    feather = 0.0 if feather is None else float(feather)
+    if isinstance(grow, bool) or not isinstance(grow, (int, float)) or not 0 <= grow <= 64 or int(grow) != grow:   # (also refuses NaN)
+        raise ValueError(f"edit_mask_composite_grow={grow}: an integer, 0 <= edit_mask_composite_grow <= 64")
+    if not 0.0 <= feather <= 16.0:   # (also refuses NaN)
+        raise ValueError(f"edit_mask_composite_feather={feather}: 0 <= edit_mask_composite_feather <= 16")
+    return dict(grow_px=int(grow), feather_px=feather, match_color=bool(match))
+
+
 def _rebind(cfg: Config, root: Config):
     object.__setattr__(cfg, "_root", root)
     for v in cfg._data.values():

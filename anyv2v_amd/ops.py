@@ -564,13 +564,15 @@ def cfg_ddim_step_ex(vtok: torch.Tensor, b_unc: int, b_cond: int, guidance: floa
     return out
 
 
-def gaussian_taps(sigma: float):
+def gaussian_taps(sigma: float, max_radius: Optional[int] = None, name: str = "feather", unit: str = "latent pixels"):
     """The feather's taps for ``latent_mask``: ``exp(-k^2 / (2 sigma^2)) / sum`` for k = -R .. R, R = ceil(3 sigma), computed in fp64 and
-    rounded to fp32 -> list of 2 R + 1 Python floats that are exactly fp32 values ([] for sigma = 0: no feather)."""
+    rounded to fp32 -> list of 2 R + 1 Python floats that are exactly fp32 values ([] for sigma = 0: no feather).  ``max_radius``: the
+    largest R of the kernel that takes them (``pixel_alpha`` passes its own, and how to name the argument it refuses)."""
     import math
     sigma = float(sigma)
-    if not 0.0 <= sigma <= _lib.MASK_MAX_RADIUS / 3.0:   # (also refuses NaN)
-        raise ValueError(f"feather={sigma}: 0 <= feather <= {_lib.MASK_MAX_RADIUS // 3} latent pixels")
+    max_radius = _lib.MASK_MAX_RADIUS if max_radius is None else max_radius
+    if not 0.0 <= sigma <= max_radius / 3.0:   # (also refuses NaN)
+        raise ValueError(f"{name}={sigma}: 0 <= {name} <= {max_radius // 3} {unit}")
     R = int(math.ceil(3.0 * sigma))
     if R == 0:
         return []
@@ -643,6 +645,70 @@ def diff_map_finish(acc: torch.Tensor, F: int, h: int, w: int, ratio: float, thr
     _lib.check(lib.anyv2v_diff_map_finish_f16(_p(acc), int(F), int(h), int(w), float(ratio), float(threshold), _p(rec), _p(m), _p(pm), _stream()),
                "anyv2v_diff_map_finish_f16")
     return m, pm
+
+
+def pixel_alpha(latent_mask: torch.Tensor, grow_px: int = 0, feather_px: float = 0.0, out: Optional[torch.Tensor] = None):
+    """Latent mask [Fm, h, w] fp16 (``latent_mask``'s result) -> pixel-space alpha [Fm, 8 h, 8 w] fp32 (``anyv2v_pixel_alpha_f16``): 1 on the
+    cells with mask > 0 grown by ``grow_px`` pixels, a Gaussian of ``feather_px`` pixels (sigma <= 16; R = ceil(3 sigma)) falling to exactly
+    0 beyond ``grow_px + 2 R``.  Separable passes; once per clip, outside any graph."""
+    lib = _lib.load()
+    assert latent_mask.dim() == 3 and latent_mask.dtype == torch.float16 and latent_mask.is_contiguous(), \
+        f"pixel_alpha: contiguous fp16 [Fm, h, w] expected, got {tuple(latent_mask.shape)} {latent_mask.dtype}"
+    if isinstance(grow_px, bool) or not 0 <= grow_px <= _lib.COMPOSITE_MAX_GROW or int(grow_px) != grow_px:   # (the range check also refuses NaN)
+        raise ValueError(f"grow_px={grow_px}: an integer, 0 <= grow_px <= {_lib.COMPOSITE_MAX_GROW} pixels")
+    taps = gaussian_taps(feather_px, _lib.COMPOSITE_MAX_RADIUS, "feather_px", "pixels")
+    Fm, h, w = latent_mask.shape
+    if out is None:
+        out = torch.empty((Fm, 8 * h, 8 * w), dtype=torch.float32, device=latent_mask.device)
+    assert out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (Fm, 8 * h, 8 * w) and out.device == latent_mask.device
+    ws = torch.empty(2 * out.numel(), dtype=torch.float32, device=latent_mask.device)
+    arr = (C.c_float * len(taps))(*taps) if taps else None
+    _lib.check(lib.anyv2v_pixel_alpha_f16(_p(latent_mask), Fm, h, w, int(grow_px), arr, len(taps) // 2, _p(ws), _p(out), _stream()),
+               "anyv2v_pixel_alpha_f16")
+    return out
+
+
+def _composite_operands(video, source_u8, alpha):
+    assert video.dtype == torch.float16 and video.is_contiguous() and video.dim() == 5 and video.shape[0] == 1 and video.shape[1] == 3, \
+        f"composite: contiguous fp16 video [1, 3, F, H, W] expected, got {tuple(video.shape)} {video.dtype}"
+    _, _, F, H, W = video.shape
+    assert source_u8.dtype == torch.uint8 and source_u8.is_contiguous() and tuple(source_u8.shape) == (F, H, W, 3) and source_u8.device == video.device, \
+        f"composite: source {tuple(source_u8.shape)} {source_u8.dtype} against video {tuple(video.shape)}: uint8 [F, H, W, 3] expected"
+    assert alpha.dtype == torch.float32 and alpha.is_contiguous() and alpha.dim() == 3 and alpha.shape[0] in (1, F) \
+        and tuple(alpha.shape[1:]) == (H, W) and alpha.device == video.device, \
+        f"composite: alpha {tuple(alpha.shape)} {alpha.dtype} against video {tuple(video.shape)}: fp32 [1 or F, H, W] expected"
+    return F, H, W
+
+
+def composite_stats(video: torch.Tensor, source_u8: torch.Tensor, alpha: torch.Tensor, out: Optional[torch.Tensor] = None):
+    """The colour match's statistics (``anyv2v_composite_stats_u8``) -> int64 [COMPOSITE_STATS_BLOCKS, COMPOSITE_STATS_RECORD]: per block
+    and channel c, at [5 c .. 5 c + 4], count / sum e / sum e^2 / sum s / sum s^2 over the kept pixels (alpha == 0) of the whole clip, e the
+    byte ``vae.to_pil`` forms from the video, s the source byte.  Exact integer sums."""
+    lib = _lib.load()
+    F, H, W = _composite_operands(video, source_u8, alpha)
+    shape = (_lib.COMPOSITE_STATS_BLOCKS, _lib.COMPOSITE_STATS_RECORD)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.int64, device=video.device)
+    assert out.dtype == torch.int64 and out.is_contiguous() and tuple(out.shape) == shape and out.device == video.device
+    _lib.check(lib.anyv2v_composite_stats_u8(_p(video), _p(source_u8), _p(alpha), alpha.shape[0], F, H, W, _p(out), _stream()),
+               "anyv2v_composite_stats_u8")
+    return out
+
+
+def composite(video: torch.Tensor, source_u8: torch.Tensor, alpha: torch.Tensor, match_color: bool = False, out: Optional[torch.Tensor] = None):
+    """``out = alpha == 0 ? source : alpha == 1 ? e : rint(fmaf(alpha, e - source, source))`` in bytes (``anyv2v_composite_u8``): video
+    [1, 3, F, H, W] fp16 in [-1, 1] (``decode_latents``), source uint8 [F, H, W, 3], alpha fp32 [Fm, H, W] with Fm 1 or F -> uint8
+    [F, H, W, 3]; e is the byte ``vae.to_pil`` forms.  ``match_color``: e is first mapped by the gain and bias that carry the edit's
+    per-channel mean and deviation over the kept region to the source's (``composite_stats``, one more launch)."""
+    lib = _lib.load()
+    F, H, W = _composite_operands(video, source_u8, alpha)
+    rec = composite_stats(video, source_u8, alpha) if match_color else None
+    if out is None:
+        out = torch.empty_like(source_u8)
+    assert out.dtype == torch.uint8 and out.is_contiguous() and out.shape == source_u8.shape and out.device == video.device
+    _lib.check(lib.anyv2v_composite_u8(_p(video), _p(source_u8), _p(alpha), alpha.shape[0], _p(rec), _p(out), F, H, W, _stream()),
+               "anyv2v_composite_u8")
+    return out
 
 
 def ddim_step(v: torch.Tensor, x: torch.Tensor, sa_t: float, sb_t: float, sa_p: float, sb_p: float, out=None):

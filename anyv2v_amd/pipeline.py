@@ -584,6 +584,22 @@ class I2VGenXLPipeline:
         from . import _lib
         if getattr(self.unet, "frame_parallel", None) is not None:
             raise NotImplementedError("masked edit on a frame-parallel clip: every rank would need its frames of the mask and of the partner latents")
+        m = self._edit_mask_fp16(mask)
+        if not torch.is_tensor(source_latents) or source_latents.dim() != 5 or source_latents.shape[0] != 1 or \
+                source_latents.shape[1] != 4 or tuple(source_latents.shape[3:]) != (m.shape[1] // 8, m.shape[2] // 8) or \
+                m.shape[0] not in (1, source_latents.shape[2]):
+            raise ValueError("source_latents: [1, 4, F, h, w] expected for a mask of "
+                             f"{tuple(m.shape)} (h = H / 8, w = W / 8, Fm = 1 or F), got "
+                             f"{tuple(source_latents.shape) if torch.is_tensor(source_latents) else type(source_latents).__name__}")
+        if isinstance(grow, bool) or not 0 <= grow <= _lib.MASK_MAX_GROW or int(grow) != grow:   # (the range check also refuses NaN)
+            raise ValueError(f"grow={grow}: an integer, 0 <= grow <= {_lib.MASK_MAX_GROW} latent pixels")
+        feather = float(feather)
+        if not 0.0 <= feather <= _lib.MASK_MAX_RADIUS / 3.0:   # (also refuses NaN)
+            raise ValueError(f"feather={feather}: 0 <= feather <= {_lib.MASK_MAX_RADIUS // 3} latent pixels")
+        self._masked_edit = dict(mask=m, source_latents=source_latents, grow=int(grow), feather=feather)
+
+    def _edit_mask_fp16(self, mask):
+        """An edit mask as ``enable_masked_edit`` / ``composite_over_source`` take it -> contiguous fp16 [Fm, H, W] in [0, 1]."""
         if not torch.is_tensor(mask) or mask.dim() not in (2, 3):
             raise ValueError(f"edit mask: a [Fm, H, W] or [H, W] tensor expected, got {type(mask).__name__}"
                              + (f" of shape {tuple(mask.shape)}" if torch.is_tensor(mask) else ""))
@@ -601,21 +617,64 @@ class I2VGenXLPipeline:
         m = (m[None] if m.dim() == 2 else m).contiguous()
         if m.shape[1] % self.vae_scale_factor or m.shape[2] % self.vae_scale_factor or m.shape[0] < 1 or m.shape[1] < 8 or m.shape[2] < 8:
             raise ValueError(f"edit mask: H x W = {m.shape[1]} x {m.shape[2]} must be positive multiples of {self.vae_scale_factor}")
-        if not torch.is_tensor(source_latents) or source_latents.dim() != 5 or source_latents.shape[0] != 1 or \
-                source_latents.shape[1] != 4 or tuple(source_latents.shape[3:]) != (m.shape[1] // 8, m.shape[2] // 8) or \
-                m.shape[0] not in (1, source_latents.shape[2]):
-            raise ValueError("source_latents: [1, 4, F, h, w] expected for a mask of "
-                             f"{tuple(m.shape)} (h = H / 8, w = W / 8, Fm = 1 or F), got "
-                             f"{tuple(source_latents.shape) if torch.is_tensor(source_latents) else type(source_latents).__name__}")
+        return m
+
+    def disable_masked_edit(self):
+        self._masked_edit = None
+
+    @torch.no_grad()
+    def composite_over_source(self, video, source_frames, mask, grow: int = 0, feather: float = 0.0, grow_px: int = 0,
+                              feather_px: float = 0.0, match_color: bool = False):
+        """The pixel-space finish of a masked edit: ``video`` ([1, 3, F, H, W] in [-1, 1], what ``decode_latents`` returns) pasted over
+        ``source_frames`` (a list of F PIL images of the video's size, or a uint8 [F, H, W, 3] tensor) -> uint8 [F, H, W, 3] on the video's
+        device.  Outside the edit region the decode is ``decode(encode(source))``, not the source; here those pixels are the source's
+        bytes, whatever the decode holds, and fully edited pixels are the bytes ``vae.to_pil`` forms from the video as an fp16 tensor (the
+        native decode hands its fp16 values over in fp32, where ``to_pil``'s own arithmetic may land one level away; DESIGN.md 5, "Composite").
+        ``mask`` / ``grow`` / ``feather``: exactly what ``enable_masked_edit`` was given -- the latent mask is rebuilt by
+        ``ops.latent_mask`` and alpha follows the region the latent blend used (every latent cell with mask > 0).  ``grow_px`` (0 .. 64
+        pixels) dilates that region, ``feather_px`` (sigma, 0 .. 16 pixels) lets alpha fall off outside it, ``match_color`` first carries
+        the edit's per-channel mean and deviation over the kept region to the source's (one gain and bias per clip).  A method called
+        behind the decode, not an argument of the sampling calls: the reference's signatures have none."""
+        from . import _lib
+        if getattr(self.unet, "frame_parallel", None) is not None:
+            raise NotImplementedError("composite on a frame-parallel clip: the masked edit it finishes is refused there")
+        if not torch.is_tensor(video) or video.dim() != 5 or video.shape[0] != 1 or video.shape[1] != 3 or not video.is_floating_point():
+            raise ValueError("video: a float [1, 3, F, H, W] tensor expected (decode_latents), got "
+                             f"{tuple(video.shape) if torch.is_tensor(video) else type(video).__name__}")
+        F, H, W = (int(v) for v in video.shape[2:])
+        m = self._edit_mask_fp16(mask)
+        if tuple(m.shape[1:]) != (H, W) or m.shape[0] not in (1, F):
+            raise ValueError(f"edit mask {tuple(m.shape)} does not match the video: [Fm, H, W] = [1 or {F}, {H}, {W}] expected")
+        if torch.is_tensor(source_frames):
+            if source_frames.dtype != torch.uint8:
+                raise ValueError(f"source_frames: a uint8 tensor expected, got {source_frames.dtype} (nothing is quantised here)")
+            src = source_frames
+        elif isinstance(source_frames, (list, tuple)) and len(source_frames) > 0 and all(hasattr(f, "convert") for f in source_frames):
+            import numpy as np
+            sizes = {tuple(f.size) for f in source_frames}
+            if sizes != {(W, H)}:
+                raise ValueError(f"source_frames: images of {sorted(sizes)} against a video of {W} x {H} (nothing is resized here)")
+            src = torch.from_numpy(np.stack([np.asarray(f.convert("RGB"), dtype=np.uint8) for f in source_frames]))
+        else:
+            raise ValueError(f"source_frames: a list of PIL images or a uint8 [F, H, W, 3] tensor expected, got {type(source_frames).__name__}")
+        if tuple(src.shape) != (F, H, W, 3):
+            raise ValueError(f"source_frames {tuple(src.shape)} do not match the video: [F, H, W, 3] = [{F}, {H}, {W}, 3] expected")
         if isinstance(grow, bool) or not 0 <= grow <= _lib.MASK_MAX_GROW or int(grow) != grow:   # (the range check also refuses NaN)
             raise ValueError(f"grow={grow}: an integer, 0 <= grow <= {_lib.MASK_MAX_GROW} latent pixels")
         feather = float(feather)
         if not 0.0 <= feather <= _lib.MASK_MAX_RADIUS / 3.0:   # (also refuses NaN)
             raise ValueError(f"feather={feather}: 0 <= feather <= {_lib.MASK_MAX_RADIUS // 3} latent pixels")
-        self._masked_edit = dict(mask=m, source_latents=source_latents, grow=int(grow), feather=feather)
-
-    def disable_masked_edit(self):
-        self._masked_edit = None
+        if isinstance(grow_px, bool) or not 0 <= grow_px <= _lib.COMPOSITE_MAX_GROW or int(grow_px) != grow_px:
+            raise ValueError(f"grow_px={grow_px}: an integer, 0 <= grow_px <= {_lib.COMPOSITE_MAX_GROW} pixels")
+        feather_px = float(feather_px)
+        if not 0.0 <= feather_px <= _lib.COMPOSITE_MAX_RADIUS / 3.0:
+            raise ValueError(f"feather_px={feather_px}: 0 <= feather_px <= {_lib.COMPOSITE_MAX_RADIUS // 3} pixels")
+        if not isinstance(match_color, bool):
+            raise ValueError(f"match_color={match_color!r}: True or False")
+        device = video.device
+        lm = ops.latent_mask(m.to(device), int(grow), feather)
+        alpha = ops.pixel_alpha(lm, int(grow_px), feather_px)
+        return ops.composite(video.to(torch.float16).contiguous(), src.to(device).contiguous(), alpha, match_color)
 
     def _refuse_masked_edit(self, what):
         """``__call__`` / ``invert``: no source branch, no trajectory to blend against -- a mask left set would be silently dropped."""

@@ -8,6 +8,7 @@ The edit template / entries take the optional sampler keys of stage 2 (``eta``, 
 inversion ignores them, and an edit that draws variance noise draws it inside its own seeded entry, so the two-stream order below
 still writes what the serial order writes.  The masked-edit keys (``edit_mask_path`` / ``_grow`` / ``_feather``; ``config.masked_edit_options``)
 and the automatic-mask keys (``edit_mask_auto*``; ``config.auto_mask_options``: the handed-over trajectory makes it the deterministic variant)
+and the composite keys (``edit_mask_composite*`` / ``edit_mask_match_color``; ``config.composite_options``: the source frames pasted back behind the decode)
 are stage 2's as well: ``Stage2.entry`` encodes the source frames it loads into the clean latent the last blend needs, on its own stream.
 
     python -m anyv2v_amd.run_group_anyv2v --inversion_template configs/group_ddim_inversion/template.yaml \\

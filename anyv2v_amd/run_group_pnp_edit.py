@@ -19,7 +19,7 @@ from pathlib import Path
 import torch
 from PIL import Image
 
-from .config import AUTO_MASK_DEFAULTS, OmegaConf, auto_mask_options, masked_edit_options, sampler_options
+from .config import AUTO_MASK_DEFAULTS, OmegaConf, auto_mask_options, composite_options, masked_edit_options, sampler_options
 from .encoders import attach_synthetic_encoders
 from .parallel import FrameParallel, gather_latents, init_distributed, seed_for_entry, shard_entries
 from .pipeline import I2VGenXLPipeline
@@ -57,6 +57,10 @@ def output_suffix(config, ddim_init_latents_t_idx) -> str:
     if auto is not None:
         mask_tag = ("_mask-auto" + "".join(f"_{k}{auto[k]}" for k in AUTO_MASK_DEFAULTS if auto[k] != AUTO_MASK_DEFAULTS[k])
                     + (f"_grow{auto['grow']}" if auto["grow"] > 0 else "") + (f"_feather{auto['feather']}" if auto["feather"] > 0 else ""))
+    comp = composite_options(config)       # optional keys ``edit_mask_composite*``: the tag only when on, parameters only where not the defaults
+    if comp is not None:
+        mask_tag += ("_comp" + (f"_grow{comp['grow_px']}" if comp["grow_px"] > 0 else "")
+                     + (f"_feather{comp['feather_px']}" if comp["feather_px"] > 0 else "") + ("_match" if comp["match_color"] else ""))
     return ("ddim_init_latents_t_idx_" + str(ddim_init_latents_t_idx) + "_nsteps_" + str(config.n_steps) + "_cfg_"
             + str(config.cfg) + "_pnpf" + str(config.pnp_f_t) + "_pnps" + str(config.pnp_spatial_attn_t) + "_pnpt"
             + str(config.pnp_temp_attn_t) + (f"_eta{eta}" if eta > 0 else "") + (f"_rescale{rescale}" if rescale > 0 else "") + mask_tag)
@@ -160,6 +164,7 @@ class Stage2:
         # seed BEFORE the entry is seeded below, so the draws of the edit itself are the ones of an unmasked entry.
         masked = masked_edit_options(config)
         auto = auto_mask_options(config)
+        comp = composite_options(config)   # (refuses the composite keys of an entry without a mask before anything runs)
         if masked is not None:
             mask = load_edit_mask(os.path.join(config.data_dir, masked[0]), config.n_frames, tuple(config.image_size))
             seed_everything(template_config.seed)
@@ -212,7 +217,13 @@ class Stage2:
         video = pipe.decode_latents(edited_latents, decode_chunk_size=1)  # (frame-parallel: every rank decodes its frames)
         if not self.writer:
             return
-        edited_video = pipe.vae.to_pil(video)
+        if comp is not None:
+            # pixel-space composite (optional keys ``edit_mask_composite*``): outside the entry's mask the files carry the source frames'
+            # bytes, not decode(encode(source)); inside, the bytes ``to_pil`` forms -- one pass over the decode's output on the device
+            frames_u8 = pipe.composite_over_source(video, frame_list, mask, grow=masked[1], feather=masked[2], **comp)
+            edited_video = [Image.fromarray(fr) for fr in frames_u8.cpu().numpy()]
+        else:
+            edited_video = pipe.vae.to_pil(video)
 
         output_dir = os.path.join(config.output_dir, output_suffix(config, t_idx))
         os.makedirs(output_dir, exist_ok=True)

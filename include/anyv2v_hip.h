@@ -428,6 +428,49 @@ int anyv2v_diff_map_accum_f16(const void* Vtok, int32_t ldv, int32_t C, int32_t 
 int anyv2v_diff_map_finish_f16(const float* acc, int32_t F, int32_t h, int32_t w, float ratio, float threshold, float* records, void* map,
                                void* pixel_mask, void* stream);
 
+/* Pixel-space composite behind the VAE decode of a masked edit: outside the edit region the frames written are the source's bytes, not
+ * decode(encode(source)).  Nothing in the reference does this (the pixel-space finish of Blended Latent Diffusion, arXiv 2206.02779;
+ * diffusers' apply_overlay).  Three entry points, no atomics, every output element written once by one thread.
+ *
+ * anyv2v_pixel_alpha_f16: latent mask fp16 [Fm, h, w] (what anyv2v_latent_mask_f16 wrote: alpha follows the region the latent blend
+ * used) -> alpha fp32 [Fm, 8 h, 8 w].
+ *   base(f, y, x) = lm(f, y / 8, x / 8) > 0     the support: a softly blended latent cell is neither source nor edit, it shows the decode
+ *   core = dilate(base, grow_px), wide = dilate(base, grow_px + R)     square-window maxima, positions outside the image ignored
+ *   a    = G * wide     separable: the row pass first, then the column pass, each in tap order in fp32 with fmaf, replicate padding
+ *   alpha = core ? 1.0f : min(a, 1.0f)
+ * so alpha is exactly 1 on the grown support, exactly 0 beyond grow_px + 2 R of it (the taps are >= 0 and the inputs 0 there) and falls
+ * off continuously in between.  R == 0: the hard mask, alpha = core.  grow_px in [0, ANYV2V_COMPOSITE_MAX_GROW], R in
+ * [0, ANYV2V_COMPOSITE_MAX_RADIUS], taps = 2 R + 1 weights in [0, 1] (NULL when R == 0) on the HOST, copied into the launch.
+ * Dilation and feather are separable two-pass kernels, O(grow_px + R) per output.  workspace: 2 * Fm * 8 h * 8 w floats.
+ *
+ * anyv2v_composite_stats_u8: the statistics of the colour match over the KEPT region (alpha == 0), per channel, per clip (a per-frame gain
+ * would flicker).  video fp16 [1, 3, F, H, W] (the decode's output, in [-1, 1]), source uint8 [F, H, W, 3], alpha fp32 [Fm, H, W], Fm 1 or
+ * F.  e = the byte vae.to_pil forms from the video value (below), s = the source byte.  A fixed grid of ANYV2V_COMPOSITE_STATS_BLOCKS
+ * blocks writes one record of ANYV2V_COMPOSITE_STATS_RECORD int64 each: for channel c at [5 c .. 5 c + 4] count, sum e, sum e^2, sum s,
+ * sum s^2, [15] = 0.  Exact integer sums: independent of the order, bit-reproducible.
+ *
+ * anyv2v_composite_u8: out uint8 [F, H, W, 3].  Per element
+ *   e   = the level ((v + 1.0) * 127.5).round().clamp(0, 255) of an fp16 tensor: sum and product each rounded to fp16, round-half-even;
+ *         NaN -> 0, +Inf -> 255, -Inf -> 0 (the bytes vae.to_pil writes for the same value)
+ *   out = alpha == 0 ? s : alpha == 1 ? e : rint(fmaf(alpha, e - s, s))     selects, never multiplies: a kept pixel is the source's byte
+ *         whatever the decode holds, a fully edited pixel is the byte written without the composite
+ * records != NULL (the colour match): every block folds the records in record order and forms per channel, in fp64,
+ *   mean = sum / count, var = max(sum2 / count - mean^2, 0), gain = clamp(sqrt(var_s) / sqrt(var_e), 0.5, 2), bias = mean_s - gain mean_e,
+ * both rounded to fp32; the identity (1, 0) when count < 64 or var_e == 0.  e' = clamp(fmaf(gain, e, bias), 0, 255) stands in for e
+ * wherever alpha > 0 and the result is rounded once, by the rint at the end.
+ * 4 pixels per thread when H W % 4 == 0 and video / alpha / source / out are 8 / 16 / 4 / 4-byte aligned, a scalar kernel otherwise --
+ * chosen here, on the host.  out may not alias an input. */
+#define ANYV2V_COMPOSITE_MAX_GROW 64
+#define ANYV2V_COMPOSITE_MAX_RADIUS 48
+#define ANYV2V_COMPOSITE_STATS_BLOCKS 256
+#define ANYV2V_COMPOSITE_STATS_RECORD 16
+int anyv2v_pixel_alpha_f16(const void* latent_mask, int32_t mask_frames, int32_t h, int32_t w, int32_t grow_px, const float* taps, int32_t R,
+                           float* workspace, float* alpha, void* stream);
+int anyv2v_composite_stats_u8(const void* video, const void* source, const float* alpha, int32_t mask_frames, int32_t F, int32_t H, int32_t W,
+                              int64_t* records, void* stream);
+int anyv2v_composite_u8(const void* video, const void* source, const float* alpha, int32_t mask_frames, const int64_t* records, void* out,
+                        int32_t F, int32_t H, int32_t W, void* stream);
+
 /* Plain elementwise DDIM / inverse-DDIM step (eta = 0, v-prediction) on same-layout tensors:
  * the generic `scheduler.step(model_output, t, sample).prev_sample` (pipeline_i2vgen_xl.py:868,1173,1418). */
 int anyv2v_ddim_step_f16(const void* V, const void* X, void* Y, float sa_t, float sb_t, float sa_p, float sb_p,
@@ -470,7 +513,8 @@ const char* anyv2v_last_error(void);
  * gn_groups (GroupNorm statistics from the GEMM epilogue), anyv2v_gemm_gn_stats_floats, anyv2v_gemm_gn_launches,
  * anyv2v_groupnorm_stats_floats, anyv2v_groupnorm_apply_stats_f16; nothing earlier changed (a 104 caller that zero-initialises its descriptors, as required,
  * must still be recompiled against this header because the structure grew).  anyv2v_freeu_f16, anyv2v_tile_blend_f16, anyv2v_latent_mask_f16,
- * anyv2v_masked_blend_f16, anyv2v_diff_map_accum_f16 and anyv2v_diff_map_finish_f16 were added under 105: new entry points, no structure changed
+ * anyv2v_masked_blend_f16, anyv2v_diff_map_accum_f16, anyv2v_diff_map_finish_f16, anyv2v_pixel_alpha_f16, anyv2v_composite_stats_u8 and
+ * anyv2v_composite_u8 were added under 105: new entry points, no structure changed
  * (a binding that needs them finds out when it resolves the symbol). */
 #define ANYV2V_ABI_VERSION 105
 int anyv2v_version(void);
