@@ -73,6 +73,8 @@ DIFF_MAP_BLOCKS, DIFF_MAP_THREADS = 64, 256
 # anyv2v_pixel_alpha_f16 / anyv2v_composite_stats_u8: the largest pixel grow and feather radius, the fixed grid of the colour statistics and
 # the int64 entries of a block's record (ANYV2V_COMPOSITE_* of include/anyv2v_hip.h)
 COMPOSITE_MAX_GROW, COMPOSITE_MAX_RADIUS, COMPOSITE_STATS_BLOCKS, COMPOSITE_STATS_RECORD = 64, 48, 256, 16
+# anyv2v_block_match_u8: the largest search radius (ANYV2V_TRACK_MAX_RADIUS of include/anyv2v_hip.h)
+TRACK_MAX_RADIUS = 32
 
 
 class FFDesc(C.Structure):
@@ -138,6 +140,11 @@ SYMBOLS = {
     "anyv2v_pixel_alpha_f16": (C.c_int, [_VP, _I32, _I32, _I32, _I32, C.POINTER(C.c_float), _I32, _VP, _VP, _VP]),
     "anyv2v_composite_stats_u8": (C.c_int, [_VP, _VP, _VP, _I32, _I32, _I32, _I32, _VP, _VP]),
     "anyv2v_composite_u8": (C.c_int, [_VP, _VP, _VP, _I32, _VP, _VP, _I32, _I32, _I32, _VP]),
+    "anyv2v_luma_u8": (C.c_int, [_VP, _VP, _I32, _I32, _I32, _VP]),
+    "anyv2v_block_match_u8": (C.c_int, [_VP, _VP, _I32, _I32, _I32, _I32, _VP]),
+    "anyv2v_flow_median_i16": (C.c_int, [_VP, _VP, _I32, _I32, _I32, _VP]),
+    "anyv2v_mask_propagate_u8": (C.c_int, [_VP, _VP, _VP, _I32, _I32, _I32, _VP]),
+    "anyv2v_first_frame_mask_u8": (C.c_int, [_VP, _VP, _VP, _I32, _I32, _I32, _I32, _VP]),
     "anyv2v_ddim_step_f16": (C.c_int, [_VP, _VP, _VP, _F32, _F32, _F32, _F32, _I64, _VP]),
     "anyv2v_guided_step_f16": (C.c_int, [_VP, _I64, _I32, _I32, _I32, _F32, _F32, _I32, _F32, _F32, _F32, _F32, _VP, _VP, _VP]),
     "anyv2v_guided_step_noise_f16": (C.c_int, [_VP, _I64, _I32, _I32, _I32, _F32, _F32, _I32, _F32, _F32, _F32, _F32, _VP, _VP, _VP, _F32, _VP]),

@@ -20,7 +20,7 @@ from typing import List, Optional
 import torch
 from PIL import Image
 
-from .config import OmegaConf, auto_mask_options, composite_options, sampler_options
+from .config import OmegaConf, auto_mask_options, composite_options, first_frame_mask_options, sampler_options, track_options
 from .pipeline import I2VGenXLPipeline
 from .run_group_ddim_inversion import ddim_inversion
 from .pnp_utils import clear_time
@@ -52,7 +52,10 @@ class AnyV2V_I2VGenXL:
         # default inversion / edit configuration of the demo (gradio_demo.py:60-78); ``pnp_config`` also takes the optional keys
         # ``eta`` / ``guidance_rescale`` (``config.sampler_options``; e.g. ``obj.config.pnp_config.eta = 0.5``) and ``edit_mask_auto`` with
         # its tuning keys and ``edit_mask_grow`` / ``edit_mask_feather`` (``config.auto_mask_options``), and ``edit_mask_composite`` with its
-        # shaping keys (``config.composite_options``: the source frames pasted back outside the generated mask), absent = off
+        # shaping keys (``config.composite_options``: the source frames pasted back outside the mask), and ``edit_mask_first_frame`` /
+        # ``edit_mask_track`` with their tuning keys (``config.first_frame_mask_options`` / ``track_options``: the mask is where the edited
+        # first frame differs from the source's, carried through the clip along the source's motion -- a local edit with no extra
+        # input), absent = off
         self.config = OmegaConf.create({
             "inverse_config": {"image_size": [512, 512], "n_frames": 16, "cfg": 1.0, "target_fps": 8, "ddim_inv_prompt": "",
                                "prompt": "", "negative_prompt": ""},
@@ -125,7 +128,11 @@ class AnyV2V_I2VGenXL:
         cfg.pnp_config.ddim_init_latents_t_idx = ddim_init_latents_t_idx
         self.pipe.register_modules(scheduler=self.ddim_scheduler)
         auto = auto_mask_options(cfg.pnp_config)
-        comp = composite_options(cfg.pnp_config)   # (refused without ``edit_mask_auto``: this class loads no mask file)
+        ff = first_frame_mask_options(cfg.pnp_config)
+        track = track_options(cfg.pnp_config)
+        if track is not None and ff is None:
+            raise ValueError("edit_mask_track without edit_mask_first_frame: this class loads no mask file")
+        comp = composite_options(cfg.pnp_config)   # (refused without a mask key: this class loads no mask file)
         if auto is not None:
             # automatic edit mask: from the trajectory in HBM (deterministic, one map), before this edit's hooks are registered
             clear_time(self.pipe)
@@ -136,11 +143,19 @@ class AnyV2V_I2VGenXL:
                 ddim_inv_latents_path=trajectory, num_frames=cfg.inverse_config.n_frames, target_fps=cfg.pnp_config.target_fps,
                 num_inference_steps=num_inference_steps, num_maps_per_mask=auto["maps"], mask_encode_strength=auto["strength"],
                 mask_thresholding_ratio=auto["ratio"], threshold=auto["threshold"], **size)
+        elif ff is not None:
+            # first-frame mask: the edited first frame is at the clip's size already; tracked along the source frames when asked for
+            source_latents = self.pipe.encode_vae_video(frame_list, device=self.device, height=cfg.inverse_config.image_size[1],
+                                                        width=cfg.inverse_config.image_size[0])
+            mask = self.pipe.first_frame_edit_mask(first_frame, edited_1st_frame, threshold=ff["threshold"], min_count=ff["min_count"])
+            if track is not None:
+                mask = self.pipe.propagate_edit_mask(frame_list, mask, radius=track["radius"], median=track["median"])
+        masked = auto if auto is not None else ff   # (either holds the ``grow`` / ``feather`` the blend and the composite read)
         init_pnp(self.pipe, self.ddim_scheduler, cfg.pnp_config)
         eta, rescale = sampler_options(cfg.pnp_config)
         self.pipe.enable_guidance_rescale(rescale)
-        if auto is not None:
-            self.pipe.enable_masked_edit(mask, source_latents, grow=auto["grow"], feather=auto["feather"])
+        if masked is not None:
+            self.pipe.enable_masked_edit(mask, source_latents, grow=masked["grow"], feather=masked["feather"])
         try:
             edited_video = self.pipe.sample_with_pnp(
                 prompt=video_prompt, image=edited_1st_frame, height=cfg.inverse_config.image_size[1],
@@ -153,11 +168,11 @@ class AnyV2V_I2VGenXL:
             if comp is None:
                 edited_video = edited_video[0]
             else:   # the decode the call above would have made, and the source frames pasted back outside the mask
-                frames_u8 = self.pipe.composite_over_source(self.pipe.decode_latents(edited_video, decode_chunk_size=1), frame_list, mask, grow=auto["grow"],
-                                                            feather=auto["feather"], **comp)
+                frames_u8 = self.pipe.composite_over_source(self.pipe.decode_latents(edited_video, decode_chunk_size=1), frame_list, mask, grow=masked["grow"],
+                                                            feather=masked["feather"], **comp)
                 edited_video = [Image.fromarray(fr) for fr in frames_u8.cpu().numpy()]
         finally:
-            if auto is not None:
+            if masked is not None:
                 self.pipe.disable_masked_edit()   # the mask belongs to this clip
         edited_video = [f.resize(tuple(cfg.inverse_config.image_size), resample=Image.LANCZOS) for f in edited_video]
         output_path = os.path.join(tmp_dir, "edited_video.mp4")

@@ -135,13 +135,83 @@ def masked_edit_options(config):
     without a path are refused, not dropped -- unless the mask is an automatic one (``auto_mask_options``), which they then shape."""
     path, grow, feather = _option(config, "edit_mask_path"), _option(config, "edit_mask_grow"), _option(config, "edit_mask_feather")
     if path is None:
-        if (grow is not None or feather is not None) and not _auto_mask_on(config):
+        if (grow is not None or feather is not None) and not _auto_mask_on(config) and not _first_frame_mask_on(config):
             raise ValueError("edit_mask_grow / edit_mask_feather without edit_mask_path: there is no mask to grow or feather")
         return None
     if _auto_mask_on(config):
         raise ValueError("edit_mask_auto together with edit_mask_path: the mask is either generated or loaded")
+    if _first_frame_mask_on(config):
+        raise ValueError("edit_mask_first_frame together with edit_mask_path: the mask is either derived from the first frames or loaded")
     grow, feather = _grow_feather(grow, feather)
     return str(path), grow, feather
+
+
+def _first_frame_mask_on(config) -> bool:
+    v = _option(config, "edit_mask_first_frame")
+    if v is not None and not isinstance(v, bool):
+        raise ValueError(f"edit_mask_first_frame={v!r}: true or false")
+    return bool(v)
+
+
+def _int_option(key, v, default, lo, hi):
+    v = default if v is None else v
+    if isinstance(v, bool) or not isinstance(v, (int, float)) or not lo <= v <= hi or int(v) != v:   # (also refuses NaN)
+        raise ValueError(f"{key}={v}: an integer, {lo} <= {key} <= {hi}")
+    return int(v)
+
+
+FIRST_FRAME_MASK_DEFAULTS = dict(threshold=24, min_count=8)   # ``I2VGenXLPipeline.first_frame_edit_mask``'s
+
+
+def first_frame_mask_options(config):
+    """The first-frame difference mask of a PnP-edit configuration (``I2VGenXLPipeline.first_frame_edit_mask``), or None: OPTIONAL keys the
+    reference's files do not have -- ``edit_mask_first_frame`` (bool) switches it on, ``edit_mask_first_frame_threshold`` (integer 0 .. 255)
+    and ``edit_mask_first_frame_min_count`` (integer 1 .. 64) tune it; ``edit_mask_grow`` / ``edit_mask_feather`` shape the mask as they
+    shape a loaded one.  -> dict(threshold, min_count, grow, feather).  A third source of the mask, exclusive with ``edit_mask_path`` and
+    ``edit_mask_auto``; alone it is a static [1, H, W] mask like a single PNG, ``edit_mask_track`` (``track_options``) carries it through the
+    clip.  Absent, null or false: None, and the entry runs and writes exactly what it did before the keys existed; the tuning keys without
+    the switch are refused, not dropped."""
+    vals = {k: _option(config, "edit_mask_first_frame_" + k) for k in FIRST_FRAME_MASK_DEFAULTS}
+    if not _first_frame_mask_on(config):
+        given = [k for k, v in vals.items() if v is not None]
+        if given:
+            raise ValueError(f"edit_mask_first_frame_{given[0]} without edit_mask_first_frame: there is no first-frame mask to tune")
+        return None
+    if _option(config, "edit_mask_path") is not None:
+        raise ValueError("edit_mask_first_frame together with edit_mask_path: the mask is either derived from the first frames or loaded")
+    if _auto_mask_on(config):
+        raise ValueError("edit_mask_first_frame together with edit_mask_auto: the mask is either derived from the first frames or generated")
+    grow, feather = _grow_feather(_option(config, "edit_mask_grow"), _option(config, "edit_mask_feather"))
+    return dict(threshold=_int_option("edit_mask_first_frame_threshold", vals["threshold"], FIRST_FRAME_MASK_DEFAULTS["threshold"], 0, 255),
+                min_count=_int_option("edit_mask_first_frame_min_count", vals["min_count"], FIRST_FRAME_MASK_DEFAULTS["min_count"], 1, 64),
+                grow=grow, feather=feather)
+
+
+TRACK_DEFAULTS = dict(radius=16, median=True)   # ``I2VGenXLPipeline.propagate_edit_mask``'s
+
+
+def track_options(config):
+    """The mask tracking of a PnP-edit configuration (``I2VGenXLPipeline.propagate_edit_mask``), or None: OPTIONAL keys the reference's
+    files do not have -- ``edit_mask_track`` (bool) carries a one-frame mask through the clip along the block-matched motion of the source
+    frames, ``edit_mask_track_radius`` (pixels per frame, integer 0 .. 32) and ``edit_mask_track_median`` (bool) tune it.
+    -> dict(radius, median).  It needs a one-frame mask: ``edit_mask_first_frame``, or an ``edit_mask_path`` that is a single file (the
+    runner refuses a directory of per-frame masks); an automatic mask already has every frame, so ``edit_mask_auto`` is refused.  Absent,
+    null or false: None; the tuning keys without the switch are refused, not dropped."""
+    on, median, radius = _option(config, "edit_mask_track"), _option(config, "edit_mask_track_median"), _option(config, "edit_mask_track_radius")
+    for key, v in (("edit_mask_track", on), ("edit_mask_track_median", median)):
+        if v is not None and not isinstance(v, bool):
+            raise ValueError(f"{key}={v!r}: true or false")
+    if not on:
+        for key, v in (("edit_mask_track_radius", radius), ("edit_mask_track_median", median)):
+            if v is not None:
+                raise ValueError(f"{key} without edit_mask_track: there is no tracking to tune")
+        return None
+    if _auto_mask_on(config):
+        raise ValueError("edit_mask_track together with edit_mask_auto: the generated mask already has every frame")
+    if _option(config, "edit_mask_path") is None and not _first_frame_mask_on(config):
+        raise ValueError("edit_mask_track without edit_mask_first_frame or edit_mask_path: there is no frame-0 mask to carry")
+    return dict(radius=_int_option("edit_mask_track_radius", radius, TRACK_DEFAULTS["radius"], 0, 32),
+                median=TRACK_DEFAULTS["median"] if median is None else median)
 
 
 AUTO_MASK_DEFAULTS = dict(maps=10, strength=0.5, ratio=3.0, threshold=0.5)   # ``I2VGenXLPipeline.generate_edit_mask``'s (diffusers' generate_mask)
@@ -163,6 +233,8 @@ def auto_mask_options(config):
         return None
     if _option(config, "edit_mask_path") is not None:
         raise ValueError("edit_mask_auto together with edit_mask_path: the mask is either generated or loaded")
+    if _first_frame_mask_on(config):
+        raise ValueError("edit_mask_first_frame together with edit_mask_auto: the mask is either derived from the first frames or generated")
     maps = AUTO_MASK_DEFAULTS["maps"] if vals["maps"] is None else vals["maps"]
     if isinstance(maps, bool) or not isinstance(maps, (int, float)) or not 1 <= maps < 2 ** 31 or int(maps) != maps:   # (refuses NaN)
         raise ValueError(f"edit_mask_auto_maps={maps}: an integer >= 1")
@@ -197,7 +269,7 @@ def composite_options(config):
             if v is not None:
                 raise ValueError(f"{key} without edit_mask_composite: there is no composite to shape")
         return None
-    if _option(config, "edit_mask_path") is None and not _auto_mask_on(config):
+    if _option(config, "edit_mask_path") is None and not _auto_mask_on(config) and not _first_frame_mask_on(config):
         raise ValueError("edit_mask_composite without edit_mask_path or edit_mask_auto: there is no mask to composite by")
     grow = 0 if grow is None else grow
     feather = 0.0 if feather is None else float(feather)

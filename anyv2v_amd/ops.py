@@ -711,6 +711,83 @@ def composite(video: torch.Tensor, source_u8: torch.Tensor, alpha: torch.Tensor,
     return out
 
 
+def _track_frames(what, t, last=None):
+    shape = ("F", "H", "W") + (() if last is None else (str(last),))
+    assert t.dtype == torch.uint8 and t.is_contiguous() and t.dim() == len(shape) and (last is None or t.shape[-1] == last) \
+        and t.shape[0] >= 1 and t.shape[1] >= 8 and t.shape[2] >= 8 and t.shape[1] % 8 == 0 and t.shape[2] % 8 == 0, \
+        f"{what}: contiguous uint8 [{', '.join(shape)}] with H, W positive multiples of 8 expected, got {tuple(t.shape)} {t.dtype}"
+    return int(t.shape[0]), int(t.shape[1]), int(t.shape[2])
+
+
+def luma_u8(frames: torch.Tensor):
+    """uint8 [F, H, W, 3] -> uint8 [F, H, W], ``Y = (77 R + 150 G + 29 B + 128) >> 8`` (``anyv2v_luma_u8``)."""
+    lib = _lib.load()
+    F, H, W = _track_frames("luma_u8", frames, 3)
+    out = torch.empty((F, H, W), dtype=torch.uint8, device=frames.device)
+    _lib.check(lib.anyv2v_luma_u8(_p(frames), _p(out), F, H, W, _stream()), "anyv2v_luma_u8")
+    return out
+
+
+def block_match(luma: torch.Tensor, radius: int = 16):
+    """Luma uint8 [F, H, W] -> int16 [F, H / 8, W / 8, 2], per frame k >= 1 and 8 x 8 cell the displacement (dy, dx) in [-radius, radius]^2
+    that minimises (SAD of the cell's 16 x 16 window of frame k against frame k - 1, dy^2 + dx^2, dy, dx); frame 0: zeros
+    (``anyv2v_block_match_u8``; the definition is in ``include/anyv2v_hip.h``).  ``radius``: an integer 0 .. 32."""
+    lib = _lib.load()
+    F, H, W = _track_frames("block_match", luma)
+    if isinstance(radius, bool) or not 0 <= radius <= _lib.TRACK_MAX_RADIUS or int(radius) != radius:   # (the range check also refuses NaN)
+        raise ValueError(f"radius={radius}: an integer, 0 <= radius <= {_lib.TRACK_MAX_RADIUS} pixels")
+    out = torch.empty((F, H // 8, W // 8, 2), dtype=torch.int16, device=luma.device)
+    _lib.check(lib.anyv2v_block_match_u8(_p(luma), _p(out), F, H, W, int(radius), _stream()), "anyv2v_block_match_u8")
+    return out
+
+
+def _track_flow(what, flow):
+    assert flow.dtype == torch.int16 and flow.is_contiguous() and flow.dim() == 4 and flow.shape[3] == 2 and min(flow.shape[:3]) >= 1, \
+        f"{what}: contiguous int16 [F, h, w, 2] expected, got {tuple(flow.shape)} {flow.dtype}"
+    return (int(v) for v in flow.shape[:3])
+
+
+def flow_median(flow: torch.Tensor):
+    """int16 [F, h, w, 2] -> the same with every component replaced by the median of its 3 x 3 cell neighbourhood, replicate border
+    (``anyv2v_flow_median_i16``)."""
+    lib = _lib.load()
+    F, h, w = _track_flow("flow_median", flow)
+    out = torch.empty_like(flow)
+    _lib.check(lib.anyv2v_flow_median_i16(_p(flow), _p(out), F, h, w, _stream()), "anyv2v_flow_median_i16")
+    return out
+
+
+def mask_propagate(mask0: torch.Tensor, flow: torch.Tensor):
+    """Frame-0 mask [H, W] (bool, or uint8 with non-zero = set) carried along ``flow`` int16 [F, H / 8, W / 8, 2] -> bool [F, H, W] with
+    ``mask_k[p] = mask_{k-1}[clamp(p + D_k[cell(p)])]`` (``anyv2v_mask_propagate_u8``: one launch, the chain walked per pixel)."""
+    lib = _lib.load()
+    F, h, w = _track_flow("mask_propagate", flow)
+    assert mask0.dtype in (torch.bool, torch.uint8) and mask0.is_contiguous() and tuple(mask0.shape) == (8 * h, 8 * w) \
+        and mask0.device == flow.device, \
+        f"mask_propagate: contiguous bool / uint8 mask [{8 * h}, {8 * w}] expected for a flow of {tuple(flow.shape)}, got {tuple(mask0.shape)} {mask0.dtype}"
+    out = torch.empty((F, 8 * h, 8 * w), dtype=torch.uint8, device=flow.device)
+    _lib.check(lib.anyv2v_mask_propagate_u8(_p(mask0), _p(flow), _p(out), F, 8 * h, 8 * w, _stream()), "anyv2v_mask_propagate_u8")
+    return out.view(torch.bool)
+
+
+def first_frame_mask(source: torch.Tensor, edited: torch.Tensor, threshold: int = 24, min_count: int = 8):
+    """Source and edited first frame, uint8 [H, W, 3] -> bool [1, H, W], constant on 8 x 8 cells: a cell is set when at least
+    ``min_count`` (1 .. 64) of its pixels have ``max_c |edited - source| > threshold`` (strict, 0 .. 255) (``anyv2v_first_frame_mask_u8``)."""
+    lib = _lib.load()
+    _, H, W = _track_frames("first_frame_mask", source[None] if source.dim() == 3 else source, 3)
+    assert source.dim() == 3 and edited.dtype == torch.uint8 and edited.is_contiguous() and edited.shape == source.shape \
+        and edited.device == source.device, \
+        f"first_frame_mask: edited {tuple(edited.shape)} {edited.dtype} against source {tuple(source.shape)}: the same uint8 [H, W, 3] expected"
+    if isinstance(threshold, bool) or not 0 <= threshold <= 255 or int(threshold) != threshold:
+        raise ValueError(f"threshold={threshold}: an integer, 0 <= threshold <= 255")
+    if isinstance(min_count, bool) or not 1 <= min_count <= 64 or int(min_count) != min_count:
+        raise ValueError(f"min_count={min_count}: an integer, 1 <= min_count <= 64")
+    out = torch.empty((1, H, W), dtype=torch.uint8, device=source.device)
+    _lib.check(lib.anyv2v_first_frame_mask_u8(_p(source), _p(edited), _p(out), H, W, int(threshold), int(min_count), _stream()),
+               "anyv2v_first_frame_mask_u8")
+    return out.view(torch.bool)
+
+
 def ddim_step(v: torch.Tensor, x: torch.Tensor, sa_t: float, sb_t: float, sa_p: float, sb_p: float, out=None):
     lib = _lib.load()
     v = v.to(torch.float16).contiguous()

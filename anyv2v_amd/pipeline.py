@@ -676,6 +676,85 @@ class I2VGenXLPipeline:
         alpha = ops.pixel_alpha(lm, int(grow_px), feather_px)
         return ops.composite(video.to(torch.float16).contiguous(), src.to(device).contiguous(), alpha, match_color)
 
+    @staticmethod
+    def _frames_u8(name, frames):
+        """A PIL image, a list of PIL images of one size, or a uint8 [H, W, 3] / [F, H, W, 3] tensor -> uint8 [F, H, W, 3] with H and W
+        positive multiples of 8 (nothing is resized, nothing is quantised)."""
+        if hasattr(frames, "convert"):
+            frames = [frames]
+        if torch.is_tensor(frames):
+            if frames.dtype != torch.uint8:
+                raise ValueError(f"{name}: a uint8 tensor expected, got {frames.dtype} (nothing is quantised here)")
+            t = frames[None] if frames.dim() == 3 else frames
+        elif isinstance(frames, (list, tuple)) and len(frames) > 0 and all(hasattr(f, "convert") for f in frames):
+            import numpy as np
+            sizes = {tuple(f.size) for f in frames}
+            if len(sizes) != 1:
+                raise ValueError(f"{name}: images of different sizes {sorted(sizes)} (nothing is resized here)")
+            t = torch.from_numpy(np.stack([np.asarray(f.convert("RGB"), dtype=np.uint8) for f in frames]))
+        else:
+            raise ValueError(f"{name}: PIL images or a uint8 [F, H, W, 3] tensor expected, got {type(frames).__name__}")
+        if t.dim() != 4 or t.shape[3] != 3 or t.shape[0] < 1 or t.shape[1] < 8 or t.shape[2] < 8 or t.shape[1] % 8 or t.shape[2] % 8:
+            raise ValueError(f"{name}: uint8 [F, H, W, 3] with H and W positive multiples of 8 expected, got {tuple(t.shape)}")
+        return t
+
+    @torch.no_grad()
+    def first_frame_edit_mask(self, source_first_frame, edited_first_frame, threshold: int = 24, min_count: int = 8):
+        """The one edit mask an AnyV2V job has for free: where the edited first frame differs from the source's -> bool [1, H, W] on the
+        execution device, constant on the 8 x 8 cells of the latent grid.  A pixel changed when ``max_c |edited - source| > threshold``
+        (strict, on the uint8 values, 0 .. 255); a cell is set when at least ``min_count`` (1 .. 64) of its 64 pixels changed.  Both frames:
+        a PIL image or a uint8 [H, W, 3] tensor of the same size, H and W multiples of 8.  Alone it is a static mask like a single PNG;
+        ``propagate_edit_mask`` carries it through the clip.  The result goes to ``enable_masked_edit`` / ``composite_over_source``
+        unchanged; ``edit_mask_grow`` remains the remedy for a border that is a cell too tight."""
+        src, ed = self._frames_u8("source_first_frame", source_first_frame), self._frames_u8("edited_first_frame", edited_first_frame)
+        if src.shape[0] != 1 or ed.shape[0] != 1:
+            raise ValueError(f"first_frame_edit_mask: one frame each expected, got {src.shape[0]} and {ed.shape[0]}")
+        if src.shape != ed.shape:
+            raise ValueError(f"edited_first_frame {tuple(ed.shape[1:])} does not match source_first_frame {tuple(src.shape[1:])} "
+                             "(nothing is resized here)")
+        if isinstance(threshold, bool) or not 0 <= threshold <= 255 or int(threshold) != threshold:   # (the range check also refuses NaN)
+            raise ValueError(f"threshold={threshold}: an integer, 0 <= threshold <= 255")
+        if isinstance(min_count, bool) or not 1 <= min_count <= 64 or int(min_count) != min_count:
+            raise ValueError(f"min_count={min_count}: an integer, 1 <= min_count <= 64")
+        device = self._execution_device
+        return ops.first_frame_mask(src[0].to(device).contiguous(), ed[0].to(device).contiguous(), int(threshold), int(min_count))
+
+    @torch.no_grad()
+    def propagate_edit_mask(self, source_frames, mask, radius: int = 16, median: bool = True, return_flow: bool = False):
+        """Carry a frame-0 edit mask through the clip along the motion of the SOURCE frames -> bool [F, H, W] on the execution device
+        (with ``return_flow`` also the int16 [F, H / 8, W / 8, 2] displacement field, (dy, dx) per frame and 8 x 8 cell).  Classical
+        full-search block matching on the luma (``ops.block_match``: per cell the displacement in [-radius, radius]^2 of its 16 x 16
+        window against the previous frame with the least sum of absolute differences; ties go to the shortest vector, so flat and
+        periodic regions stay put), a 3 x 3 median over the cells (``median``), then ``mask_k[p] = mask_{k-1}[clamp(p + D_k[cell(p)])]``.
+        All integers: bit-reproducible, no model involved, once per clip.  ``source_frames``: a list of F PIL images or a uint8
+        [F, H, W, 3] tensor; ``mask``: [H, W] or [1, H, W], bool or uint8 (non-zero = edit); ``radius``: an integer 0 .. 32 pixels per
+        frame.  Occlusions, sub-pixel motion and a coarse-to-fine search are outside the definition: motion beyond ``radius`` per frame is
+        not followed, and ``grow`` of ``enable_masked_edit`` (``edit_mask_grow``) is the remedy for a border that drifts by a cell.  The
+        result goes to ``enable_masked_edit`` / ``composite_over_source`` unchanged; no step engine, engine key or ``_masked_edit`` is
+        touched here."""
+        from . import _lib
+        src = self._frames_u8("source_frames", source_frames)
+        if not torch.is_tensor(mask) or mask.dim() not in (2, 3):
+            raise ValueError(f"edit mask: a [H, W] or [1, H, W] tensor expected, got {type(mask).__name__}"
+                             + (f" of shape {tuple(mask.shape)}" if torch.is_tensor(mask) else ""))
+        if mask.dtype not in (torch.bool, torch.uint8):
+            raise ValueError(f"edit mask: bool or uint8 expected (a soft mask has no position to carry), got {mask.dtype}")
+        if mask.dim() == 3 and mask.shape[0] != 1:
+            raise ValueError(f"edit mask {tuple(mask.shape)}: it already has {mask.shape[0]} frames; a frame-0 mask [H, W] or [1, H, W] expected")
+        m0 = mask[0] if mask.dim() == 3 else mask
+        if tuple(m0.shape) != tuple(src.shape[1:3]):
+            raise ValueError(f"edit mask {tuple(m0.shape)} does not match the frames: [H, W] = {list(src.shape[1:3])} expected")
+        if isinstance(radius, bool) or not 0 <= radius <= _lib.TRACK_MAX_RADIUS or int(radius) != radius:   # (the range check also refuses NaN)
+            raise ValueError(f"radius={radius}: an integer, 0 <= radius <= {_lib.TRACK_MAX_RADIUS} pixels")
+        if not isinstance(median, bool):
+            raise ValueError(f"median={median!r}: True or False")
+        device = self._execution_device
+        flow = ops.block_match(ops.luma_u8(src.to(device).contiguous()), int(radius))
+        if median:
+            flow = ops.flow_median(flow)
+        tracked = ops.mask_propagate(m0.to(device).contiguous(), flow)
+        return (tracked, flow) if return_flow else tracked
+
     def _refuse_masked_edit(self, what):
         """``__call__`` / ``invert``: no source branch, no trajectory to blend against -- a mask left set would be silently dropped."""
         if getattr(self, "_masked_edit", None) is not None:

@@ -9,6 +9,7 @@ inversion ignores them, and an edit that draws variance noise draws it inside it
 still writes what the serial order writes.  The masked-edit keys (``edit_mask_path`` / ``_grow`` / ``_feather``; ``config.masked_edit_options``)
 and the automatic-mask keys (``edit_mask_auto*``; ``config.auto_mask_options``: the handed-over trajectory makes it the deterministic variant)
 and the composite keys (``edit_mask_composite*`` / ``edit_mask_match_color``; ``config.composite_options``: the source frames pasted back behind the decode)
+and the first-frame mask and tracking keys (``edit_mask_first_frame*`` / ``edit_mask_track*``; ``config.first_frame_mask_options`` / ``track_options``)
 are stage 2's as well: ``Stage2.entry`` encodes the source frames it loads into the clean latent the last blend needs, on its own stream.
 
     python -m anyv2v_amd.run_group_anyv2v --inversion_template configs/group_ddim_inversion/template.yaml \\

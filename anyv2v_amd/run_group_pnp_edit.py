@@ -19,7 +19,8 @@ from pathlib import Path
 import torch
 from PIL import Image
 
-from .config import AUTO_MASK_DEFAULTS, OmegaConf, auto_mask_options, composite_options, masked_edit_options, sampler_options
+from .config import (AUTO_MASK_DEFAULTS, FIRST_FRAME_MASK_DEFAULTS, TRACK_DEFAULTS, OmegaConf, auto_mask_options, composite_options,
+                     first_frame_mask_options, masked_edit_options, sampler_options, track_options)
 from .encoders import attach_synthetic_encoders
 from .parallel import FrameParallel, gather_latents, init_distributed, seed_for_entry, shard_entries
 from .pipeline import I2VGenXLPipeline
@@ -51,8 +52,15 @@ def output_suffix(config, ddim_init_latents_t_idx) -> str:
     so two entries that differ in them alone do not overwrite each other and every other directory keeps the reference's name."""
     eta, rescale = sampler_options(config)
     masked = masked_edit_options(config)   # optional keys ``edit_mask_*``: a masked and an unmasked edit do not overwrite each other
-    mask_tag = "" if masked is None else ("_mask-" + os.path.splitext(os.path.basename(os.path.normpath(masked[0])))[0]
+    track = track_options(config)          # optional keys ``edit_mask_track*``: the one-frame mask carried through the clip
+    track_tag = "" if track is None else ("-track" + (f"_radius{track['radius']}" if track["radius"] != TRACK_DEFAULTS["radius"] else "")
+                                          + ("" if track["median"] else "_nomedian"))
+    mask_tag = "" if masked is None else ("_mask-" + os.path.splitext(os.path.basename(os.path.normpath(masked[0])))[0] + track_tag
                                           + (f"_grow{masked[1]}" if masked[1] > 0 else "") + (f"_feather{masked[2]}" if masked[2] > 0 else ""))
+    ff = first_frame_mask_options(config)  # optional keys ``edit_mask_first_frame*``: the parameters where they are not the defaults
+    if ff is not None:
+        mask_tag = ("_mask-ff" + "".join(f"_{k}{ff[k]}" for k in FIRST_FRAME_MASK_DEFAULTS if ff[k] != FIRST_FRAME_MASK_DEFAULTS[k]) + track_tag
+                    + (f"_grow{ff['grow']}" if ff["grow"] > 0 else "") + (f"_feather{ff['feather']}" if ff["feather"] > 0 else ""))
     auto = auto_mask_options(config)       # optional keys ``edit_mask_auto*``: the generated mask's parameters, where they are not the defaults
     if auto is not None:
         mask_tag = ("_mask-auto" + "".join(f"_{k}{auto[k]}" for k in AUTO_MASK_DEFAULTS if auto[k] != AUTO_MASK_DEFAULTS[k])
@@ -164,8 +172,12 @@ class Stage2:
         # seed BEFORE the entry is seeded below, so the draws of the edit itself are the ones of an unmasked entry.
         masked = masked_edit_options(config)
         auto = auto_mask_options(config)
+        ff = first_frame_mask_options(config)
+        track = track_options(config)
         comp = composite_options(config)   # (refuses the composite keys of an entry without a mask before anything runs)
         if masked is not None:
+            if track is not None and os.path.isdir(os.path.join(config.data_dir, masked[0])):
+                raise ValueError(f"edit_mask_track with a directory of masks ({masked[0]}): every frame already has its mask")
             mask = load_edit_mask(os.path.join(config.data_dir, masked[0]), config.n_frames, tuple(config.image_size))
             seed_everything(template_config.seed)
             source_latents = pipe.encode_vae_video(frame_list, device=pipe._execution_device, height=config.image_size[1],
@@ -187,6 +199,18 @@ class Stage2:
                 num_inference_steps=config.n_steps, num_maps_per_mask=auto["maps"], mask_encode_strength=auto["strength"],
                 mask_thresholding_ratio=auto["ratio"], threshold=auto["threshold"], generator=torch.manual_seed(template_config.seed), **src)
             masked = (None, auto["grow"], auto["feather"])
+        elif ff is not None:
+            # first-frame mask (optional keys ``edit_mask_first_frame*``): where the edited first frame differs from the source's; no model,
+            # no draw.  The clean latent is encoded under the template's seed like the ones above.
+            seed_everything(template_config.seed)
+            source_latents = pipe.encode_vae_video(frame_list, device=pipe._execution_device, height=config.image_size[1],
+                                                   width=config.image_size[0])
+            mask = pipe.first_frame_edit_mask(src_1st_frame, edited_1st_frame, threshold=ff["threshold"], min_count=ff["min_count"])
+            masked = (None, ff["grow"], ff["feather"])
+        if track is not None:
+            # tracking (optional keys ``edit_mask_track*``): the one-frame mask, derived or loaded, carried along the source frames' motion
+            # (a loaded PNG: every non-black pixel is carried as "edit" -- a grey level has no position to follow)
+            mask = pipe.propagate_edit_mask(frame_list, mask, radius=track["radius"], median=track["median"])
         seed_everything(seed_for_entry(template_config.seed, entry_idx) if self.e_world > 1 else template_config.seed)
         random_latents = torch.randn(ddim_latents_at_t.shape, dtype=torch.float32).to(ddim_latents_at_t)  # drawn even if unused (:124)
         logger.info(f"Blending random_ratio (1 means random latent): {config.random_ratio}")
@@ -235,7 +259,7 @@ class Stage2:
         logger.info(f"Saved gif to: {os.path.join(output_dir, f'{name}.gif')}")
         for i, frame in enumerate(edited_video):
             frame.save(os.path.join(output_dir, f"{name}_{i:05d}.png"))
-        if auto is not None:   # the generated mask, one frame per file in the format ``load_edit_mask`` reads (white = edited)
+        if auto is not None or ff is not None or track is not None:   # the mask made here, one frame per file in the format ``load_edit_mask`` reads (white = edited)
             for i, plane in enumerate((mask.to(torch.uint8) * 255).cpu().numpy()):
                 Image.fromarray(plane, mode="L").save(os.path.join(output_dir, f"mask_{i:05d}.png"))
         torch.save(edited_latents.cpu(), os.path.join(output_dir, "edited_latents.pt"))

@@ -471,6 +471,40 @@ int anyv2v_composite_stats_u8(const void* video, const void* source, const float
 int anyv2v_composite_u8(const void* video, const void* source, const float* alpha, int32_t mask_frames, const int64_t* records, void* out,
                         int32_t F, int32_t H, int32_t W, void* stream);
 
+/* Mask tracking (track.hip): carry a frame-0 pixel mask through the clip along block-matched motion of the SOURCE frames (full-search
+ * block matching; nothing in the reference does this).  All integers, so every result is defined bit for bit.  Frames are uint8
+ * [F, H, W, 3] with H % 8 == 0, W % 8 == 0, F >= 1; cells are the 8 x 8 pixel blocks of the latent grid, h = H / 8, w = W / 8; clamp()
+ * clamps a pixel coordinate into the frame (replicate border).
+ *
+ * anyv2v_luma_u8: Y = (77 R + 150 G + 29 B + 128) >> 8, uint8 [F, H, W].
+ *
+ * anyv2v_block_match_u8: flow int16 [F, h, w, 2], ordered (dy, dx).  For frame k >= 1 and cell (cy, cx) the window is the 16 x 16 pixels
+ * centred on the cell (the cell plus 4 pixels on each side).  For every integer d = (dy, dx) in [-radius, radius]^2
+ *   cost(d) = sum over p in the window of |Y_k[clamp(p)] - Y_{k-1}[clamp(p + d)]|        (<= 65 280)
+ * and D_k[cy, cx] is the d that minimises the tuple (cost, dy^2 + dx^2, dy, dx) in lexicographic order: ties go to the shortest vector, so
+ * a flat or periodic region stays at zero displacement.  D_0 = 0; radius in [0, ANYV2V_TRACK_MAX_RADIUS], radius 0 gives all zeros.
+ * One block per 4 x 4 cells: Y_{k-1} with its halo staged in LDS already clamped, four pixels per v_sad_u8, an odd dx by byte-align
+ * operations on the same five dwords (identically for every dx), the winner by an integer key minimum -- no atomics, no floating point.
+ *
+ * anyv2v_flow_median_i16: every component replaced by the median of its 3 x 3 cell neighbourhood, replicate border, per frame; out may
+ * not alias the input.
+ *
+ * anyv2v_mask_propagate_u8: mask_0 uint8 [H, W] (non-zero = set) -> out uint8 [F, H, W] of 0 / 1 with
+ *   mask_k[p] = mask_{k-1}[clamp(p + D_k[cell(p)])],
+ * evaluated in one launch, one thread per output pixel: q = p; for j = k .. 1: q = clamp(q + D_j[cell(q)]); out = mask_0[q] != 0 (equal
+ * to the frame-after-frame warp by induction on k).  Any int16 flow is safe: every step is clamped into the frame.
+ *
+ * anyv2v_first_frame_mask_u8: source, edited uint8 [H, W, 3] -> mask uint8 [H, W] of 0 / 1, constant on cells:
+ *   changed[p] = max over c of |edited[p, c] - source[p, c]| > threshold      (strict; threshold in [0, 255])
+ *   a cell is set when at least min_count (1 .. 64) of its 64 pixels changed. */
+#define ANYV2V_TRACK_MAX_RADIUS 32
+int anyv2v_luma_u8(const void* frames, void* luma, int32_t F, int32_t H, int32_t W, void* stream);
+int anyv2v_block_match_u8(const void* luma, void* flow, int32_t F, int32_t H, int32_t W, int32_t radius, void* stream);
+int anyv2v_flow_median_i16(const void* flow, void* out, int32_t F, int32_t h, int32_t w, void* stream);
+int anyv2v_mask_propagate_u8(const void* mask0, const void* flow, void* out, int32_t F, int32_t H, int32_t W, void* stream);
+int anyv2v_first_frame_mask_u8(const void* source, const void* edited, void* mask, int32_t H, int32_t W, int32_t threshold,
+                               int32_t min_count, void* stream);
+
 /* Plain elementwise DDIM / inverse-DDIM step (eta = 0, v-prediction) on same-layout tensors:
  * the generic `scheduler.step(model_output, t, sample).prev_sample` (pipeline_i2vgen_xl.py:868,1173,1418). */
 int anyv2v_ddim_step_f16(const void* V, const void* X, void* Y, float sa_t, float sb_t, float sa_p, float sb_p,
@@ -513,8 +547,9 @@ const char* anyv2v_last_error(void);
  * gn_groups (GroupNorm statistics from the GEMM epilogue), anyv2v_gemm_gn_stats_floats, anyv2v_gemm_gn_launches,
  * anyv2v_groupnorm_stats_floats, anyv2v_groupnorm_apply_stats_f16; nothing earlier changed (a 104 caller that zero-initialises its descriptors, as required,
  * must still be recompiled against this header because the structure grew).  anyv2v_freeu_f16, anyv2v_tile_blend_f16, anyv2v_latent_mask_f16,
- * anyv2v_masked_blend_f16, anyv2v_diff_map_accum_f16, anyv2v_diff_map_finish_f16, anyv2v_pixel_alpha_f16, anyv2v_composite_stats_u8 and
- * anyv2v_composite_u8 were added under 105: new entry points, no structure changed
+ * anyv2v_masked_blend_f16, anyv2v_diff_map_accum_f16, anyv2v_diff_map_finish_f16, anyv2v_pixel_alpha_f16, anyv2v_composite_stats_u8,
+ * anyv2v_composite_u8, anyv2v_luma_u8, anyv2v_block_match_u8, anyv2v_flow_median_i16, anyv2v_mask_propagate_u8 and
+ * anyv2v_first_frame_mask_u8 were added under 105: new entry points, no structure changed
  * (a binding that needs them finds out when it resolves the symbol). */
 #define ANYV2V_ABI_VERSION 105
 int anyv2v_version(void);
