@@ -441,9 +441,9 @@ def test_gather_latents_raises_on_every_rank_together(tmp_path):
 
 
 # ------------------------------------------------------------------------------------------------- pipelined fused runner
-def _two_clip_job(base, tag, grouped=False):
-    """Two clips (the second: the first one's frames mirrored), three edits in an order that is NOT grouped by clip -- or, with
-    ``grouped``, the usual edit list grouped by clip ([clip, clip, clip2]: clip-wise dealing then differs from round-robin dealing)."""
+def _make_second_clip(base):
+    """``demo/clip2``: the first clip's frames mirrored (once per workspace; a test that spawns ranks makes it before it spawns them, so
+    that no two processes write it at the same time)."""
     clip, clip2 = os.path.join(base, "demo", "clip"), os.path.join(base, "demo", "clip2")
     if not os.path.isdir(clip2):
         os.makedirs(os.path.join(clip2, "edited_first_frame"))
@@ -451,6 +451,12 @@ def _two_clip_job(base, tag, grouped=False):
             Image.open(os.path.join(clip, f"{i:05d}.png")).transpose(Image.FLIP_LEFT_RIGHT).save(os.path.join(clip2, f"{i:05d}.png"))
         Image.open(os.path.join(clip, "edited_first_frame", "e.png")).transpose(Image.FLIP_TOP_BOTTOM).save(
             os.path.join(clip2, "edited_first_frame", "e.png"))
+
+
+def _two_clip_job(base, tag, grouped=False):
+    """Two clips (the second: the first one's frames mirrored), three edits in an order that is NOT grouped by clip -- or, with
+    ``grouped``, the usual edit list grouped by clip ([clip, clip, clip2]: clip-wise dealing then differs from round-robin dealing)."""
+    _make_second_clip(base)
     inv, inv_list, ed, ed_list = _configs(base, tag)
     inv_list = [dict(inv_list[0]), dict(inv_list[0], video_name="clip2")]
     e = ed_list[0]
@@ -562,6 +568,7 @@ def test_fused_runner_world2_deals_whole_clips_and_pipelines_them(tmp_path):
     import filecmp
     import torch.multiprocessing as mp
     base = _make_workspace(tmp_path)
+    _make_second_clip(base)
     for tag, pipelined in (("w2s", False), ("w2p", True)):
         mp.spawn(_clip_shard_worker, args=(2, _free_port(), base, tag, pipelined), nprocs=2, join=True)
         os.replace(os.path.join(base, "gathered_latents.pt"), os.path.join(base, f"gathered_{tag}.pt"))
