@@ -20,7 +20,8 @@ from typing import List, Optional
 import torch
 from PIL import Image
 
-from .config import OmegaConf, auto_mask_options, composite_options, first_frame_mask_options, sampler_options, track_options
+from .config import OmegaConf, sampler_options
+from .masked_edit import finish_frames, make_edit_mask, masked, plan_from_config
 from .pipeline import I2VGenXLPipeline
 from .run_group_ddim_inversion import ddim_inversion
 from .pnp_utils import clear_time
@@ -50,12 +51,10 @@ class AnyV2V_I2VGenXL:
     def __init__(self, model_path: str = MODEL_ID, device="cuda:0", tmp_dir: str = "_demo_temp", pipe: Optional[I2VGenXLPipeline] = None,
                  random_init_seed: Optional[int] = None, synthetic_encoders: bool = False) -> None:
         # default inversion / edit configuration of the demo (gradio_demo.py:60-78); ``pnp_config`` also takes the optional keys
-        # ``eta`` / ``guidance_rescale`` (``config.sampler_options``; e.g. ``obj.config.pnp_config.eta = 0.5``) and ``edit_mask_auto`` with
-        # its tuning keys and ``edit_mask_grow`` / ``edit_mask_feather`` (``config.auto_mask_options``), and ``edit_mask_composite`` with its
-        # shaping keys (``config.composite_options``: the source frames pasted back outside the mask), and ``edit_mask_first_frame`` /
-        # ``edit_mask_track`` with their tuning keys (``config.first_frame_mask_options`` / ``track_options``: the mask is where the edited
-        # first frame differs from the source's, carried through the clip along the source's motion -- a local edit with no extra
-        # input), absent = off
+        # ``eta`` / ``guidance_rescale`` (``config.sampler_options``; e.g. ``obj.config.pnp_config.eta = 0.5``) and the ``edit_mask_*`` keys of
+        # ``masked_edit.plan_from_config`` whose mask needs no file: ``edit_mask_auto`` or ``edit_mask_first_frame`` (where the edited first
+        # frame differs from the source's -- a local edit with no extra input) with their tuning keys, ``edit_mask_grow`` /
+        # ``edit_mask_feather``, ``edit_mask_track`` and ``edit_mask_composite`` with theirs; absent = off
         self.config = OmegaConf.create({
             "inverse_config": {"image_size": [512, 512], "n_frames": 16, "cfg": 1.0, "target_fps": 8, "ddim_inv_prompt": "",
                                "prompt": "", "negative_prompt": ""},
@@ -127,53 +126,41 @@ class AnyV2V_I2VGenXL:
         cfg.pnp_config.pnp_temp_attn_t = temp_inj
         cfg.pnp_config.ddim_init_latents_t_idx = ddim_init_latents_t_idx
         self.pipe.register_modules(scheduler=self.ddim_scheduler)
-        auto = auto_mask_options(cfg.pnp_config)
-        ff = first_frame_mask_options(cfg.pnp_config)
-        track = track_options(cfg.pnp_config)
-        if track is not None and ff is None:
-            raise ValueError("edit_mask_track without edit_mask_first_frame: this class loads no mask file")
-        comp = composite_options(cfg.pnp_config)   # (refused without a mask key: this class loads no mask file)
-        if auto is not None:
-            # automatic edit mask: from the trajectory in HBM (deterministic, one map), before this edit's hooks are registered
-            clear_time(self.pipe)
-            size = dict(height=cfg.inverse_config.image_size[1], width=cfg.inverse_config.image_size[0])
+        plan = plan_from_config(cfg.pnp_config)   # (refuses tracking and the composite without a mask key)
+        if plan is not None and plan.source == "path":   # this class loads no mask file: the key alone is ignored, what needs its mask is refused
+            if plan.track is not None or plan.composite is not None:
+                raise ValueError(f"edit_mask_{'track' if plan.track is not None else 'composite'} without edit_mask_first_frame: this class loads no mask file")
+            plan = None
+        size = dict(height=cfg.inverse_config.image_size[1], width=cfg.inverse_config.image_size[0])
+        mask = source_latents = None
+        if plan is not None:
             source_latents = self.pipe.encode_vae_video(frame_list, device=self.device, **size)
-            mask = self.pipe.generate_edit_mask(
-                prompt=video_prompt, image=edited_1st_frame, ddim_inv_prompt=cfg.inverse_config.ddim_inv_prompt, ddim_inv_1st_frame=first_frame,
-                ddim_inv_latents_path=trajectory, num_frames=cfg.inverse_config.n_frames, target_fps=cfg.pnp_config.target_fps,
-                num_inference_steps=num_inference_steps, num_maps_per_mask=auto["maps"], mask_encode_strength=auto["strength"],
-                mask_thresholding_ratio=auto["ratio"], threshold=auto["threshold"], **size)
-        elif ff is not None:
-            # first-frame mask: the edited first frame is at the clip's size already; tracked along the source frames when asked for
-            source_latents = self.pipe.encode_vae_video(frame_list, device=self.device, height=cfg.inverse_config.image_size[1],
-                                                        width=cfg.inverse_config.image_size[0])
-            mask = self.pipe.first_frame_edit_mask(first_frame, edited_1st_frame, threshold=ff["threshold"], min_count=ff["min_count"])
-            if track is not None:
-                mask = self.pipe.propagate_edit_mask(frame_list, mask, radius=track["radius"], median=track["median"])
-        masked = auto if auto is not None else ff   # (either holds the ``grow`` / ``feather`` the blend and the composite read)
+
+            def generate(auto):
+                # automatic edit mask: from the trajectory in HBM (deterministic, one map), before this edit's hooks are registered
+                clear_time(self.pipe)
+                return self.pipe.generate_edit_mask(
+                    prompt=video_prompt, image=edited_1st_frame, ddim_inv_prompt=cfg.inverse_config.ddim_inv_prompt, ddim_inv_1st_frame=first_frame,
+                    ddim_inv_latents_path=trajectory, num_frames=cfg.inverse_config.n_frames, target_fps=cfg.pnp_config.target_fps,
+                    num_inference_steps=num_inference_steps, num_maps_per_mask=auto["maps"], mask_encode_strength=auto["strength"],
+                    mask_thresholding_ratio=auto["ratio"], threshold=auto["threshold"], **size)
+            mask = make_edit_mask(self.pipe, plan, generate=generate, source_first_frame=first_frame, edited_first_frame=edited_1st_frame,
+                                  source_frames=frame_list)
         init_pnp(self.pipe, self.ddim_scheduler, cfg.pnp_config)
         eta, rescale = sampler_options(cfg.pnp_config)
         self.pipe.enable_guidance_rescale(rescale)
-        if masked is not None:
-            self.pipe.enable_masked_edit(mask, source_latents, grow=masked["grow"], feather=masked["feather"])
-        try:
+        comp = plan is not None and plan.composite is not None
+        with masked(self.pipe, plan, mask, source_latents):
             edited_video = self.pipe.sample_with_pnp(
-                prompt=video_prompt, image=edited_1st_frame, height=cfg.inverse_config.image_size[1],
-                width=cfg.inverse_config.image_size[0], num_frames=cfg.inverse_config.n_frames,
+                prompt=video_prompt, image=edited_1st_frame, num_frames=cfg.inverse_config.n_frames,
                 num_inference_steps=cfg.pnp_config.n_steps, guidance_scale=guidance_scale, negative_prompt=video_negative_prompt,
                 eta=eta, target_fps=cfg.pnp_config.target_fps, latents=mixed_latents, generator=generator, return_dict=True,
                 ddim_init_latents_t_idx=ddim_init_latents_t_idx, ddim_inv_latents_path=trajectory,
                 ddim_inv_prompt=cfg.inverse_config.ddim_inv_prompt, ddim_inv_1st_frame=first_frame,
-                **({} if comp is None else dict(output_type="latent"))).frames
-            if comp is None:
-                edited_video = edited_video[0]
-            else:   # the decode the call above would have made, and the source frames pasted back outside the mask
-                frames_u8 = self.pipe.composite_over_source(self.pipe.decode_latents(edited_video, decode_chunk_size=1), frame_list, mask, grow=masked["grow"],
-                                                            feather=masked["feather"], **comp)
-                edited_video = [Image.fromarray(fr) for fr in frames_u8.cpu().numpy()]
-        finally:
-            if masked is not None:
-                self.pipe.disable_masked_edit()   # the mask belongs to this clip
+                **size, **(dict(output_type="latent") if comp else {})).frames
+            # with the composite: the decode the call above would have made, and the source frames pasted back outside the mask
+            edited_video = finish_frames(self.pipe, plan, self.pipe.decode_latents(edited_video, decode_chunk_size=1), frame_list, mask) \
+                if comp else edited_video[0]
         edited_video = [f.resize(tuple(cfg.inverse_config.image_size), resample=Image.LANCZOS) for f in edited_video]
         output_path = os.path.join(tmp_dir, "edited_video.mp4")
         export_to_video(edited_video, output_path, fps=cfg.pnp_config.target_fps)

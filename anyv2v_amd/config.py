@@ -10,6 +10,8 @@ from typing import Any
 
 import yaml
 
+from .masked_edit import AUTO_MASK_DEFAULTS, COMPOSITE_DEFAULTS, FIRST_FRAME_MASK_DEFAULTS, TRACK_DEFAULTS, plan_from_config  # noqa: F401
+
 _PAT = re.compile(r"\$\{([^{}]+)\}")
 
 
@@ -106,178 +108,51 @@ def sampler_options(config) -> tuple:
     return one("eta"), one("guidance_rescale")
 
 
-def _option(config, key):
-    return config.get(key, None) if hasattr(config, "get") else getattr(config, key, None)   # (a ``Config`` or any plain namespace)
-
-
-def _auto_mask_on(config) -> bool:
-    v = _option(config, "edit_mask_auto")
-    if v is not None and not isinstance(v, bool):
-        raise ValueError(f"edit_mask_auto={v!r}: true or false")
-    return bool(v)
-
-
-def _grow_feather(grow, feather):
-    grow = 0 if grow is None else grow
-    feather = 0.0 if feather is None else float(feather)
-    if isinstance(grow, bool) or not 0 <= grow <= 8 or int(grow) != grow:   # (the range check also refuses NaN)
-        raise ValueError(f"edit_mask_grow={grow}: an integer, 0 <= edit_mask_grow <= 8")
-    if not 0.0 <= feather <= 8.0:   # (also refuses NaN)
-        raise ValueError(f"edit_mask_feather={feather}: 0 <= edit_mask_feather <= 8")
-    return int(grow), feather
-
-
+# The OPTIONAL ``edit_mask_*`` keys (the reference's files have none) are read, checked against each other and range-checked in ONE place,
+# ``masked_edit.plan_from_config``.  The five functions below document them and return their part of that plan, or None when it is off
+# (absent, null or false: the entry runs and writes exactly what it did before the keys existed).  A key with nothing to act on is refused.
 def masked_edit_options(config):
-    """(edit_mask_path, grow, feather) of a PnP-edit configuration, or None: three OPTIONAL keys the reference's files do not have --
-    ``edit_mask_path`` (one PNG, or a directory of ``%05d.png`` files; white = edit, black = keep the source), ``edit_mask_grow`` (latent
-    pixels, integer 0 .. 8) and ``edit_mask_feather`` (sigma in latent pixels, 0 .. 8) -- for ``I2VGenXLPipeline.enable_masked_edit``.
-    Without ``edit_mask_path`` (absent or null) the entry runs and writes exactly what it did before the keys existed; grow / feather
-    without a path are refused, not dropped -- unless the mask is an automatic one (``auto_mask_options``), which they then shape."""
-    path, grow, feather = _option(config, "edit_mask_path"), _option(config, "edit_mask_grow"), _option(config, "edit_mask_feather")
-    if path is None:
-        if (grow is not None or feather is not None) and not _auto_mask_on(config) and not _first_frame_mask_on(config):
-            raise ValueError("edit_mask_grow / edit_mask_feather without edit_mask_path: there is no mask to grow or feather")
-        return None
-    if _auto_mask_on(config):
-        raise ValueError("edit_mask_auto together with edit_mask_path: the mask is either generated or loaded")
-    if _first_frame_mask_on(config):
-        raise ValueError("edit_mask_first_frame together with edit_mask_path: the mask is either derived from the first frames or loaded")
-    grow, feather = _grow_feather(grow, feather)
-    return str(path), grow, feather
-
-
-def _first_frame_mask_on(config) -> bool:
-    v = _option(config, "edit_mask_first_frame")
-    if v is not None and not isinstance(v, bool):
-        raise ValueError(f"edit_mask_first_frame={v!r}: true or false")
-    return bool(v)
-
-
-def _int_option(key, v, default, lo, hi):
-    v = default if v is None else v
-    if isinstance(v, bool) or not isinstance(v, (int, float)) or not lo <= v <= hi or int(v) != v:   # (also refuses NaN)
-        raise ValueError(f"{key}={v}: an integer, {lo} <= {key} <= {hi}")
-    return int(v)
-
-
-FIRST_FRAME_MASK_DEFAULTS = dict(threshold=24, min_count=8)   # ``I2VGenXLPipeline.first_frame_edit_mask``'s
+    """-> (edit_mask_path, grow, feather) for ``I2VGenXLPipeline.enable_masked_edit``: ``edit_mask_path`` (one PNG, or a directory of
+    ``%05d.png`` files; white = edit, black = keep the source), ``edit_mask_grow`` (latent pixels, integer 0 .. 8) and ``edit_mask_feather``
+    (sigma in latent pixels, 0 .. 8).  Grow / feather without a path are refused -- unless the mask is an automatic or a first-frame one,
+    which they then shape."""
+    plan = plan_from_config(config)
+    return (plan.path, plan.grow, plan.feather) if plan is not None and plan.source == "path" else None
 
 
 def first_frame_mask_options(config):
-    """The first-frame difference mask of a PnP-edit configuration (``I2VGenXLPipeline.first_frame_edit_mask``), or None: OPTIONAL keys the
-    reference's files do not have -- ``edit_mask_first_frame`` (bool) switches it on, ``edit_mask_first_frame_threshold`` (integer 0 .. 255)
-    and ``edit_mask_first_frame_min_count`` (integer 1 .. 64) tune it; ``edit_mask_grow`` / ``edit_mask_feather`` shape the mask as they
-    shape a loaded one.  -> dict(threshold, min_count, grow, feather).  A third source of the mask, exclusive with ``edit_mask_path`` and
-    ``edit_mask_auto``; alone it is a static [1, H, W] mask like a single PNG, ``edit_mask_track`` (``track_options``) carries it through the
-    clip.  Absent, null or false: None, and the entry runs and writes exactly what it did before the keys existed; the tuning keys without
-    the switch are refused, not dropped."""
-    vals = {k: _option(config, "edit_mask_first_frame_" + k) for k in FIRST_FRAME_MASK_DEFAULTS}
-    if not _first_frame_mask_on(config):
-        given = [k for k, v in vals.items() if v is not None]
-        if given:
-            raise ValueError(f"edit_mask_first_frame_{given[0]} without edit_mask_first_frame: there is no first-frame mask to tune")
-        return None
-    if _option(config, "edit_mask_path") is not None:
-        raise ValueError("edit_mask_first_frame together with edit_mask_path: the mask is either derived from the first frames or loaded")
-    if _auto_mask_on(config):
-        raise ValueError("edit_mask_first_frame together with edit_mask_auto: the mask is either derived from the first frames or generated")
-    grow, feather = _grow_feather(_option(config, "edit_mask_grow"), _option(config, "edit_mask_feather"))
-    return dict(threshold=_int_option("edit_mask_first_frame_threshold", vals["threshold"], FIRST_FRAME_MASK_DEFAULTS["threshold"], 0, 255),
-                min_count=_int_option("edit_mask_first_frame_min_count", vals["min_count"], FIRST_FRAME_MASK_DEFAULTS["min_count"], 1, 64),
-                grow=grow, feather=feather)
-
-
-TRACK_DEFAULTS = dict(radius=16, median=True)   # ``I2VGenXLPipeline.propagate_edit_mask``'s
+    """-> dict(threshold, min_count, grow, feather) for ``I2VGenXLPipeline.first_frame_edit_mask``: ``edit_mask_first_frame`` (bool) switches
+    the first-frame difference mask on, ``edit_mask_first_frame_threshold`` (integer 0 .. 255) and ``edit_mask_first_frame_min_count``
+    (integer 1 .. 64) tune it; ``edit_mask_grow`` / ``edit_mask_feather`` shape it like a loaded one.  A third source of the mask, exclusive with
+    ``edit_mask_path`` and ``edit_mask_auto``; alone it is a static [1, H, W] mask like a single PNG, ``edit_mask_track`` carries it on."""
+    plan = plan_from_config(config)
+    return None if plan is None or plan.first_frame is None else dict(plan.first_frame, grow=plan.grow, feather=plan.feather)
 
 
 def track_options(config):
-    """The mask tracking of a PnP-edit configuration (``I2VGenXLPipeline.propagate_edit_mask``), or None: OPTIONAL keys the reference's
-    files do not have -- ``edit_mask_track`` (bool) carries a one-frame mask through the clip along the block-matched motion of the source
-    frames, ``edit_mask_track_radius`` (pixels per frame, integer 0 .. 32) and ``edit_mask_track_median`` (bool) tune it.
-    -> dict(radius, median).  It needs a one-frame mask: ``edit_mask_first_frame``, or an ``edit_mask_path`` that is a single file (the
-    runner refuses a directory of per-frame masks); an automatic mask already has every frame, so ``edit_mask_auto`` is refused.  Absent,
-    null or false: None; the tuning keys without the switch are refused, not dropped."""
-    on, median, radius = _option(config, "edit_mask_track"), _option(config, "edit_mask_track_median"), _option(config, "edit_mask_track_radius")
-    for key, v in (("edit_mask_track", on), ("edit_mask_track_median", median)):
-        if v is not None and not isinstance(v, bool):
-            raise ValueError(f"{key}={v!r}: true or false")
-    if not on:
-        for key, v in (("edit_mask_track_radius", radius), ("edit_mask_track_median", median)):
-            if v is not None:
-                raise ValueError(f"{key} without edit_mask_track: there is no tracking to tune")
-        return None
-    if _auto_mask_on(config):
-        raise ValueError("edit_mask_track together with edit_mask_auto: the generated mask already has every frame")
-    if _option(config, "edit_mask_path") is None and not _first_frame_mask_on(config):
-        raise ValueError("edit_mask_track without edit_mask_first_frame or edit_mask_path: there is no frame-0 mask to carry")
-    return dict(radius=_int_option("edit_mask_track_radius", radius, TRACK_DEFAULTS["radius"], 0, 32),
-                median=TRACK_DEFAULTS["median"] if median is None else median)
-
-
-AUTO_MASK_DEFAULTS = dict(maps=10, strength=0.5, ratio=3.0, threshold=0.5)   # ``I2VGenXLPipeline.generate_edit_mask``'s (diffusers' generate_mask)
+    """-> dict(radius, median) for ``I2VGenXLPipeline.propagate_edit_mask``: ``edit_mask_track`` (bool) carries a one-frame mask through the
+    clip along the block-matched motion of the source frames, ``edit_mask_track_radius`` (pixels per frame, integer 0 .. 32) and
+    ``edit_mask_track_median`` (bool) tune it.  It needs a one-frame mask: ``edit_mask_first_frame``, or an ``edit_mask_path`` that is a single
+    file (the runner refuses a directory of per-frame masks); an automatic mask already has every frame, so ``edit_mask_auto`` is refused."""
+    plan = plan_from_config(config)
+    return None if plan is None or plan.track is None else dict(plan.track)
 
 
 def auto_mask_options(config):
-    """The automatic edit mask of a PnP-edit configuration (``I2VGenXLPipeline.generate_edit_mask``), or None: OPTIONAL keys the reference's
-    files do not have -- ``edit_mask_auto`` (bool) switches it on, ``edit_mask_auto_maps`` (noise draws, integer >= 1),
-    ``edit_mask_auto_strength`` (0 < s <= 1: how far the source is noised), ``edit_mask_auto_ratio`` (> 0) and ``edit_mask_auto_threshold``
-    (in (0, 1)) tune it; ``edit_mask_grow`` / ``edit_mask_feather`` shape the generated mask as they shape a loaded one.
-    -> dict(maps, strength, ratio, threshold, grow, feather).  Absent, null or false: None, and the entry runs and writes exactly what it
-    did before the keys existed; the tuning keys without ``edit_mask_auto``, and ``edit_mask_auto`` with ``edit_mask_path``, are refused."""
-    import math
-    vals = {k: _option(config, "edit_mask_auto_" + k) for k in AUTO_MASK_DEFAULTS}
-    if not _auto_mask_on(config):
-        given = [k for k, v in vals.items() if v is not None]
-        if given:
-            raise ValueError(f"edit_mask_auto_{given[0]} without edit_mask_auto: there is no automatic mask to tune")
-        return None
-    if _option(config, "edit_mask_path") is not None:
-        raise ValueError("edit_mask_auto together with edit_mask_path: the mask is either generated or loaded")
-    if _first_frame_mask_on(config):
-        raise ValueError("edit_mask_first_frame together with edit_mask_auto: the mask is either derived from the first frames or generated")
-    maps = AUTO_MASK_DEFAULTS["maps"] if vals["maps"] is None else vals["maps"]
-    if isinstance(maps, bool) or not isinstance(maps, (int, float)) or not 1 <= maps < 2 ** 31 or int(maps) != maps:   # (refuses NaN)
-        raise ValueError(f"edit_mask_auto_maps={maps}: an integer >= 1")
-    num = {k: float(AUTO_MASK_DEFAULTS[k] if vals[k] is None else vals[k]) for k in ("strength", "ratio", "threshold")}
-    if not 0.0 < num["strength"] <= 1.0:
-        raise ValueError(f"edit_mask_auto_strength={num['strength']}: 0 < edit_mask_auto_strength <= 1")
-    if not (num["ratio"] > 0.0 and math.isfinite(num["ratio"])):
-        raise ValueError(f"edit_mask_auto_ratio={num['ratio']}: finite and > 0")
-    if not 0.0 < num["threshold"] < 1.0:
-        raise ValueError(f"edit_mask_auto_threshold={num['threshold']}: 0 < edit_mask_auto_threshold < 1")
-    grow, feather = _grow_feather(_option(config, "edit_mask_grow"), _option(config, "edit_mask_feather"))
-    return dict(maps=int(maps), grow=grow, feather=feather, **num)
-
-
-COMPOSITE_DEFAULTS = dict(grow_px=0, feather_px=0.0, match_color=False)   # ``I2VGenXLPipeline.composite_over_source``'s
+    """-> dict(maps, strength, ratio, threshold, grow, feather) for ``I2VGenXLPipeline.generate_edit_mask``: ``edit_mask_auto`` (bool) switches
+    the automatic mask on, ``edit_mask_auto_maps`` (noise draws, integer >= 1), ``edit_mask_auto_strength`` (0 < s <= 1: how far the source is
+    noised), ``edit_mask_auto_ratio`` (> 0) and ``edit_mask_auto_threshold`` (in (0, 1)) tune it; ``edit_mask_grow`` / ``edit_mask_feather``
+    shape the generated mask like a loaded one.  Refused together with another source of the mask."""
+    plan = plan_from_config(config)
+    return None if plan is None or plan.auto is None else dict(plan.auto, grow=plan.grow, feather=plan.feather)
 
 
 def composite_options(config):
-    """The pixel-space composite of a masked PnP-edit configuration (``I2VGenXLPipeline.composite_over_source``), or None: OPTIONAL keys the
-    reference's files do not have -- ``edit_mask_composite`` (bool) switches it on, ``edit_mask_composite_grow`` (pixels, integer 0 .. 64),
-    ``edit_mask_composite_feather`` (sigma in pixels, 0 .. 16) and ``edit_mask_match_color`` (bool) shape it.
-    -> dict(grow_px, feather_px, match_color).  Absent, null or false: None, and the entry runs and writes exactly what it did before the
-    keys existed; the shaping keys without ``edit_mask_composite``, and ``edit_mask_composite`` without a mask (``edit_mask_path`` or
-    ``edit_mask_auto``), are refused, not dropped."""
-    on, match = _option(config, "edit_mask_composite"), _option(config, "edit_mask_match_color")
-    for key, v in (("edit_mask_composite", on), ("edit_mask_match_color", match)):
-        if v is not None and not isinstance(v, bool):
-            raise ValueError(f"{key}={v!r}: true or false")
-    grow, feather = _option(config, "edit_mask_composite_grow"), _option(config, "edit_mask_composite_feather")
-    if not on:
-        for key, v in (("edit_mask_composite_grow", grow), ("edit_mask_composite_feather", feather), ("edit_mask_match_color", match)):
-            if v is not None:
-                raise ValueError(f"{key} without edit_mask_composite: there is no composite to shape")
-        return None
-    if _option(config, "edit_mask_path") is None and not _auto_mask_on(config) and not _first_frame_mask_on(config):
-        raise ValueError("edit_mask_composite without edit_mask_path or edit_mask_auto: there is no mask to composite by")
-    grow = 0 if grow is None else grow
-    feather = 0.0 if feather is None else float(feather)
-    if isinstance(grow, bool) or not isinstance(grow, (int, float)) or not 0 <= grow <= 64 or int(grow) != grow:   # (also refuses NaN)
-        raise ValueError(f"edit_mask_composite_grow={grow}: an integer, 0 <= edit_mask_composite_grow <= 64")
-    if not 0.0 <= feather <= 16.0:   # (also refuses NaN)
-        raise ValueError(f"edit_mask_composite_feather={feather}: 0 <= edit_mask_composite_feather <= 16")
-    return dict(grow_px=int(grow), feather_px=feather, match_color=bool(match))
+    """-> dict(grow_px, feather_px, match_color) for ``I2VGenXLPipeline.composite_over_source``: ``edit_mask_composite`` (bool) switches the
+    pixel-space composite on, ``edit_mask_composite_grow`` (pixels, integer 0 .. 64), ``edit_mask_composite_feather`` (sigma in pixels,
+    0 .. 16) and ``edit_mask_match_color`` (bool) shape it.  Refused without a mask (``edit_mask_path``, ``_auto`` or ``_first_frame``)."""
+    plan = plan_from_config(config)
+    return None if plan is None or plan.composite is None else dict(plan.composite)
 
 
 def _rebind(cfg: Config, root: Config):

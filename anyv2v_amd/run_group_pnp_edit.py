@@ -19,9 +19,9 @@ from pathlib import Path
 import torch
 from PIL import Image
 
-from .config import (AUTO_MASK_DEFAULTS, FIRST_FRAME_MASK_DEFAULTS, TRACK_DEFAULTS, OmegaConf, auto_mask_options, composite_options,
-                     first_frame_mask_options, masked_edit_options, sampler_options, track_options)
+from .config import OmegaConf, sampler_options
 from .encoders import attach_synthetic_encoders
+from .masked_edit import finish_frames, make_edit_mask, masked, plan_from_config
 from .parallel import FrameParallel, gather_latents, init_distributed, seed_for_entry, shard_entries
 from .pipeline import I2VGenXLPipeline
 from .pnp_utils import clear_time, register_conv_injection, register_spatial_attention_pnp, register_temp_attention_pnp
@@ -51,24 +51,8 @@ def output_suffix(config, ddim_init_latents_t_idx) -> str:
     """``run_group_pnp_edit.py:154-167``; the optional sampler keys (``config.sampler_options``) add to the name only when they are on,
     so two entries that differ in them alone do not overwrite each other and every other directory keeps the reference's name."""
     eta, rescale = sampler_options(config)
-    masked = masked_edit_options(config)   # optional keys ``edit_mask_*``: a masked and an unmasked edit do not overwrite each other
-    track = track_options(config)          # optional keys ``edit_mask_track*``: the one-frame mask carried through the clip
-    track_tag = "" if track is None else ("-track" + (f"_radius{track['radius']}" if track["radius"] != TRACK_DEFAULTS["radius"] else "")
-                                          + ("" if track["median"] else "_nomedian"))
-    mask_tag = "" if masked is None else ("_mask-" + os.path.splitext(os.path.basename(os.path.normpath(masked[0])))[0] + track_tag
-                                          + (f"_grow{masked[1]}" if masked[1] > 0 else "") + (f"_feather{masked[2]}" if masked[2] > 0 else ""))
-    ff = first_frame_mask_options(config)  # optional keys ``edit_mask_first_frame*``: the parameters where they are not the defaults
-    if ff is not None:
-        mask_tag = ("_mask-ff" + "".join(f"_{k}{ff[k]}" for k in FIRST_FRAME_MASK_DEFAULTS if ff[k] != FIRST_FRAME_MASK_DEFAULTS[k]) + track_tag
-                    + (f"_grow{ff['grow']}" if ff["grow"] > 0 else "") + (f"_feather{ff['feather']}" if ff["feather"] > 0 else ""))
-    auto = auto_mask_options(config)       # optional keys ``edit_mask_auto*``: the generated mask's parameters, where they are not the defaults
-    if auto is not None:
-        mask_tag = ("_mask-auto" + "".join(f"_{k}{auto[k]}" for k in AUTO_MASK_DEFAULTS if auto[k] != AUTO_MASK_DEFAULTS[k])
-                    + (f"_grow{auto['grow']}" if auto["grow"] > 0 else "") + (f"_feather{auto['feather']}" if auto["feather"] > 0 else ""))
-    comp = composite_options(config)       # optional keys ``edit_mask_composite*``: the tag only when on, parameters only where not the defaults
-    if comp is not None:
-        mask_tag += ("_comp" + (f"_grow{comp['grow_px']}" if comp["grow_px"] > 0 else "")
-                     + (f"_feather{comp['feather_px']}" if comp["feather_px"] > 0 else "") + ("_match" if comp["match_color"] else ""))
+    plan = plan_from_config(config)   # optional keys ``edit_mask_*``: a masked and an unmasked edit do not overwrite each other
+    mask_tag = "" if plan is None else plan.tag()
     return ("ddim_init_latents_t_idx_" + str(ddim_init_latents_t_idx) + "_nsteps_" + str(config.n_steps) + "_cfg_"
             + str(config.cfg) + "_pnpf" + str(config.pnp_f_t) + "_pnps" + str(config.pnp_spatial_attn_t) + "_pnpt"
             + str(config.pnp_temp_attn_t) + (f"_eta{eta}" if eta > 0 else "") + (f"_rescale{rescale}" if rescale > 0 else "") + mask_tag)
@@ -167,50 +151,36 @@ class Stage2:
                     config.ddim_latents_path, device=device, timesteps=[int(t) for t in ddim_scheduler.timesteps[t_idx:]])
             traj = loaded_trajectories[tkey]
         ddim_latents_at_t = load_ddim_latents_at_t(ddim_scheduler.timesteps[t_idx], traj)
-        # masked edit (optional keys ``edit_mask_path`` / ``_grow`` / ``_feather``): the mask at the frames' size and the clean latent of the
-        # source frames loaded above -- the partner of the last step, which the trajectory does not hold.  Encoded under the template's
+        # masked edit (optional keys ``edit_mask_*``, ``masked_edit.plan_from_config``): the mask at the frames' size and the clean latent of
+        # the source frames loaded above -- the partner of the last step, which the trajectory does not hold.  Encoded under the template's
         # seed BEFORE the entry is seeded below, so the draws of the edit itself are the ones of an unmasked entry.
-        masked = masked_edit_options(config)
-        auto = auto_mask_options(config)
-        ff = first_frame_mask_options(config)
-        track = track_options(config)
-        comp = composite_options(config)   # (refuses the composite keys of an entry without a mask before anything runs)
-        if masked is not None:
-            if track is not None and os.path.isdir(os.path.join(config.data_dir, masked[0])):
-                raise ValueError(f"edit_mask_track with a directory of masks ({masked[0]}): every frame already has its mask")
-            mask = load_edit_mask(os.path.join(config.data_dir, masked[0]), config.n_frames, tuple(config.image_size))
+        plan = plan_from_config(config)   # (refuses keys that have nothing to act on before anything runs)
+        mask = source_latents = None
+        if plan is not None:
+            loaded = None
+            if plan.source == "path":
+                if plan.track is not None and os.path.isdir(os.path.join(config.data_dir, plan.path)):
+                    raise ValueError(f"edit_mask_track with a directory of masks ({plan.path}): every frame already has its mask")
+                loaded = load_edit_mask(os.path.join(config.data_dir, plan.path), config.n_frames, tuple(config.image_size))
             seed_everything(template_config.seed)
             source_latents = pipe.encode_vae_video(frame_list, device=pipe._execution_device, height=config.image_size[1],
                                                    width=config.image_size[0])
-        elif auto is not None:
-            # automatic mask (optional keys ``edit_mask_auto*``): generated here, under the template's seed like the encode above, from the
-            # trajectory when ``run_group_anyv2v`` handed it over in HBM (deterministic, one map), else from noise draws on the clean
-            # latents.  The hooks of the previous entry are inert while it runs; ``init_pnp`` below registers this entry's.
-            seed_everything(template_config.seed)
-            source_latents = pipe.encode_vae_video(frame_list, device=pipe._execution_device, height=config.image_size[1],
-                                                   width=config.image_size[0])
-            clear_time(pipe)
-            pipe.register_modules(scheduler=ddim_scheduler)
-            pipe.auto_vae_tiling(config.image_size[1], config.image_size[0])
-            src = dict(ddim_inv_latents_path=traj) if handed is not None else dict(source_latents=source_latents)
-            mask = pipe.generate_edit_mask(
-                prompt=config.editing_prompt, image=edited_1st_frame, ddim_inv_prompt=config.ddim_inv_prompt, ddim_inv_1st_frame=src_1st_frame,
-                height=config.image_size[1], width=config.image_size[0], num_frames=config.n_frames, target_fps=config.target_fps,
-                num_inference_steps=config.n_steps, num_maps_per_mask=auto["maps"], mask_encode_strength=auto["strength"],
-                mask_thresholding_ratio=auto["ratio"], threshold=auto["threshold"], generator=torch.manual_seed(template_config.seed), **src)
-            masked = (None, auto["grow"], auto["feather"])
-        elif ff is not None:
-            # first-frame mask (optional keys ``edit_mask_first_frame*``): where the edited first frame differs from the source's; no model,
-            # no draw.  The clean latent is encoded under the template's seed like the ones above.
-            seed_everything(template_config.seed)
-            source_latents = pipe.encode_vae_video(frame_list, device=pipe._execution_device, height=config.image_size[1],
-                                                   width=config.image_size[0])
-            mask = pipe.first_frame_edit_mask(src_1st_frame, edited_1st_frame, threshold=ff["threshold"], min_count=ff["min_count"])
-            masked = (None, ff["grow"], ff["feather"])
-        if track is not None:
-            # tracking (optional keys ``edit_mask_track*``): the one-frame mask, derived or loaded, carried along the source frames' motion
-            # (a loaded PNG: every non-black pixel is carried as "edit" -- a grey level has no position to follow)
-            mask = pipe.propagate_edit_mask(frame_list, mask, radius=track["radius"], median=track["median"])
+
+            def generate(auto):
+                # automatic mask: under the template's seed like the encode above, from the trajectory when ``run_group_anyv2v`` handed it
+                # over in HBM (deterministic, one map), else from noise draws on the clean latents.  The hooks of the previous entry are
+                # inert while it runs; ``init_pnp`` below registers this entry's.
+                clear_time(pipe)
+                pipe.register_modules(scheduler=ddim_scheduler)
+                pipe.auto_vae_tiling(config.image_size[1], config.image_size[0])
+                src = dict(ddim_inv_latents_path=traj) if handed is not None else dict(source_latents=source_latents)
+                return pipe.generate_edit_mask(
+                    prompt=config.editing_prompt, image=edited_1st_frame, ddim_inv_prompt=config.ddim_inv_prompt, ddim_inv_1st_frame=src_1st_frame,
+                    height=config.image_size[1], width=config.image_size[0], num_frames=config.n_frames, target_fps=config.target_fps,
+                    num_inference_steps=config.n_steps, num_maps_per_mask=auto["maps"], mask_encode_strength=auto["strength"],
+                    mask_thresholding_ratio=auto["ratio"], threshold=auto["threshold"], generator=torch.manual_seed(template_config.seed), **src)
+            mask = make_edit_mask(pipe, plan, loaded=loaded, generate=generate, source_first_frame=src_1st_frame,
+                                  edited_first_frame=edited_1st_frame, source_frames=frame_list)
         seed_everything(seed_for_entry(template_config.seed, entry_idx) if self.e_world > 1 else template_config.seed)
         random_latents = torch.randn(ddim_latents_at_t.shape, dtype=torch.float32).to(ddim_latents_at_t)  # drawn even if unused (:124)
         logger.info(f"Blending random_ratio (1 means random latent): {config.random_ratio}")
@@ -221,9 +191,7 @@ class Stage2:
         pipe.auto_vae_tiling(config.image_size[1], config.image_size[0])
         eta, rescale = sampler_options(config)   # optional keys ``eta`` / ``guidance_rescale``; absent: (0, 0), the default engines
         pipe.enable_guidance_rescale(rescale)
-        if masked is not None:
-            pipe.enable_masked_edit(mask, source_latents, grow=masked[1], feather=masked[2])   # (refuses a frame-parallel clip)
-        try:
+        with masked(pipe, plan, mask, source_latents):
             edited_latents = pipe.sample_with_pnp(
                 prompt=config.editing_prompt, image=edited_1st_frame, height=config.image_size[1], width=config.image_size[0],
                 num_frames=config.n_frames, num_inference_steps=config.n_steps, guidance_scale=config.cfg,
@@ -231,8 +199,6 @@ class Stage2:
                 generator=torch.manual_seed(config.seed), return_dict=True, ddim_init_latents_t_idx=t_idx,
                 ddim_inv_latents_path=traj, ddim_inv_prompt=config.ddim_inv_prompt, ddim_inv_1st_frame=src_1st_frame,
                 output_type="latent").frames
-        finally:
-            pipe.disable_masked_edit()   # the mask belongs to this entry's clip, not to the pipeline
         self.my_latents[entry_idx] = edited_latents
         self.lat_shape = tuple(edited_latents.shape)
         rng = _RngState(device)
@@ -241,13 +207,8 @@ class Stage2:
         video = pipe.decode_latents(edited_latents, decode_chunk_size=1)  # (frame-parallel: every rank decodes its frames)
         if not self.writer:
             return
-        if comp is not None:
-            # pixel-space composite (optional keys ``edit_mask_composite*``): outside the entry's mask the files carry the source frames'
-            # bytes, not decode(encode(source)); inside, the bytes ``to_pil`` forms -- one pass over the decode's output on the device
-            frames_u8 = pipe.composite_over_source(video, frame_list, mask, grow=masked[1], feather=masked[2], **comp)
-            edited_video = [Image.fromarray(fr) for fr in frames_u8.cpu().numpy()]
-        else:
-            edited_video = pipe.vae.to_pil(video)
+        # (optional keys ``edit_mask_composite*``: one pass over the decode's output on the device; off: the reference's ``to_pil``)
+        edited_video = finish_frames(pipe, plan, video, frame_list, mask) or pipe.vae.to_pil(video)
 
         output_dir = os.path.join(config.output_dir, output_suffix(config, t_idx))
         os.makedirs(output_dir, exist_ok=True)
@@ -259,7 +220,7 @@ class Stage2:
         logger.info(f"Saved gif to: {os.path.join(output_dir, f'{name}.gif')}")
         for i, frame in enumerate(edited_video):
             frame.save(os.path.join(output_dir, f"{name}_{i:05d}.png"))
-        if auto is not None or ff is not None or track is not None:   # the mask made here, one frame per file in the format ``load_edit_mask`` reads (white = edited)
+        if plan is not None and (plan.source != "path" or plan.track is not None):   # the mask made here, one frame per file in the format ``load_edit_mask`` reads (white = edited)
             for i, plane in enumerate((mask.to(torch.uint8) * 255).cpu().numpy()):
                 Image.fromarray(plane, mode="L").save(os.path.join(output_dir, f"mask_{i:05d}.png"))
         torch.save(edited_latents.cpu(), os.path.join(output_dir, "edited_latents.pt"))
