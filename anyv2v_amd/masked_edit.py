@@ -2,7 +2,7 @@
 keys mean (``plan_from_config`` -> ``MaskedEditPlan``), the pipeline methods that make, shape and apply a mask (``MaskedEditMixin``,
 inherited by ``I2VGenXLPipeline``) and the three steps both runners take around ``sample_with_pnp`` (``make_edit_mask``, ``masked``,
 ``finish_frames``).  The kernels are ``csrc/mask.hip``, ``automask.hip``, ``composite.hip`` and ``track.hip`` behind ``ops``; the blend
-itself runs inside the step engines of ``pipeline.py``."""
+itself runs inside the step engines of ``step_engine.py``."""
 from __future__ import annotations
 
 import contextlib

@@ -16,15 +16,18 @@ from __future__ import annotations
 
 import logging
 import os
+from contextlib import nullcontext
+from types import SimpleNamespace
 from typing import Dict, Optional, Union
 
 import torch
 
-from . import ops, pnp_utils
+from . import pnp_utils
 from .masked_edit import MaskedEditMixin, edit_mask_timestep  # noqa: F401  (``edit_mask_timestep`` stays importable from here)
 from .schedulers import DDIMScheduler
+from .step_engine import SourceFeatureCache, _StepEngine, _use_graphs, cached_engine, pnp_step_plan  # noqa: F401  (re-exported)
 from .unet import I2VGenXLUNet, I2VGenXLUNetConfig
-from .utils import LatentTrajectory, capture_hip_graph, load_ddim_latents_at_t, release_graphs
+from .utils import LatentTrajectory, load_ddim_latents_at_t
 
 logger = logging.getLogger(__name__)
 
@@ -37,215 +40,6 @@ class I2VGenXLPipelineOutput:
 class StableVideoDiffusionInversionPipelineOutput:
     def __init__(self, inverted_latents):
         self.inverted_latents = inverted_latents
-
-
-def _use_graphs() -> bool:
-    return os.environ.get("ANYV2V_NO_GRAPH", "0") != "1"
-
-
-class SourceFeatureCache:
-    """Job-level exact saving for several edits of ONE clip (``configs/group_pnp_edit/group_config.json`` holds 8 edits of one
-    clip): the source branch of ``sample_with_pnp`` is only a feature generator -- its v-prediction is discarded
-    (``pipeline_i2vgen_xl.py:1136,1160-1162``) and it depends on the clip, its inversion and the step, not on the edit.  The first
-    edit runs the three-branch steps and RECORDS, per step and injected hook site, what the other branches read from the source
-    branch (Q | K of the 16 attention sites, the conv features of ``up_blocks[1].resnets[1]``); every further edit of the same
-    clip REPLAYS them and runs [negative, editing] only.  Kept in HBM (~0.85 GB per fully injected step at 16 f x 512^2).
-
-    ``signature``: what the recorded features depend on; a different one (next clip, other weights) empties the cache."""
-
-    def __init__(self, max_bytes: Optional[int] = None):
-        self.signature = None
-        self.steps: Dict[tuple, Dict[str, torch.Tensor]] = {}   # (t, injection state) -> site -> features
-        self.recorded_steps = self.replayed_steps = 0
-        # byte budget (``ANYV2V_SOURCE_CACHE_GB``, default 96 GB of the 288): a step that would exceed it is simply not recorded and
-        # runs as a three-branch step in every edit -- same results, no saving for that step
-        self.max_bytes = int(float(os.environ.get("ANYV2V_SOURCE_CACHE_GB", "96")) * 2 ** 30) if max_bytes is None else int(max_bytes)
-        self.skipped_steps = 0
-
-    def store(self, t, state, feats: Dict[str, torch.Tensor]) -> bool:
-        need = sum(v.numel() * v.element_size() for v in feats.values())
-        if self.nbytes() + need > self.max_bytes:
-            self.skipped_steps += 1
-            return False
-        self.steps[(int(t), tuple(state))] = {n: v.clone() for n, v in feats.items()}
-        return True
-
-    def bind(self, signature):
-        if signature != self.signature:
-            self.steps.clear()
-            self.signature = signature
-
-    def has(self, t, state) -> bool:
-        """Features of step ``t`` recorded under exactly this injection ``state`` (which sites are on).  The same state, not a
-        superset: the source branch's own arithmetic depends on it at the rounding level (on a conv-injection step its main path
-        runs as a one-branch launch with its own split-K plan, at an injected attention site its Q | K | V come from a one-branch
-        projection), so only a same-state record reproduces the uncached edit bit for bit."""
-        return (int(t), tuple(state)) in self.steps
-
-    def nbytes(self) -> int:
-        return sum(v.numel() * v.element_size() for d in self.steps.values() for v in d.values())
-
-
-class _StepEngine:
-    """One denoising step = UNet forward on ``sample[B,4,F,h,w]`` + fused CFG/DDIM update of the latent slot.
-
-    ``sample`` is a static buffer: slot ``lat_slot`` (the last one) IS the latent being denoised and is updated in
-    place; ``dup_slots`` are re-filled from it after the update (CFG feeds the same latent twice); slot 0 of a PnP
-    step is overwritten by the caller with the source trajectory before each step.
-    """
-
-    def __init__(self, pipe, sample, cond, b_unc, b_cond, guidance, dup_slots, shared_stem=False, batch_hint=None, lat_slots=None,
-                 stochastic=False, rescale=0.0, blend=None):
-        self.pipe, self.unet = pipe, pipe.unet
-        # masked edit (``enable_masked_edit``): static buffers (partner latent [1, 4, F, h, w], latent mask [Fm, h, w]) the captured step
-        # blends the latent slot against, behind the update.  The caller owns them -- the three-branch engine and its [negative, editing]
-        # twins step the SAME latent and share one pair -- and refills the partner before every step.  None: nothing is launched
-        self.blend = None if blend is None else tuple(blend)
-        assert not (self.blend is not None and lat_slots is not None), "the batched inversion has no masked edit"
-        # sampler options (``_SamplerOptions``): with either one on, the step is ``ops.cfg_ddim_step_ex`` on an 8-float coefficient row
-        # (+ ``ops.guidance_stats`` in front of it under the rescale); with both off, nothing below differs from the default engine
-        self.stochastic, self.rescale = bool(stochastic), float(rescale)
-        self.options = self.stochastic or self.rescale > 0.0
-        assert not (self.options and lat_slots is not None), "the batched inversion has no sampler options"
-        # (num, den): this engine runs a subset of another engine's branches ([negative, editing] of a three-branch edit step) and
-        # must make the same launch choices -- ops.batch_hint
-        self.batch_hint = batch_hint
-        self.sample = sample
-        self.cond = cond
-        self.b_unc, self.b_cond, self.guidance = b_unc, b_cond, float(guidance)
-        self.lat_slot = sample.shape[0] - 1
-        # several clips inverted in one batch (``invert_clips``): every slot is a latent of its own, stepped without guidance
-        self.lat_slots = None if lat_slots is None else list(lat_slots)
-        self.dup_slots = list(dup_slots)
-        self.coef = torch.zeros(8 if self.options else 4, dtype=torch.float32, device=sample.device)
-        # static operands of the captured step: the variance noise of THIS step (copied in before every replay -- drawn outside the
-        # graph, from the caller's generator) and the records of the rescale statistics
-        self.noise = torch.zeros_like(sample[:1]) if self.stochastic else None
-        self.gstats = (torch.zeros(ops.GUIDANCE_STATS_FLOATS, dtype=torch.float32, device=sample.device)
-                       if self.rescale > 0.0 and b_unc >= 0 else None)   # (no guidance, no rescale: pipeline_video_editing.py:685)
-        self.graphs: Dict[tuple, torch.cuda.CUDAGraph] = {}
-        # (a frame-parallel forward contains collectives: run eagerly -- at 128 frames launch overhead is irrelevant)
-        # (likewise with foreign hooks on the seams B1 / B2: torch-style code that may sync, e.g. ``t in cuda_tensor``)
-        self.use_graphs = (_use_graphs() and sample.is_cuda and getattr(pipe.unet, "frame_parallel", None) is None
-                           and not pnp_utils.has_foreign_hooks(pipe.unet))
-        B, _, F, H, W = sample.shape
-        unet = self.unet
-        if not unet._packed:
-            unet.pack()
-        with ops.batch_hint(*(batch_hint or (1, 1))):
-            self.ctx = unet._prepare_clip(B, F, H, W, cond["encoder_hidden_states"], cond["fps"], cond["image_latents"],
-                                          cond["image_embeddings"])
-        # CFG batches [.., negative, positive]: the last two slots hold the same latent (dup_slots) and -- checked here,
-        # once -- the same image latents and fps, so the UNet may share their stem (exact; unet._forward_core)
-        self._shared_stem_requested = bool(shared_stem)
-        self.nosrc = None  # the [negative, editing]-only engine of a PnP edit (shares `sample[1:]`), built on demand
-        self.drop_src_tail = False  # set by sample_with_pnp on its three-branch engine
-        self.ctx.shared_stem = bool(shared_stem and B >= 2 and os.environ.get("ANYV2V_SHARED_STEM", "1") == "1"
-                                    and torch.equal(cond["image_latents"][B - 2], cond["image_latents"][B - 1])
-                                    and torch.equal(cond["fps"][B - 2], cond["fps"][B - 1]))
-
-    def rebind(self, sample_init, cond) -> bool:
-        """Point this engine (its static buffers and captured graphs) at another clip of the same geometry: the new latents go
-        into ``self.sample``, the new clip's step-invariant tensors are computed by ``_prepare_clip`` and copied INTO the
-        context tensors the graphs were captured on.  False if the clip cannot run on this engine (different shared-stem
-        decision): the caller then builds a fresh one."""
-        B, _, F, H, W = self.sample.shape
-        shared = bool(self._shared_stem_requested and B >= 2 and os.environ.get("ANYV2V_SHARED_STEM", "1") == "1"
-                      and torch.equal(cond["image_latents"][B - 2], cond["image_latents"][B - 1])
-                      and torch.equal(cond["fps"][B - 2], cond["fps"][B - 1]))
-        if shared != self.ctx.shared_stem:
-            return False
-        if sample_init.data_ptr() != self.sample.data_ptr():
-            self.sample.copy_(sample_init)
-        with ops.batch_hint(*(self.batch_hint or (1, 1))):
-            fresh = self.unet._prepare_clip(B, F, H, W, cond["encoder_hidden_states"], cond["fps"], cond["image_latents"],
-                                            cond["image_embeddings"])
-        if fresh is not self.ctx:
-            if (fresh.Sk, fresh.F) != (self.ctx.Sk, self.ctx.F):
-                return False
-            for name, new in vars(fresh).items():
-                old = getattr(self.ctx, name, None)
-                if torch.is_tensor(new) and name not in ("stats", "t_buf"):
-                    if not torch.is_tensor(old) or old.shape != new.shape or old.dtype != new.dtype:
-                        return False
-                    old.copy_(new)
-            self.ctx.key, self.ctx._keepalive = fresh.key, fresh._keepalive
-            self.unet._ctx = self.ctx
-        self.cond = cond
-        return True
-
-    def _body(self):
-        if self.batch_hint is not None:
-            self.ctx.batch_hint = self.batch_hint   # (the forward switches between the stem's and the full batch's ratio)
-            with ops.batch_hint(*self.batch_hint):
-                return self._body_inner()
-        return self._body_inner()
-
-    def _body_inner(self):
-        # drop_src_tail: the engine's slot 0 is the PnP source branch, whose prediction the update below never reads -- the forward
-        # stops computing it behind the last hook site and returns the rows of slots [1:] (unet._forward_core)
-        vtok = self.unet._forward_core(self.ctx, self.sample, drop_source_tail=self.drop_src_tail)
-        if self.lat_slots is not None:
-            for L in self.lat_slots:
-                lat = self.sample[L:L + 1]
-                ops.cfg_ddim_step(vtok, -1, L, 1.0, self.coef, lat, lat)
-            return
-        L = self.lat_slot
-        lat = self.sample[L:L + 1]
-        off = 1 if vtok.shape[0] != self.sample.shape[0] * self.sample.shape[2] * self.sample.shape[3] * self.sample.shape[4] else 0
-        b_unc, b_cond = self.b_unc - off if self.b_unc >= 0 else self.b_unc, self.b_cond - off
-        if self.options:
-            if self.gstats is not None:
-                ops.guidance_stats(vtok, b_unc, b_cond, self.guidance, lat.shape, out=self.gstats)
-            ops.cfg_ddim_step_ex(vtok, b_unc, b_cond, self.guidance, self.coef, lat, lat, prediction=self.pipe.scheduler.prediction,
-                                 stats=self.gstats, phi=self.rescale if self.gstats is not None else 0.0, noise=self.noise)
-        else:
-            ops.cfg_ddim_step(vtok, b_unc, b_cond, self.guidance, self.coef, lat, lat)
-        if self.blend is not None:
-            ops.masked_blend(lat, self.blend[0], self.blend[1], out=lat)   # in place, before the copies: every slot gets the blended latent
-        for s in self.dup_slots:
-            self.sample[s].copy_(self.sample[L])
-
-    def step(self, t_row: torch.Tensor, coef_row: torch.Tensor, key: tuple, noise: Optional[torch.Tensor] = None,
-             partner: Optional[torch.Tensor] = None):
-        """``noise``: this step's variance noise (a stochastic engine needs a fresh draw for every step).  ``partner``: the latent a
-        masked edit keeps outside the mask after THIS step (the source at the level the step arrives at)."""
-        with ops.workspace_slot(getattr(self.pipe, "ws_slot", 0)):
-            if partner is None:
-                self._step(t_row, coef_row, key, noise)   # (the call of an engine without a mask, as it always was)
-            else:
-                self._step(t_row, coef_row, key + ("blend",), noise, partner)   # (the graph of a masked step holds the blend launch)
-
-    def _step(self, t_row: torch.Tensor, coef_row: torch.Tensor, key: tuple, noise=None, partner=None):
-        self.ctx.t_buf.copy_(t_row, non_blocking=True)
-        self.coef.copy_(coef_row, non_blocking=True)
-        if getattr(self, "blend", None) is not None:
-            if partner is None:
-                raise ValueError("a masked step engine needs the step's partner latent: replaying the buffer would blend against the last step's")
-            self.blend[0].copy_(partner.reshape(self.blend[0].shape), non_blocking=True)
-        if self.stochastic:
-            if noise is None:
-                raise ValueError("a stochastic step engine needs the step's variance noise: replaying the buffer would repeat the last draw")
-            self.noise.copy_(noise.reshape(self.noise.shape), non_blocking=True)
-        if not self.use_graphs:
-            self._body()
-            return
-        g = self.graphs.get(key)
-        if g is None:
-            # warm up eagerly on the side (pure: the UNet forward does not touch the latents), then capture
-            if self.batch_hint is not None:
-                self.ctx.batch_hint = self.batch_hint
-                with ops.batch_hint(*self.batch_hint):
-                    self.unet._forward_core(self.ctx, self.sample)
-            else:
-                self.unet._forward_core(self.ctx, self.sample, drop_source_tail=self.drop_src_tail)
-            torch.cuda.synchronize()
-            g = torch.cuda.CUDAGraph()
-            with capture_hip_graph(g):
-                self._body()
-            self.graphs[key] = g
-            # capture does not execute: fall through to the replay below
-        g.replay()
 
 
 def _vae_config(root):
@@ -626,45 +420,58 @@ class I2VGenXLPipeline(MaskedEditMixin):
         self.source_cache = SourceFeatureCache() if on else None
         return self.source_cache
 
-    def _engine(self, tag, sample, cond, **kw) -> _StepEngine:
-        """A step engine for this loop: a new one, or -- for the next clip of the same geometry in a multi-clip job -- the one
-        captured for the previous clip, re-pointed at the new clip (``_StepEngine.rebind``): graph capture and its warm-up
-        forward (~0.25 s per 16 x 512^2 clip) are paid once per process instead of once per clip.  ANYV2V_ENGINE_CACHE=0
-        switches it off."""
-        if os.environ.get("ANYV2V_ENGINE_CACHE", "1") != "1" or getattr(self.unet, "frame_parallel", None) is not None:
-            return _StepEngine(self, sample, cond, **kw)
-        if not self.unet._packed:
-            self.unet.pack()  # (weights loaded / moved since the last call: new packed tensors, engines of the old ones are stale)
-        key = (tag, self.unet._pack_gen, tuple(sample.shape), str(sample.device), tuple(cond["encoder_hidden_states"].shape), kw.get("b_unc"),
-               kw.get("b_cond"), float(kw.get("guidance")), tuple(kw.get("dup_slots")), bool(kw.get("shared_stem", False)),
-               _use_graphs(), pnp_utils.has_foreign_hooks(self.unet), id(self.unet), kw.get("lat_slots"),
-               getattr(self.unet, "freeu", None))   # (a captured graph holds the FreeU launches of the setting it was captured under)
-        if kw.get("stochastic") or kw.get("rescale"):
-            # ... and the launches of its sampler options; with both off the key is the default engine's, unchanged
-            key += (("sampler", bool(kw.get("stochastic")), float(kw.get("rescale") or 0.0)),)
-        if kw.get("blend") is not None:
-            # ... and the blend launch of a masked edit, on buffers of this mask geometry; without a mask the key is unchanged
-            key += (("blend", tuple(kw["blend"][1].shape)),)
-        eng = self._engines.pop(key, None)
-        if eng is None or not eng.rebind(sample, cond):
-            eng = _StepEngine(self, sample, cond, **kw)
-        # Every engine pins a private graph pool holding a whole forward's activations (and a nested one for the source-free
-        # steps), so the cache is small and evicts eagerly: one engine per loop kind (a new guidance value or geometry replaces
-        # the old engine of that loop -- a slider in a long-lived front-end must not accumulate pools), at most
-        # ANYV2V_ENGINE_CACHE_MAX (3 = inversion + CFG + PnP) overall; an evicted engine drops its graphs and returns the memory.
-        evict = [k for k in self._engines if k[0] == tag]
-        self._engines[key] = eng  # most recently used last
-        limit = max(1, int(os.environ.get("ANYV2V_ENGINE_CACHE_MAX", "3")))
-        evict += [k for k in list(self._engines)[: max(0, len(self._engines) - len(evict) - limit)] if k not in evict]
-        for k in evict:
-            old = self._engines.pop(k)
-            release_graphs(old.graphs)   # (parked, not destroyed, while another engine / thread is capturing: utils.release_graphs)
-            if old.nosrc is not None:
-                release_graphs(old.nosrc.graphs)
-                old.nosrc = None
-        if evict and sample.is_cuda:
-            torch.cuda.empty_cache()
-        return eng
+    def _step_tables(self, ts, nb, **coef_kw):
+        """What the loops share.  -> (timestep rows [n, nb], DDIM coefficient rows [n, 4 or 8]) on the device: a step copies row i, no host sync."""
+        t_table = torch.tensor(ts, dtype=torch.float32, device=self._execution_device)[:, None].expand(-1, nb).contiguous()
+        return t_table, self.scheduler.coefficient_table(ts, self._execution_device, **coef_kw)
+
+    def _loop_setup(self, kind, prompt, image, height, width, target_fps, num_frames, num_inference_steps, guidance_scale, negative_prompt,
+                    eta, num_videos_per_prompt, generator, latents, prompt_embeds, negative_prompt_embeds, cross_attention_kwargs, clip_skip,
+                    image_embeddings, image_latents, t_idx=None, source=None):
+        """``invert`` ("inv"), ``__call__`` ("cfg") and ``sample_with_pnp`` ("pnp") in front of the step engine: input checks, conditioning,
+        the branch batch -- [negative, positive] under classifier-free guidance (:1329-1337; zero negative image embedding, :437-439), the
+        source branch (``source``: the ``ddim_inv_*`` arguments) in front of it in a PnP edit (:1044,1093-1094) --, the timesteps from
+        ``t_idx`` on (:813,1105; the inversion runs them all and takes no sampler options), latents, step tables, engine keywords."""
+        height = height or self.unet.config.sample_size * self.vae_scale_factor
+        width = width or self.unet.config.sample_size * self.vae_scale_factor
+        self.check_inputs(prompt, image, height, width, negative_prompt, prompt_embeds, negative_prompt_embeds)
+        if kind != "pnp":
+            self._refuse_masked_edit("invert" if kind == "inv" else "__call__")
+        elif isinstance(prompt, list):
+            assert len(source[0]) == len(prompt)  # :1000
+        device = self._execution_device
+        self._guidance_scale = guidance_scale
+        pe, npe, ie, il = self._conditioning(prompt, image, height, width, num_frames, negative_prompt, prompt_embeds,
+                                             negative_prompt_embeds, target_fps, clip_skip, image_embeddings, image_latents)
+        self._single_clip(pe, num_videos_per_prompt)
+        stochastic, eta, phi = self._sampler_options(eta, cross_attention_kwargs) if kind != "inv" else (False, 0.0, 0.0)
+        opts = dict(stochastic=stochastic, rescale=phi) if (stochastic or phi > 0.0) else {}
+        cfg_on = bool(self.do_classifier_free_guidance)
+        branches, source_cond = [(pe, ie, il)], None
+        if cfg_on:
+            branches.insert(0, (npe, torch.zeros_like(ie), il))
+        if kind == "pnp":
+            source_cond = self._source_conditioning(source[0], source[1], height, width, num_frames, clip_skip, *source[2:])
+            branches.insert(0, source_cond)
+        else:
+            pnp_utils.clear_time(self)  # inversion (stage 1 of the reference) and plain CFG sampling (DDIM reconstruction) run hook-free
+        ehs, ie_all, il_all = (torch.cat(x) if len(x) > 1 else x[0] for x in zip(*branches))
+        nb = ehs.shape[0]
+        self.scheduler.set_timesteps(num_inference_steps, device=device)
+        if kind != "inv":
+            self.scheduler.timesteps = self.scheduler.timesteps[t_idx:]
+        ts = [int(t) for t in self.scheduler.timesteps.tolist()]
+        latents = self.prepare_latents(1, self.unet.config.in_channels, num_frames, height, width, torch.float16, device,
+                                       generator, latents).to(torch.float16)
+        sample = latents.repeat(nb, 1, 1, 1, 1).contiguous()
+        cond = dict(encoder_hidden_states=ehs.contiguous(), fps=torch.tensor([target_fps] * nb, device=device),
+                    image_latents=il_all.contiguous(), image_embeddings=ie_all.contiguous())
+        src = 1 if kind == "pnp" else 0   # slots in front of the CFG pair
+        engine_kw = dict(b_unc=src if cfg_on else -1, b_cond=nb - 1, guidance=guidance_scale, dup_slots=range(src, nb - 1),
+                         shared_stem=cfg_on and kind != "inv", **opts)
+        t_table, coef_table = self._step_tables(ts, nb, **(dict(eta=eta, phi=phi, n=latents.numel()) if opts else {}))
+        return SimpleNamespace(nb=nb, ts=ts, sample=sample, cond=cond, t_table=t_table, coef_table=coef_table, engine_kw=engine_kw,
+                               latents=latents, height=height, width=width, cfg_on=cfg_on, stochastic=stochastic, source_cond=source_cond)
 
     # ------------------------------------------------------------------ A1: DDIM inversion (:1197-1451)
     @torch.no_grad()
@@ -676,43 +483,17 @@ class I2VGenXLPipeline(MaskedEditMixin):
                return_dict: bool = True, cross_attention_kwargs=None, clip_skip: Optional[int] = 1,
                output_dir: Optional[str] = None, image_embeddings=None, image_latents=None,
                return_trajectory: bool = False, background_save: bool = False):
-        height = height or self.unet.config.sample_size * self.vae_scale_factor
-        width = width or self.unet.config.sample_size * self.vae_scale_factor
-        self.check_inputs(prompt, image, height, width, negative_prompt, prompt_embeds, negative_prompt_embeds)
-        self._refuse_masked_edit("invert")
-        device = self._execution_device
-        self._guidance_scale = guidance_scale
-        pnp_utils.clear_time(self)  # inversion never injects (stage 1 of the reference runs without hooks)
-        pe, npe, ie, il = self._conditioning(prompt, image, height, width, num_frames, negative_prompt, prompt_embeds,
-                                             negative_prompt_embeds, target_fps, clip_skip, image_embeddings, image_latents)
-        self._single_clip(pe, num_videos_per_prompt)
-        cfg_on = self.do_classifier_free_guidance
-        if cfg_on:  # [uncond, cond] (:1329-1337); zero negative image embedding (:437-439)
-            ehs = torch.cat([npe, pe])
-            ie_all = torch.cat([torch.zeros_like(ie), ie])
-            il_all = torch.cat([il, il])
-        else:
-            ehs, ie_all, il_all = pe, ie, il
-        nb = ehs.shape[0]
-        fps = torch.tensor([target_fps] * nb, device=device)
-        self.scheduler.set_timesteps(num_inference_steps, device=device)
-        timesteps = self.scheduler.timesteps
-        latents = self.prepare_latents(1, self.unet.config.in_channels, num_frames, height, width, torch.float16, device,
-                                       generator, latents).to(torch.float16)
-        sample = latents.repeat(nb, 1, 1, 1, 1).contiguous()
-        cond = dict(encoder_hidden_states=ehs.contiguous(), fps=fps, image_latents=il_all.contiguous(),
-                    image_embeddings=ie_all.contiguous())
-        eng = self._engine("inv", sample, cond, b_unc=0 if cfg_on else -1, b_cond=nb - 1, guidance=guidance_scale,
-                           dup_slots=range(nb - 1))
+        lp = self._loop_setup("inv", prompt, image, height, width, target_fps, num_frames, num_inference_steps, guidance_scale,
+                              negative_prompt, eta, num_videos_per_prompt, generator, latents, prompt_embeds, negative_prompt_embeds,
+                              cross_attention_kwargs, clip_skip, image_embeddings, image_latents)
+        nb, ts = lp.nb, lp.ts
+        eng = cached_engine(self, "inv", lp.sample, lp.cond, **lp.engine_kw)
         sample = eng.sample  # (a cached engine keeps its own static buffer; the latents were copied into it)
-        ts = [int(t) for t in timesteps.tolist()]
-        t_table = torch.tensor(ts, dtype=torch.float32, device=device)[:, None].expand(-1, nb).contiguous()
-        coef_table = self.scheduler.coefficient_table(ts, device)
         traj = LatentTrajectory()
         for i, t in enumerate(ts):
             if self.pace_wait is not None:
                 self.pace_wait(i, len(ts))
-            eng.step(t_table[i], coef_table[i], key=("inv",))
+            eng.step(lp.t_table[i], lp.coef_table[i], key=("inv",))
             traj[t] = sample[nb - 1:nb].clone()
         if output_dir is not None:
             # ddim_latents_{t}.pt, reference format.  Complete when invert() returns (as in the reference, which writes
@@ -757,10 +538,9 @@ class I2VGenXLPipeline(MaskedEditMixin):
                     image_latents=torch.cat(ils).contiguous(), image_embeddings=torch.cat(ies).contiguous())
         self.scheduler.set_timesteps(num_inference_steps, device=device)
         ts = [int(t) for t in self.scheduler.timesteps.tolist()]
-        eng = self._engine(f"inv{n}", sample, cond, b_unc=-1, b_cond=n - 1, guidance=1.0, dup_slots=(), lat_slots=tuple(range(n)))
+        eng = cached_engine(self, f"inv{n}", sample, cond, b_unc=-1, b_cond=n - 1, guidance=1.0, dup_slots=(), lat_slots=tuple(range(n)))
         sample = eng.sample
-        t_table = torch.tensor(ts, dtype=torch.float32, device=device)[:, None].expand(-1, n).contiguous()
-        coef_table = self.scheduler.coefficient_table(ts, device)
+        t_table, coef_table = self._step_tables(ts, n)
         trajs = [LatentTrajectory() for _ in range(n)]
         for i, t in enumerate(ts):
             eng.step(t_table[i], coef_table[i], key=("inv",))
@@ -784,41 +564,14 @@ class I2VGenXLPipeline(MaskedEditMixin):
                  latents_trace: Optional[dict] = None):
         """``latents_trace``: optional dict, filled with t -> latents after the step at t (drift reports; not a reference
         argument)."""
-        height = height or self.unet.config.sample_size * self.vae_scale_factor
-        width = width or self.unet.config.sample_size * self.vae_scale_factor
-        self.check_inputs(prompt, image, height, width, negative_prompt, prompt_embeds, negative_prompt_embeds)
-        self._refuse_masked_edit("__call__")
-        device = self._execution_device
-        self._guidance_scale = guidance_scale
-        pe, npe, ie, il = self._conditioning(prompt, image, height, width, num_frames, negative_prompt, prompt_embeds,
-                                             negative_prompt_embeds, target_fps, clip_skip, image_embeddings, image_latents)
-        self._single_clip(pe, num_videos_per_prompt)
-        stochastic, eta, phi = self._sampler_options(eta, cross_attention_kwargs)
-        cfg_on = self.do_classifier_free_guidance
-        pnp_utils.clear_time(self)  # plain CFG sampling (DDIM reconstruction) runs hook-free
-        if cfg_on:
-            ehs, ie_all, il_all = torch.cat([npe, pe]), torch.cat([torch.zeros_like(ie), ie]), torch.cat([il, il])
-        else:
-            ehs, ie_all, il_all = pe, ie, il
-        nb = ehs.shape[0]
-        fps = torch.tensor([target_fps] * nb, device=device)
-        self.scheduler.set_timesteps(num_inference_steps, device=device)
-        self.scheduler.timesteps = self.scheduler.timesteps[ddim_init_latents_t_idx:]  # :813
-        ts = [int(t) for t in self.scheduler.timesteps.tolist()]
-        latents = self.prepare_latents(1, self.unet.config.in_channels, num_frames, height, width, torch.float16, device,
-                                       generator, latents).to(torch.float16)
-        sample = latents.repeat(nb, 1, 1, 1, 1).contiguous()
-        cond = dict(encoder_hidden_states=ehs.contiguous(), fps=fps, image_latents=il_all.contiguous(),
-                    image_embeddings=ie_all.contiguous())
-        opts = dict(stochastic=stochastic, rescale=phi) if (stochastic or phi > 0.0) else {}
-        eng = self._engine("cfg", sample, cond, b_unc=0 if cfg_on else -1, b_cond=nb - 1, guidance=guidance_scale,
-                           dup_slots=range(nb - 1), shared_stem=cfg_on, **opts)
+        lp = self._loop_setup("cfg", prompt, image, height, width, target_fps, num_frames, num_inference_steps, guidance_scale,
+                              negative_prompt, eta, num_videos_per_prompt, generator, latents, prompt_embeds, negative_prompt_embeds,
+                              cross_attention_kwargs, clip_skip, image_embeddings, image_latents, t_idx=ddim_init_latents_t_idx)
+        nb = lp.nb
+        eng = cached_engine(self, "cfg", lp.sample, lp.cond, **lp.engine_kw)
         sample = eng.sample
-        t_table = torch.tensor(ts, dtype=torch.float32, device=device)[:, None].expand(-1, nb).contiguous()
-        coef_table = self.scheduler.coefficient_table(ts, device, eta=eta, phi=phi, n=latents.numel()) if opts else \
-            self.scheduler.coefficient_table(ts, device)
-        for i, t in enumerate(ts):
-            eng.step(t_table[i], coef_table[i], key=("cfg",), noise=self._variance_noise(stochastic, sample[nb - 1:nb], generator))
+        for i, t in enumerate(lp.ts):
+            eng.step(lp.t_table[i], lp.coef_table[i], key=("cfg",), noise=self._variance_noise(lp.stochastic, sample[nb - 1:nb], generator))
             if latents_trace is not None:
                 latents_trace[t] = sample[nb - 1:nb].clone()
         return self._finish(sample[nb - 1:nb].clone(), output_type, decode_chunk_size, return_dict)
@@ -836,135 +589,55 @@ class I2VGenXLPipeline(MaskedEditMixin):
                         ddim_inv_1st_frame=None, image_embeddings=None, image_latents=None,
                         ddim_inv_prompt_embeds=None, ddim_inv_image_embeddings=None, ddim_inv_image_latents=None,
                         latents_trace: Optional[dict] = None):
-        height = height or self.unet.config.sample_size * self.vae_scale_factor
-        width = width or self.unet.config.sample_size * self.vae_scale_factor
-        self.check_inputs(prompt, image, height, width, negative_prompt, prompt_embeds, negative_prompt_embeds)
-        if isinstance(prompt, list):
-            assert len(ddim_inv_prompt) == len(prompt)  # :1000
-        device = self._execution_device
-        self._guidance_scale = guidance_scale
-        pe, npe, ie, il = self._conditioning(prompt, image, height, width, num_frames, negative_prompt, prompt_embeds,
-                                             negative_prompt_embeds, target_fps, clip_skip, image_embeddings, image_latents)
-        self._single_clip(pe, num_videos_per_prompt)
-        stochastic, eta, phi = self._sampler_options(eta, cross_attention_kwargs)
-        opts = dict(stochastic=stochastic, rescale=phi) if (stochastic or phi > 0.0) else {}
-        spe, sie, sil = self._source_conditioning(ddim_inv_prompt, ddim_inv_1st_frame, height, width, num_frames, clip_skip,
-                                                  ddim_inv_prompt_embeds, ddim_inv_image_embeddings, ddim_inv_image_latents)
-        cfg_on = self.do_classifier_free_guidance
-        if cfg_on:  # order: [ddim_inversion, negative, editing] (:1044,1093-1094)
-            ehs = torch.cat([spe, npe, pe])
-            ie_all = torch.cat([sie, torch.zeros_like(ie), ie])
-            il_all = torch.cat([sil, il, il])
-        else:
-            ehs, ie_all, il_all = torch.cat([spe, pe]), torch.cat([sie, ie]), torch.cat([sil, il])
-        nb = ehs.shape[0]
-        fps = torch.tensor([target_fps] * nb, device=device)
-        self.scheduler.set_timesteps(num_inference_steps, device=device)
-        self.scheduler.timesteps = self.scheduler.timesteps[ddim_init_latents_t_idx:]  # :1105
-        ts = [int(t) for t in self.scheduler.timesteps.tolist()]
-        latents = self.prepare_latents(1, self.unet.config.in_channels, num_frames, height, width, torch.float16, device,
-                                       generator, latents).to(torch.float16)
-        sample = latents.repeat(nb, 1, 1, 1, 1).contiguous()
-        cond = dict(encoder_hidden_states=ehs.contiguous(), fps=fps, image_latents=il_all.contiguous(),
-                    image_embeddings=ie_all.contiguous())
+        lp = self._loop_setup("pnp", prompt, image, height, width, target_fps, num_frames, num_inference_steps, guidance_scale,
+                              negative_prompt, eta, num_videos_per_prompt, generator, latents, prompt_embeds, negative_prompt_embeds,
+                              cross_attention_kwargs, clip_skip, image_embeddings, image_latents, t_idx=ddim_init_latents_t_idx,
+                              source=(ddim_inv_prompt, ddim_inv_1st_frame, ddim_inv_prompt_embeds, ddim_inv_image_embeddings,
+                                      ddim_inv_image_latents))
+        nb, ts, device = lp.nb, lp.ts, self._execution_device
         # masked edit (``enable_masked_edit``): the latent mask of this clip and the buffer of the per-step partner; one more engine option
-        masked = self._masked_edit_buffers(height, width, num_frames, latents)
-        if masked is not None:
-            opts = dict(opts, blend=masked[:2])
+        masked = self._masked_edit_buffers(lp.height, lp.width, num_frames, lp.latents)
+        engine_kw = lp.engine_kw if masked is None else dict(lp.engine_kw, blend=masked[:2])
         # the source branch's prediction is never read (:1136,1160-1162): its forward may stop behind the last hook site (exact)
-        drop_tail = cfg_on and nb == 3 and os.environ.get("ANYV2V_DROP_SRC_TAIL", "1") == "1"
-        eng = self._engine("pnp-droptail" if drop_tail else "pnp", sample, cond, b_unc=1 if cfg_on else -1, b_cond=nb - 1,
-                           guidance=guidance_scale, dup_slots=range(1, nb - 1), shared_stem=cfg_on, **opts)
-        eng.drop_src_tail = drop_tail
+        drop_tail = lp.cfg_on and nb == 3 and os.environ.get("ANYV2V_DROP_SRC_TAIL", "1") == "1"
+        eng = cached_engine(self, "pnp-droptail" if drop_tail else "pnp", lp.sample, lp.cond, drop_src_tail=drop_tail, **engine_kw)
         sample = eng.sample
         if masked is not None and eng.blend[1] is not masked[1]:
             # a cached engine: its graphs were captured on ITS buffers -- this clip's latent mask goes into them
             eng.blend[1].copy_(masked[1])
-            opts["blend"] = eng.blend
         # source trajectory resident in HBM (in-memory hand-off from invert(), or read once from the reference's files)
-        if isinstance(ddim_inv_latents_path, LatentTrajectory):
-            traj = ddim_inv_latents_path
-        else:
-            traj = LatentTrajectory.load(ddim_inv_latents_path, device=device, timesteps=ts)
-        t_table = torch.tensor(ts, dtype=torch.float32, device=device)[:, None].expand(-1, nb).contiguous()
-        coef_table = self.scheduler.coefficient_table(ts, device, eta=eta, phi=phi, n=latents.numel()) if opts else \
-            self.scheduler.coefficient_table(ts, device)
-        # Exact work elimination (SURVEY A.5 probe "branches 1,2 of a B=3 forward equal a B=2 forward"): on a step that lies
-        # outside every injection schedule nothing reads the source branch, so the step runs on the [negative, editing]
-        # slots only.  Both engines share the `sample` storage, so they can alternate freely.
-        skip_src = cfg_on and nb == 3 and os.environ.get("ANYV2V_SRC_SKIP", "1") == "1"
-        eng_nosrc = None
-        nosrc_bound = False
-        # multi-edit job: record / replay what the injected sites read from the source branch (SourceFeatureCache).  The sampler
-        # options (eta, guidance rescale) leave it valid: the source branch is fed from the inversion trajectory (``sample[0]`` below)
-        # and never sees the edit latent, its noise or its rescaled prediction, so what it records does not depend on them.
+        in_memory = isinstance(ddim_inv_latents_path, LatentTrajectory)
+        traj = ddim_inv_latents_path if in_memory else LatentTrajectory.load(ddim_inv_latents_path, device=device, timesteps=ts)
+        # Exact work elimination (SURVEY A.5 probe "branches 1,2 of a B=3 forward equal a B=2 forward"): on a step outside every
+        # injection schedule nothing reads the source branch, so it runs on the [negative, editing] slots only -- the engine's twin
+        skip_src = lp.cfg_on and nb == 3 and os.environ.get("ANYV2V_SRC_SKIP", "1") == "1"
+        twin = None   # (``bind_nosrc``: once per call, at the first step that needs it)
+        # multi-edit job: record / replay what the injected sites read from the source branch (SourceFeatureCache).  The sampler options
+        # leave it valid: that branch is fed from the inversion trajectory and never sees the edit latent, its noise or its prediction
         cache = self.source_cache if (skip_src and not pnp_utils.has_foreign_hooks(self.unet)
                                       and getattr(self.unet, "frame_parallel", None) is None) else None
-        sites = pnp_utils.injection_sites(self) if cache is not None else []
         if cache is not None:
-            fp_ = lambda x: (tuple(x.shape), float(x.float().sum()), float(x.float().abs().sum()))
-            src = ("object", traj.serial) if isinstance(ddim_inv_latents_path, LatentTrajectory) else ("files", os.path.abspath(str(ddim_inv_latents_path)))
-            cache.bind((src, tuple(ts), fp_(load_ddim_latents_at_t(ts[0], traj)), fp_(spe), fp_(sie), fp_(sil), int(target_fps),
-                        self.unet._pack_gen, id(self.unet), tuple(latents.shape), getattr(self.unet, "freeu", None)))
-            if not hasattr(eng, "site_bufs"):
-                # rows of ONE branch at the site's level: up_blocks[1] works at 1/16 of the 64x64 level's pixels, [2] at 1/4, [3] at 1/1
-                full = num_frames * (height // self.vae_scale_factor) * (width // self.vae_scale_factor)
-                level_div = {"1": 16, "2": 4, "3": 1}
-                eng.site_bufs = {name: torch.empty((full // level_div[name.split(".up")[1][0]], cols), dtype=torch.float16, device=device)
-                                 for name, _obj, cols in sites}
-
-        def set_io(mode, names):
-            for name, obj, _ in sites:
-                obj.src_io = (mode, eng.site_bufs[name]) if (mode is not None and name in names) else None
-
+            traj_id = ("object", traj.serial) if in_memory else ("files", os.path.abspath(str(ddim_inv_latents_path)))
+            cache.begin_run(self, eng, traj_id, ts, load_ddim_latents_at_t(ts[0], traj), lp.source_cond, target_fps, lp.latents.shape)
         for i, t in enumerate(ts):
             if self.pace_record is not None:
                 self.pace_record(i, len(ts))
             pnp_utils.register_time(self, t)  # host-side only: python int, no device sync (:1143)
             state = pnp_utils.injection_state(self)
-            noise = self._variance_noise(stochastic, sample[nb - 1:nb], generator)   # one draw per step, whichever engine runs it
+            noise = self._variance_noise(lp.stochastic, sample[nb - 1:nb], generator)   # one draw per step, whichever engine runs it
             # masked edit: after this step the edit latent sits at level ts[i + 1] -- its partner is the source at that level, the clean
             # latent after the last step.  Copied into the static buffer outside the graph, whichever engine runs the step
             extra = {} if masked is None else dict(partner=(
                 load_ddim_latents_at_t(ts[i + 1], traj).to(device=device, dtype=torch.float16) if i + 1 < len(ts) else masked[2]))
-            if any(state) and nb != 3:
-                # the hooks slice the batch in thirds (pnp_utils.py:111,166,272); with guidance_scale <= 1 the reference
-                # builds a 2-way batch and silently injects the wrong rows -- refuse instead
-                raise ValueError("PnP feature injection needs classifier-free guidance (guidance_scale > 1): the hooks "
-                                 "assume the 3-way batch [source, negative, editing]")
-            if skip_src and not any(state):
-                if not nosrc_bound:  # built once per engine (it lives on `sample[1:]`), re-pointed at this clip once per call
-                    cond2 = {k: v[1:].contiguous() for k, v in cond.items()}
-                    if eng.nosrc is None or not eng.nosrc.rebind(sample[1:], cond2):
-                        eng.nosrc = _StepEngine(self, sample[1:], cond2, b_unc=0, b_cond=1, guidance=guidance_scale,
-                                                dup_slots=[0], shared_stem=True, batch_hint=(3, 2), **opts)
-                    eng_nosrc, nosrc_bound = eng.nosrc, True
-                eng_nosrc.step(t_table[i, 1:], coef_table[i], key=("pnp-nosrc",), noise=noise, **extra)
-            elif cache is not None and cache.has(t, state):
-                # replay: the source features of this step are in HBM -- [negative, editing] only
-                names = [n for (n, _, _), on in zip(sites, state) if on]
-                if not nosrc_bound:
-                    cond2 = {k: v[1:].contiguous() for k, v in cond.items()}
-                    if eng.nosrc is None or not eng.nosrc.rebind(sample[1:], cond2):
-                        eng.nosrc = _StepEngine(self, sample[1:], cond2, b_unc=0, b_cond=1, guidance=guidance_scale,
-                                                dup_slots=[0], shared_stem=True, batch_hint=(3, 2), **opts)
-                    eng_nosrc, nosrc_bound = eng.nosrc, True
-                for n in names:
-                    eng.site_bufs[n].copy_(cache.steps[(int(t), state)][n], non_blocking=True)
-                set_io("replay", names)
-                eng_nosrc.step(t_table[i, 1:], coef_table[i], key=("pnp-replay",) + state, noise=noise, **extra)
-                set_io(None, ())
-                cache.replayed_steps += 1
+            kind, key = pnp_step_plan(nb, skip_src, state, None if cache is None else cache.has(t, state))
+            if kind in ("nosrc", "replay"):   # [negative, editing] only
+                twin = twin or eng.bind_nosrc()
+                step_eng, t_row = twin, lp.t_table[i, 1:]
             else:
                 sample[0].copy_(load_ddim_latents_at_t(t, traj).to(device=device, dtype=torch.float16)[0], non_blocking=True)
-                if cache is not None:
-                    names = [n for (n, _, _), on in zip(sites, state) if on]
-                    set_io("record", names)
-                    eng.step(t_table[i], coef_table[i], key=("pnp-record",) + state, noise=noise, **extra)
-                    set_io(None, ())
-                    cache.recorded_steps += bool(cache.store(t, state, {n: eng.site_bufs[n] for n in names}))
-                else:
-                    eng.step(t_table[i], coef_table[i], key=("pnp",) + state, noise=noise, **extra)
+                step_eng, t_row = eng, lp.t_table[i]
+            with (cache.step_io(eng, kind, t, state) if kind in ("record", "replay") else nullcontext()):
+                step_eng.step(t_row, lp.coef_table[i], key=key, noise=noise, **extra)
             if latents_trace is not None:
                 latents_trace[t] = sample[nb - 1:nb].clone()
         return self._finish(sample[nb - 1:nb].clone(), output_type, decode_chunk_size, return_dict)

@@ -91,7 +91,7 @@ class Stage2:
         self.my_latents, self.lat_shape = {}, None
         self.my_entries = self._my_entries if self._my_entries is not None else shard_entries(configs_list, self.e_rank, self.e_world)
         # Several edits of one clip on this rank (the demo group config: 8 edits of one clip): keep the source branch's injected features
-        # in HBM after the first edit, so that the further ones run [negative, editing] only (pipeline.SourceFeatureCache; exact).
+        # in HBM after the first edit, so that the further ones run [negative, editing] only (step_engine.SourceFeatureCache; exact).
         # ANYV2V_SOURCE_CACHE=0 switches it off.
         clips = [e.get("video_name") for e in self.my_entries]
         if os.environ.get("ANYV2V_SOURCE_CACHE", "1") == "1" and len(clips) != len(set(clips)) and pipe.source_cache is None:

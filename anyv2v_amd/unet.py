@@ -268,7 +268,7 @@ class HipAttnProcessor:
     def __init__(self, injection_schedule=None):
         self.injection_schedule = injection_schedule
         self.t = None
-        # source-feature cache of a multi-edit job (pipeline.SourceFeatureCache): None, ("record", buf) -- copy the source branch's
+        # source-feature cache of a multi-edit job (step_engine.SourceFeatureCache): None, ("record", buf) -- copy the source branch's
         # Q | K columns of this step into ``buf`` [Ts, 2 C] -- or ("replay", buf): the batch is [negative, editing] only and the
         # source branch's Q, K are read from ``buf`` (recorded by an earlier edit of the same clip)
         self.src_io = None

@@ -2106,7 +2106,7 @@ def check_unet_vs_oracle(cfg_name="mini", B=3, Fr=4, hw=8, with_pnp=True, tol=3e
 
 def check_engine_reuse_across_clips():
     """Multi-clip jobs keep the step engines (static buffers + HIP graphs) and re-point them at the next clip
-    (``pipeline._engine`` / ``_StepEngine.rebind``): clip B through engines captured for clip A must be BIT-equal to clip B on a
+    (``step_engine.cached_engine`` / ``_StepEngine.rebind``): clip B through engines captured for clip A must be BIT-equal to clip B on a
     fresh pipeline -- any step-invariant tensor left over from clip A would show here.  Covers inversion, the PnP edit with its
     [negative, editing]-only engine (schedules ending early) and the plain CFG loop."""
     from anyv2v_amd import pnp_utils
@@ -2325,7 +2325,7 @@ _MODELS = {}
 
 
 def check_source_cache(cfg_name="mini", Fr=4, hw=8, n_steps=6):
-    """Multi-edit job (``pipeline.SourceFeatureCache``): three edits of ONE clip -- different prompts and edited frames, the third
+    """Multi-edit job (``step_engine.SourceFeatureCache``): three edits of ONE clip -- different prompts and edited frames, the third
     also with shorter injection schedules -- with the cache (the first records, the others replay and run [negative, editing]
     only) must be BIT-EQUAL to the same three edits without it; the cache really is used (replayed steps counted) and is dropped
     when the clip changes."""
