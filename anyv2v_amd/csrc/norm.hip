@@ -16,8 +16,7 @@
 // sharded entry points, which agree on one pivot first).  The ABI-101 sharded pair (anyv2v_groupnorm_partial_f16 / _apply_f16)
 // keeps its one-all-reduce contract and therefore the rank-independent pivot K = 0: unshifted sums, as before.
 #include "common.h"
-
-#define GN_MAX_CHUNKS 256
+#include "norm_plan.h"
 
 // pivot of (stat group sg, channel group g): the caller's agreed value, x[first row of sg][first channel of g] (pivot == nullptr,
 // from_data) or 0 (pivot == nullptr, !from_data: the unshifted sums of the one-all-reduce sharded pair)
@@ -177,6 +176,42 @@ __device__ __forceinline__ void gn_apply_rows(const half_t* __restrict__ X0, con
     for (; r < r_end; r += rpb) *(h8*)(dst + (size_t)r * C) = norm8(*(const h8*)(src + (size_t)r * ld));
 }
 
+// The statistics prologue shared by the apply kernels.  The first min(blockDim.x, 256) threads are `parts` = that / G rows of G threads;
+// thread (part, g) brings the sums (as, aq) of channel group g over its share of the chunks (or records), about the pivot kpiv.  The
+// parts are added in ascending order -- the same additions in every block of a statistics group, so identical in all of them -- and
+// thread g < G writes smean[g] = kpiv + s / n, srstd[g] = rsqrt(q / n - (s / n)^2 + eps).  Called by every thread of the block.
+__device__ __forceinline__ void gn_fold_stats(float as, float aq, float kpiv, int parts, int G, float inv_cnt, float eps, float* smean,
+                                              float* srstd) {
+    __shared__ float rs[256], rq[256];
+    const int tid = threadIdx.x;
+    if (tid < 256) {
+        rs[tid] = as;
+        rq[tid] = aq;
+    }
+    __syncthreads();
+    if (tid < G) {
+        float s = 0.f, q = 0.f;
+        for (int p2 = 0; p2 < parts; ++p2) {
+            s += rs[p2 * G + tid];
+            q += rq[p2 * G + tid];
+        }
+        const float m = s * inv_cnt;  // mean - pivot
+        const float var = fmaxf(q * inv_cnt - m * m, 0.f);
+        smean[tid] = kpiv + m;
+        srstd[tid] = rsqrtf(var + eps);
+    }
+    __syncthreads();
+}
+
+// (as, aq) += the record src = (K_i, s_i, q_i) over n values, moved to the pivot kpiv exactly: s_i + n d, q_i + 2 d s_i + n d^2 with
+// d = K_i - kpiv (a difference of two fp16 values: exact)
+__device__ __forceinline__ void gn_move_record(const float* src, float kpiv, float n, float& as, float& aq) {
+    const float d = src[0] - kpiv, si = src[1], qi = src[2];
+    const float nd = n * d;
+    as += si + nd;
+    aq += qi + (2.f * d * si + nd * d);
+}
+
 template <int U>
 __global__ __launch_bounds__(1024) void gn_apply_kernel(const half_t* __restrict__ X0, const half_t* __restrict__ X1, int C0,
                                                         int C1, half_t* __restrict__ Y, const half_t* __restrict__ gamma,
@@ -184,90 +219,45 @@ __global__ __launch_bounds__(1024) void gn_apply_kernel(const half_t* __restrict
                                                         int from_data, const float* __restrict__ partial, int nchunks, float inv_cnt,
                                                         float eps, int rows_per_group, int G, int silu, int rpb,
                                                         int rows_per_block) {
-    __shared__ float rs[256], rq[256], smean[64], srstd[64];
-    const int C = C0 + C1, V = C >> 3, cpg = C / G;
+    __shared__ float smean[64], srstd[64];
     const int sg = blockIdx.y, tid = threadIdx.x;
-    {   // statistics of this stat group: same order of additions in every block -> identical in all of them
-        const int nt = blockDim.x < 256 ? blockDim.x : 256;
-        const int parts = nt / G;  // G <= 64 <= blockDim.x
-        const int g = tid % G, part = tid / G;
-        // this group's pivot, loaded before the chunk sums so that its latency overlaps theirs
-        const float kpiv = tid < G ? gn_pivot(X0, X1, C0, C1, pivot, from_data, sg, rows_per_group, G, tid) : 0.f;
-        if (tid < 256) {
-            float as = 0.f, aq = 0.f;
-            if (part < parts)
-                for (int c = part; c < nchunks; c += parts) {
-                    const float* src = partial + (((size_t)sg * nchunks + c) * G + g) * 2;
-                    as += src[0];
-                    aq += src[1];
-                }
-            rs[tid] = as;
-            rq[tid] = aq;
+    const int nt = blockDim.x < 256 ? blockDim.x : 256;
+    const int parts = nt / G;  // G <= 64 <= blockDim.x
+    const int g = tid % G, part = tid / G;
+    // this group's pivot, loaded before the chunk sums so that its latency overlaps theirs
+    const float kpiv = tid < G ? gn_pivot(X0, X1, C0, C1, pivot, from_data, sg, rows_per_group, G, tid) : 0.f;
+    float as = 0.f, aq = 0.f;
+    if (part < parts)   // thread (part, g) takes chunks part, part + parts, ... in ascending order
+        for (int c = part; c < nchunks; c += parts) {
+            const float* src = partial + (((size_t)sg * nchunks + c) * G + g) * 2;
+            as += src[0];
+            aq += src[1];
         }
-        __syncthreads();
-        if (tid < G) {
-            float s = 0.f, q = 0.f;
-            for (int p2 = 0; p2 < parts; ++p2) {
-                s += rs[p2 * G + tid];
-                q += rq[p2 * G + tid];
-            }
-            const float m = s * inv_cnt;  // mean - pivot
-            const float var = fmaxf(q * inv_cnt - m * m, 0.f);
-            smean[tid] = kpiv + m;
-            srstd[tid] = rsqrtf(var + eps);
-        }
-        __syncthreads();
-    }
+    gn_fold_stats(as, aq, kpiv, parts, G, inv_cnt, eps, smean, srstd);
     gn_apply_rows<U>(X0, X1, C0, C1, Y, gamma, beta, smean, srstd, rows_per_group, G, silu, rpb, rows_per_block);
 }
 
 // GroupNorm from the records a producing GEMM wrote (AnyV2VGemmDesc.gn_stats): gn_apply_kernel with another statistics prologue.
 // rec: [statistics group][record][G][3] = (K_i, s_i, q_i), nrec records per (statistics group, channel group), each over n_rec
-// values except the last (n_last).  Every block moves them to the pivot of record 0 exactly -- s += s_i + n_i d,
-// q += q_i + 2 d s_i + n_i d^2, d = K_i - K (a difference of two fp16 values: exact) -- thread (part, g) taking records part,
-// part + parts, ... in ascending order, then the parts in ascending order: the same additions in every block.
+// values except the last (n_last).  Every block moves them to the pivot of record 0 (gn_move_record), thread (part, g) taking records
+// part, part + parts, ... in ascending order.
 template <int U>
 __global__ __launch_bounds__(1024) void gn_apply_stats_kernel(const half_t* __restrict__ X, half_t* __restrict__ Y,
                                                               const half_t* __restrict__ gamma, const half_t* __restrict__ beta,
                                                               const float* __restrict__ rec, int nrec, float n_rec, float n_last,
                                                               float inv_cnt, float eps, int C, int rows_per_group, int G, int silu,
                                                               int rpb, int rows_per_block) {
-    __shared__ float rs[256], rq[256], smean[64], srstd[64];
+    __shared__ float smean[64], srstd[64];
     const int sg = blockIdx.y, tid = threadIdx.x;
-    {
-        const int nt = blockDim.x < 256 ? blockDim.x : 256;
-        const int parts = nt / G;  // G <= 64 <= blockDim.x
-        const int g = tid % G, part = tid / G;
-        const float* base = rec + ((size_t)sg * nrec * G + g) * 3;
-        const float kpiv = base[0];
-        if (tid < 256) {
-            float as = 0.f, aq = 0.f;
-            if (part < parts)
-                for (int c = part; c < nrec; c += parts) {
-                    const float* src = base + (size_t)c * G * 3;
-                    const float n = c + 1 == nrec ? n_last : n_rec;
-                    const float d = src[0] - kpiv, si = src[1], qi = src[2];
-                    const float nd = n * d;
-                    as += si + nd;
-                    aq += qi + (2.f * d * si + nd * d);
-                }
-            rs[tid] = as;
-            rq[tid] = aq;
-        }
-        __syncthreads();
-        if (tid < G) {
-            float s = 0.f, q = 0.f;
-            for (int p2 = 0; p2 < parts; ++p2) {
-                s += rs[p2 * G + tid];
-                q += rq[p2 * G + tid];
-            }
-            const float m = s * inv_cnt;  // mean - pivot
-            const float var = fmaxf(q * inv_cnt - m * m, 0.f);
-            smean[tid] = kpiv + m;
-            srstd[tid] = rsqrtf(var + eps);
-        }
-        __syncthreads();
-    }
+    const int nt = blockDim.x < 256 ? blockDim.x : 256;
+    const int parts = nt / G;  // G <= 64 <= blockDim.x
+    const int g = tid % G, part = tid / G;
+    const float* base = rec + ((size_t)sg * nrec * G + g) * 3;
+    const float kpiv = base[0];
+    float as = 0.f, aq = 0.f;
+    if (part < parts)
+        for (int c = part; c < nrec; c += parts) gn_move_record(base + (size_t)c * G * 3, kpiv, c + 1 == nrec ? n_last : n_rec, as, aq);
+    gn_fold_stats(as, aq, kpiv, parts, G, inv_cnt, eps, smean, srstd);
     // (X twice: the second source is never read with C1 = 0, and a literal nullptr here crashes hipcc 7.2's inliner)
     gn_apply_rows<U>(X, X, C, 0, Y, gamma, beta, smean, srstd, rows_per_group, G, silu, rpb, rows_per_block);
 }
@@ -284,33 +274,16 @@ __global__ void gn_fold_records_kernel(const float* __restrict__ rec, float* __r
     if (cnt > run) cnt = run;
     const float kpiv = base[0];
     float as = 0.f, aq = 0.f;
-    for (int c = 0; c < cnt; ++c) {
-        const float* src = base + (size_t)c * G * 3;
-        const float d = src[0] - kpiv, si = src[1], qi = src[2];
-        const float nd = n_rec * d;
-        as += si + nd;
-        aq += qi + (2.f * d * si + nd * d);
-    }
+    for (int c = 0; c < cnt; ++c) gn_move_record(base + (size_t)c * G * 3, kpiv, n_rec, as, aq);
     float* o = out + (((size_t)sg * nruns + j) * G + g) * 3;
     o[0] = kpiv;
     o[1] = as;
     o[2] = aq;
 }
+
 extern "C" int64_t anyv2v_groupnorm_scratch_floats(int32_t M, int32_t rows_per_group, int32_t G) {
-    const int64_t nsg = rows_per_group > 0 ? M / rows_per_group : 0;
-    return nsg * G * 2 * (int64_t)(1 + GN_MAX_CHUNKS);
+    return av_gn_scratch_floats(M, rows_per_group, G);
 }
-
-// launch plan shared by the one-call and the two-phase (sharded) entry points
-struct GnPlan {
-    int nsg, V, rpb, threads, nchunks, rows_chunk, rows_block;
-    size_t lds;
-    long long bps;
-};
-
-template <int U>
-__global__ void gn_apply_kernel(const half_t*, const half_t*, int, int, half_t*, const half_t*, const half_t*, const float*,
-                                int, const float*, int, float, float, int, int, int, int, int);
 
 // resident gn_apply blocks on the whole device for a block size (occupancy query, cached per size)
 static int gn_apply_slots(int threads) {
@@ -327,47 +300,15 @@ static int gn_apply_slots(int threads) {
     return cache[threads];
 }
 
-static int gn_plan(GnPlan& pl, const void* X0, const void* X1, int32_t C0, int32_t C1, int32_t M, int32_t rows_per_group,
-                   int32_t G) {
-    AV_CHECK(C0 > 0 && C1 >= 0 && (C1 == 0 || X1), "groupnorm: bad C0/C1");
-    const int C = C0 + C1;
-    AV_CHECK(C0 % 8 == 0 && C1 % 8 == 0, "groupnorm: C0/C1 must be multiples of 8 (%d,%d)", C0, C1);
-    AV_CHECK(G > 0 && G <= 64 && C % G == 0, "groupnorm: bad group count %d for C=%d", G, C);
-    AV_CHECK(rows_per_group > 0 && M % rows_per_group == 0, "groupnorm: M %% rows_per_group != 0");
-    AV_CHECK(av_aligned16(X0) && av_aligned16(X1), "groupnorm: pointers must be 16-byte aligned");
-    pl.nsg = M / rows_per_group;
-    pl.V = C / 8;
-    AV_CHECK(pl.V <= 1024, "groupnorm: C too large (%d)", C);
-    pl.rpb = 256 / pl.V;
-    if (pl.rpb < 1) pl.rpb = 1;
-    pl.threads = pl.V * pl.rpb;
-    if (pl.threads < 64) pl.threads = 64;
-    if (pl.threads < G) pl.threads = G;
-    // (chunking decided on the hinted number of statistics groups -- anyv2v_set_batch_hint: a two-branch step sums its chunks in
-    //  the order the three-branch step does)
-    const int nsg_h = av_hint_rows(M) / rows_per_group > 0 ? av_hint_rows(M) / rows_per_group : 1;
-    int nchunks = (1536 + nsg_h - 1) / nsg_h;
-    int max_chunks = (rows_per_group + pl.rpb * 8 - 1) / (pl.rpb * 8);  // >= 8 row-iterations per thread
-    if (max_chunks < 1) max_chunks = 1;
-    if (nchunks > max_chunks) nchunks = max_chunks;
-    if (nchunks > GN_MAX_CHUNKS) nchunks = GN_MAX_CHUNKS;
-    pl.rows_chunk = (rows_per_group + nchunks - 1) / nchunks;
-    pl.nchunks = (rows_per_group + pl.rows_chunk - 1) / pl.rows_chunk;
-    pl.lds = (size_t)pl.rpb * C * 2 * sizeof(float);
-    AV_CHECK(pl.lds <= 64 * 1024, "groupnorm: LDS reduction buffer too large");
-    // Apply blocks: as many as the chip holds at once (CUs x resident blocks of this size), not more -- 2064 blocks on 1792 slots
-    // ran a second, 15 %-full round (the 64x64-level launches, profiles/r03_bench_kernel_summary.md); each block at least 8
-    // row-iterations per thread where the stat group is large enough.  (The partition has no effect on the result.)
-    const long long vec_sg = (long long)rows_per_group * pl.V;
-    AV_CHECK(vec_sg < (1ll << 31), "groupnorm: stat group too large (%lld vectors)", vec_sg);
-    const int slots = gn_apply_slots(pl.threads);
-    pl.bps = slots / pl.nsg;
-    const long long max_bps = (rows_per_group + pl.rpb * 8 - 1) / (pl.rpb * 8);
-    if (pl.bps > max_bps) pl.bps = max_bps;
-    if (pl.bps < 1) pl.bps = 1;
-    pl.rows_block = (int)((rows_per_group + pl.bps - 1) / pl.bps);
-    pl.bps = (rows_per_group + pl.rows_block - 1) / pl.rows_block;
-    return ANYV2V_OK;
+// launch plan shared by the one-call and the two-phase (sharded) entry points: av_gn_plan under the batch hint in force and this
+// device's occupancy.  X0 is not null; a second width needs a second source.
+static GnPlan gn_plan(const void* X0, const void* X1, int32_t C0, int32_t C1, int32_t M, int32_t rows_per_group, int32_t G) {
+    if (C1 > 0 && !X1) {
+        anyv2v_set_error("groupnorm: bad C0/C1");
+        return GnPlan{ANYV2V_EINVAL};
+    }
+    return av_gn_plan(C0, C1, M, rows_per_group, G, av_hint_rows(M), gn_apply_slots(av_gn_threads(C0 + C1, G)),
+                      av_aligned16(X0) && av_aligned16(X1));
 }
 
 // pivot: [nsg][G] agreed pivots, or nullptr: each stat group's own first element per channel group (from_data) or 0
@@ -394,46 +335,39 @@ extern "C" int anyv2v_groupnorm_f16(const void* X0, const void* X1, int32_t C0, 
                                     const void* gamma, const void* beta, float* stats, int32_t M,
                                     int32_t rows_per_group, int32_t G, float eps, int32_t silu, void* stream) {
     AV_CHECK(X0 && Y && gamma && beta && stats, "groupnorm: null pointer");
-    GnPlan pl;
-    if (int rc = gn_plan(pl, X0, X1, C0, C1, M, rows_per_group, G)) return rc;
+    const GnPlan pl = gn_plan(X0, X1, C0, C1, M, rows_per_group, G);
+    if (pl.status) return pl.status;
     if (int rc = gn_partial(pl, X0, X1, C0, C1, nullptr, 1, stats, rows_per_group, G, (hipStream_t)stream)) return rc;
     return gn_apply(pl, X0, X1, C0, C1, Y, gamma, beta, nullptr, 1, stats, rows_per_group, G, eps, silu, 1, (hipStream_t)stream);
 }
 
 extern "C" int64_t anyv2v_groupnorm_stats_floats(int32_t M, int32_t rows_per_group, int32_t G) {
-    if (M <= 0 || rows_per_group <= 0 || G <= 0 || rows_per_group % 16 != 0 || M % rows_per_group != 0) return 0;
-    return (int64_t)3 * (M / 16) * G + (int64_t)3 * (M / rows_per_group) * GN_MAX_CHUNKS * G;
+    return av_gn_stats_floats(M, rows_per_group, G);
 }
 
 extern "C" int anyv2v_groupnorm_apply_stats_f16(const void* X, void* Y, const void* gamma, const void* beta, float* stats,
                                                 const int32_t* sizes, float eps, int32_t silu, void* stream) {
     AV_CHECK(X && Y && gamma && beta && stats && sizes, "groupnorm_apply_stats: null pointer");
     const int32_t M = sizes[0], C = sizes[1], rows_per_group = sizes[2], G = sizes[3];
-    GnPlan pl;
-    if (int rc = gn_plan(pl, X, nullptr, C, 0, M, rows_per_group, G)) return rc;
+    const GnPlan pl = gn_plan(X, nullptr, C, 0, M, rows_per_group, G);
+    if (pl.status) return pl.status;
     AV_CHECK(av_aligned16(Y) && av_aligned16(gamma) && av_aligned16(beta), "groupnorm: pointers must be 16-byte aligned");
-    AV_CHECK(rows_per_group % 16 == 0, "groupnorm_apply_stats: rows_per_group must be a multiple of 16 (%d)", rows_per_group);
-    AV_CHECK((int64_t)sizes[4] >= anyv2v_groupnorm_stats_floats(M, rows_per_group, G),
+    const GnRecordsPlan rp = av_gn_records_plan(M, C, rows_per_group, G);
+    if (rp.status) return rp.status;
+    AV_CHECK((int64_t)sizes[4] >= av_gn_stats_floats(M, rows_per_group, G),
              "groupnorm_apply_stats: stats holds %d floats, needs anyv2v_groupnorm_stats_floats() = %lld", sizes[4],
-             (long long)anyv2v_groupnorm_stats_floats(M, rows_per_group, G));
-    const int cpg = C / G;
-    int nrec = rows_per_group / 16;
-    float n_rec = 16.f * (float)cpg, n_last = n_rec;
+             (long long)av_gn_stats_floats(M, rows_per_group, G));
     const float* rec = stats;
     hipStream_t s = (hipStream_t)stream;
-    if (nrec > GN_MAX_CHUNKS) {   // fold runs of records first, into the tail of `stats`
-        const int run = (nrec + GN_MAX_CHUNKS - 1) / GN_MAX_CHUNKS, nruns = (nrec + run - 1) / run;
-        float* folded = stats + (size_t)3 * (M / 16) * G;
-        hipLaunchKernelGGL(gn_fold_records_kernel, dim3(nruns, pl.nsg), dim3(64), 0, s, rec, folded, nrec, run, nruns, G, n_rec);
+    if (rp.fold) {   // runs of records first, into the tail of `stats`
+        hipLaunchKernelGGL(gn_fold_records_kernel, dim3(rp.nruns, pl.nsg), dim3(64), 0, s, rec, stats + rp.folded_at, rp.nrec, rp.run,
+                           rp.nruns, G, rp.n_gemm);
         if (int rc = av_launch_status("groupnorm<fold records>")) return rc;
-        n_last = n_rec * (float)(nrec - (nruns - 1) * run);
-        n_rec *= (float)run;
-        nrec = nruns;
-        rec = folded;
+        rec = stats + rp.folded_at;
     }
-    const float inv_cnt = 1.0f / ((float)rows_per_group * (float)cpg);
+    const float inv_cnt = 1.0f / ((float)rows_per_group * (float)(C / G));
     hipLaunchKernelGGL(gn_apply_stats_kernel<4>, dim3((unsigned)pl.bps, (unsigned)pl.nsg), dim3(pl.threads), 0, s, (const half_t*)X,
-                       (half_t*)Y, (const half_t*)gamma, (const half_t*)beta, rec, nrec, n_rec, n_last, inv_cnt, eps, C,
+                       (half_t*)Y, (const half_t*)gamma, (const half_t*)beta, rec, rp.nruns, rp.n_rec, rp.n_last, inv_cnt, eps, C,
                        rows_per_group, G, silu, pl.rpb, pl.rows_block);
     return av_launch_status("groupnorm<from records>");
 }
@@ -448,25 +382,22 @@ extern "C" int anyv2v_groupnorm_pivot_f16(const void* X0, const void* X1, int32_
                                           int32_t rows_per_group, int32_t G, int32_t shards, void* stream) {
     AV_CHECK(X0 && pivot, "groupnorm_pivot: null pointer");
     AV_CHECK(shards >= 1, "groupnorm_pivot: shards must be >= 1");
-    GnPlan pl;
-    if (int rc = gn_plan(pl, X0, X1, C0, C1, M, rows_per_group, G)) return rc;
+    const GnPlan pl = gn_plan(X0, X1, C0, C1, M, rows_per_group, G);
+    if (pl.status) return pl.status;
     hipLaunchKernelGGL(gn_pivot_kernel, dim3(pl.nsg), dim3(64), 0, (hipStream_t)stream, (const half_t*)X0, (const half_t*)X1, C0,
                        C1, pivot, rows_per_group, G, (float)shards);
     return av_launch_status("groupnorm<pivot>");
 }
 
 extern "C" int64_t anyv2v_groupnorm_partial_floats(int32_t M, int32_t rows_per_group, int32_t G, int32_t C) {
-    GnPlan pl;
-    static const int dummy __attribute__((aligned(16))) = 0;
-    if (gn_plan(pl, &dummy, nullptr, C, 0, M, rows_per_group, G) != ANYV2V_OK) return -1;
-    return (int64_t)pl.nsg * pl.nchunks * G * 2;
+    return av_gn_partial_floats(av_gn_plan(C, 0, M, rows_per_group, G, av_hint_rows(M), 1), G);   // (the chunking ignores the occupancy)
 }
 
 extern "C" int anyv2v_groupnorm_partial_pivot_f16(const void* X0, const void* X1, int32_t C0, int32_t C1, const float* pivot,
                                                   float* stats, int32_t M, int32_t rows_per_group, int32_t G, void* stream) {
     AV_CHECK(X0 && pivot && stats, "groupnorm_partial: null pointer");
-    GnPlan pl;
-    if (int rc = gn_plan(pl, X0, X1, C0, C1, M, rows_per_group, G)) return rc;
+    const GnPlan pl = gn_plan(X0, X1, C0, C1, M, rows_per_group, G);
+    if (pl.status) return pl.status;
     return gn_partial(pl, X0, X1, C0, C1, pivot, 0, stats, rows_per_group, G, (hipStream_t)stream);
 }
 
@@ -476,16 +407,16 @@ extern "C" int anyv2v_groupnorm_apply_pivot_f16(const void* X0, const void* X1, 
                                                 int32_t shards, void* stream) {
     AV_CHECK(X0 && Y && gamma && beta && pivot && stats, "groupnorm_apply: null pointer");
     AV_CHECK(shards >= 1, "groupnorm_apply: shards must be >= 1");
-    GnPlan pl;
-    if (int rc = gn_plan(pl, X0, X1, C0, C1, M, rows_per_group, G)) return rc;
+    const GnPlan pl = gn_plan(X0, X1, C0, C1, M, rows_per_group, G);
+    if (pl.status) return pl.status;
     return gn_apply(pl, X0, X1, C0, C1, Y, gamma, beta, pivot, 0, stats, rows_per_group, G, eps, silu, shards, (hipStream_t)stream);
 }
 
 extern "C" int anyv2v_groupnorm_partial_f16(const void* X0, const void* X1, int32_t C0, int32_t C1, float* stats, int32_t M,
                                             int32_t rows_per_group, int32_t G, void* stream) {
     AV_CHECK(X0 && stats, "groupnorm_partial: null pointer");
-    GnPlan pl;
-    if (int rc = gn_plan(pl, X0, X1, C0, C1, M, rows_per_group, G)) return rc;
+    const GnPlan pl = gn_plan(X0, X1, C0, C1, M, rows_per_group, G);
+    if (pl.status) return pl.status;
     return gn_partial(pl, X0, X1, C0, C1, nullptr, 0, stats, rows_per_group, G, (hipStream_t)stream);
 }
 
@@ -495,8 +426,8 @@ extern "C" int anyv2v_groupnorm_apply_f16(const void* X0, const void* X1, int32_
                                           void* stream) {
     AV_CHECK(X0 && Y && gamma && beta && stats, "groupnorm_apply: null pointer");
     AV_CHECK(shards >= 1, "groupnorm_apply: shards must be >= 1");
-    GnPlan pl;
-    if (int rc = gn_plan(pl, X0, X1, C0, C1, M, rows_per_group, G)) return rc;
+    const GnPlan pl = gn_plan(X0, X1, C0, C1, M, rows_per_group, G);
+    if (pl.status) return pl.status;
     return gn_apply(pl, X0, X1, C0, C1, Y, gamma, beta, nullptr, 0, stats, rows_per_group, G, eps, silu, shards, (hipStream_t)stream);
 }
 

@@ -258,7 +258,25 @@ def ln_fold(w: torch.Tensor, bias: Optional[torch.Tensor], gamma: torch.Tensor, 
 
 
 def gn_scratch_floats(M: int, rows_per_group: int, groups: int = 32) -> int:
-    return (M // rows_per_group) * groups * 2 * 257  # == anyv2v_groupnorm_scratch_floats (1 + 256 chunks)
+    """Size of the ``stats`` scratch of ``groupnorm`` (== anyv2v_groupnorm_scratch_floats): any plan's partial sums, and the pivots of
+    the sharded form behind them."""
+    return int(_lib.load().anyv2v_groupnorm_scratch_floats(int(M), int(rows_per_group), int(groups)))
+
+
+def _gn_operands(x0, x1, out):
+    """(M, C0, C1, out) of a GroupNorm call over [x0 | x1]: the operand checks, and the output where none was handed over."""
+    _rowmajor(x0, "X0")
+    assert x0.is_contiguous()
+    M, C0 = x0.shape
+    C1 = 0
+    if x1 is not None:
+        _rowmajor(x1, "X1")
+        assert x1.is_contiguous() and x1.shape[0] == M
+        C1 = x1.shape[1]
+    if out is None:
+        out = torch.empty((M, C0 + C1), dtype=torch.float16, device=x0.device)
+    assert out.is_contiguous()
+    return M, C0, C1, out
 
 
 def groupnorm(x0: torch.Tensor, gamma, beta, stats: torch.Tensor, rows_per_group: int, *, x1=None, groups: int = 32,
@@ -269,17 +287,7 @@ def groupnorm(x0: torch.Tensor, gamma, beta, stats: torch.Tensor, rows_per_group
     if shard is not None:
         return _groupnorm_sharded(x0, gamma, beta, stats, rows_per_group, x1, groups, eps, silu, out, shard)
     lib = _lib.load()
-    _rowmajor(x0, "X0")
-    assert x0.is_contiguous()
-    M, C0 = x0.shape
-    C1 = 0
-    if x1 is not None:
-        _rowmajor(x1, "X1")
-        assert x1.is_contiguous() and x1.shape[0] == M
-        C1 = x1.shape[1]
-    if out is None:
-        out = torch.empty((M, C0 + C1), dtype=torch.float16, device=x0.device)
-    assert out.is_contiguous()
+    M, C0, C1, out = _gn_operands(x0, x1, out)
     need = gn_scratch_floats(M, rows_per_group, groups)
     assert stats.dtype == torch.float32 and stats.numel() >= need, "GroupNorm scratch too small"
     _lib.check(lib.anyv2v_groupnorm_f16(_p(x0), _p(x1), C0, C1, _p(out), _p(gamma), _p(beta), _p(stats), M,
@@ -290,21 +298,11 @@ def groupnorm(x0: torch.Tensor, gamma, beta, stats: torch.Tensor, rows_per_group
 def _groupnorm_sharded(x0, gamma, beta, stats, rows_per_group, x1, groups, eps, silu, out, shard):
     lib = _lib.load()
     shards, all_reduce_sum = shard
-    _rowmajor(x0, "X0")
-    assert x0.is_contiguous()
-    M, C0 = x0.shape
-    C1 = 0
-    if x1 is not None:
-        _rowmajor(x1, "X1")
-        assert x1.is_contiguous() and x1.shape[0] == M
-        C1 = x1.shape[1]
-    if out is None:
-        out = torch.empty((M, C0 + C1), dtype=torch.float16, device=x0.device)
-    assert out.is_contiguous()
+    M, C0, C1, out = _gn_operands(x0, x1, out)
     n = int(lib.anyv2v_groupnorm_partial_floats(M, rows_per_group, groups, C0 + C1))
     npiv = (M // rows_per_group) * groups
     assert n > 0 and stats.dtype == torch.float32 and stats.numel() >= n + npiv, "GroupNorm scratch too small"
-    piv = stats[n:n + npiv]   # behind the partial sums (a gn_scratch_floats() buffer always has room for both)
+    piv = stats[n:n + npiv]   # behind the partial sums (a gn_scratch_floats() buffer has room for both: tests/test_norm_plan_host.py)
     _lib.check(lib.anyv2v_groupnorm_pivot_f16(_p(x0), _p(x1), C0, C1, _p(piv), M, rows_per_group, groups, int(shards), _stream()),
                "anyv2v_groupnorm_pivot_f16")
     all_reduce_sum(piv)

@@ -1008,22 +1008,27 @@ def _skip_row(name, why):
     return dict(name=f"{name}: SKIPPED ({why})", err=0.0, l2=0.0, tol=0.0, ok=True, skipped=True)
 
 
+# (C0, C1, rows_per_group, nsg, G, silu); tests/test_norm_plan_host.py pins the plan of each on the CPU
+GN_PLAN_EDGE_CASES = [
+    (320, 0, 4099, 2, 32, True),        # 86 chunks of 48 rows, rpb = 6: neither divides 4099
+    (640, 0, 1021, 3, 32, False),       # a prime row count, rpb = 3
+    (320, 0, 65536 + 37, 1, 32, True),  # the 256-chunk cap, ragged last chunk
+    (1280, 640, 12289, 2, 32, True),    # two sources, chunked by the cap (251 chunks of 49 rows)
+    (2560, 0, 2053, 2, 32, False),      # V = 320: one row per block
+    (2560, 0, 1024, 2, 32, True),
+    (8, 0, 3001, 2, 4, True),           # C = 8: one vector per row, 256 rows per block
+    (8, 0, 70001, 1, 8, False),
+]
+GN_PLAN_HINT_CASE = (8, 16 * 1024, 320)   # (nsg, rows_per_group, C): 191 chunks; hinted as 12 groups: 128 chunks
+
+
 def check_groupnorm_plan_edges():
     """The launch plan's edges: rows_per_group that is not a multiple of the rows per block or of the chunk size, the 256-chunk
     cap, the same tensor under ``batch_hint(3, 2)`` (another chunk count: within KTOL and bit-reproducible call to call),
     C = 2560 (one row per block), C = 8; every call writes nothing outside its output rows nor past the stats scratch."""
     out = []
     TAIL = 4096
-    cases = [  # (C0, C1, rows_per_group, nsg, G, silu)
-        (320, 0, 4099, 2, 32, True),        # 86 chunks of 48 rows, rpb = 6: neither divides 4099
-        (640, 0, 1021, 3, 32, False),       # a prime row count, rpb = 3
-        (320, 0, 65536 + 37, 1, 32, True),  # the 256-chunk cap, ragged last chunk
-        (1280, 640, 12289, 2, 32, True),    # two sources at the cap
-        (2560, 0, 2053, 2, 32, False),      # V = 320: one row per block
-        (2560, 0, 1024, 2, 32, True),
-        (8, 0, 3001, 2, 4, True),           # C = 8: one vector per row, 256 rows per block
-        (8, 0, 70001, 1, 8, False),
-    ]
+    cases = GN_PLAN_EDGE_CASES
     for C0, C1, rpg, nsg, G, silu in cases:
         C, M = C0 + C1, nsg * rpg
         x = _offset_data(nsg, rpg, C, G, 3, seed=rpg)
@@ -1038,8 +1043,8 @@ def check_groupnorm_plan_edges():
         out.append(_res(name, y, ref, KTOL))
         out.append(dict(name=name + ": output guard rows and stats tail untouched", err=0.0, tol=0.0,
                         ok=_guard_intact(buf, M, guard) and bool((stats[need:] == -1234.5).all())))
-    # batch hint: 8 groups of 16 x 1024 rows -> 192 chunks; hinted as 12 groups -> 128 chunks
-    nsg, rpg, C = 8, 16 * 1024, 320
+    # batch hint: 8 groups of 16 x 1024 rows -> 191 chunks (of 86 rows: a target of 192); hinted as 12 groups -> 128 chunks
+    nsg, rpg, C = GN_PLAN_HINT_CASE
     x = _offset_data(nsg, rpg, C, 32, 50, seed=99)
     ga, be = _affine(C, 41)
     ref = _gn_ref64(x, None, ga, be, rpg, 32, 1e-5, True)
@@ -1050,6 +1055,36 @@ def check_groupnorm_plan_edges():
     out.append(_res("groupnorm 8 x 16384 rows, offset 50 sigma: plain", plain, ref, KTOL))
     out.append(_res("groupnorm 8 x 16384 rows, offset 50 sigma: under batch_hint(3, 2)", h1, ref, KTOL))
     out.append(dict(name="groupnorm under batch_hint(3, 2): bit-reproducible call to call", err=0.0, tol=0.0, ok=bool(torch.equal(h1, h2))))
+    return out
+
+
+def check_groupnorm_from_records_ragged():
+    """``groupnorm_from_stats`` on hand-built records at the edges of the run folding: 256 records per statistics group (no fold), 257
+    (runs of 2, the last run one record), 513 (171 full runs of 3), 514 (runs of 3, the last run one record).  Records as a GEMM
+    writes them: per 16 rows and channel group (K, s, q) about K = the block's first row, the group's first channel; computed in
+    float64, rounded to fp32.  Group offsets of 3 sigma make the pivots differ.  Nothing is written past ``gn_stats_floats``."""
+    out = []
+    C, G, nsg, TAIL = 64, 32, 2, 4096
+    cpg = C // G
+    ga, be = _affine(C, 71)
+    for nrec in (256, 257, 513, 514):
+        rpg = 16 * nrec
+        M = nsg * rpg
+        x = _offset_data(nsg, rpg, C, G, 3, seed=nrec)
+        xb = x.double().view(nsg, nrec, 16, G, cpg)
+        K = xb[:, :, 0, :, 0]
+        d = xb - K[:, :, None, :, None]
+        records = torch.stack([K, d.sum((2, 4)), d.square().sum((2, 4))], -1).float()    # [nsg][nrec][G][3]
+        need = ops.gn_stats_floats(M, rpg, G)
+        stats = torch.full((need + TAIL,), -1234.5, dtype=torch.float32, device=DEV)
+        stats[:records.numel()] = records.reshape(-1)
+        buf, y, guard = _guarded(M, C)
+        ops.groupnorm_from_stats(x, ga, be, stats, rpg, groups=G, eps=1e-5, silu=True, out=y)
+        name = f"groupnorm from {nrec} hand-built records x {nsg} groups"
+        out.append(_res(name, y, _gn_ref64(x, None, ga, be, rpg, G, 1e-5, True), KTOL))
+        out.append(dict(name=name + ": output guard rows and stats tail untouched", err=0.0, tol=0.0,
+                        ok=_guard_intact(buf, M, guard) and bool((stats[need:] == -1234.5).all())
+                        and bool(torch.equal(stats[:records.numel()], records.reshape(-1)))))
     return out
 
 

@@ -103,6 +103,10 @@ def test_groupnorm_plan_edges_and_write_guards():
     _assert_all(gc.check_groupnorm_plan_edges())
 
 
+def test_groupnorm_from_hand_built_records_with_a_ragged_last_run():
+    _assert_all(gc.check_groupnorm_from_records_ragged())
+
+
 def test_groupnorm_sharded_with_offsets():
     _assert_all(gc.check_groupnorm_sharded_offsets())
 
