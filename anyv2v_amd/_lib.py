@@ -75,6 +75,9 @@ DIFF_MAP_BLOCKS, DIFF_MAP_THREADS = 64, 256
 COMPOSITE_MAX_GROW, COMPOSITE_MAX_RADIUS, COMPOSITE_STATS_BLOCKS, COMPOSITE_STATS_RECORD = 64, 48, 256, 16
 # anyv2v_block_match_u8: the largest search radius (ANYV2V_TRACK_MAX_RADIUS of include/anyv2v_hip.h)
 TRACK_MAX_RADIUS = 32
+# anyv2v_resample_table: the filters (Pillow's Image.Resampling numbers) and the largest side (ANYV2V_RESAMPLE_* of include/anyv2v_hip.h)
+RESAMPLE_FILTERS = {"lanczos": 1, "bilinear": 2, "bicubic": 3, "box": 4}
+RESAMPLE_MAX_SIDE = 16384
 
 
 class FFDesc(C.Structure):
@@ -145,6 +148,9 @@ SYMBOLS = {
     "anyv2v_flow_median_i16": (C.c_int, [_VP, _VP, _I32, _I32, _I32, _VP]),
     "anyv2v_mask_propagate_u8": (C.c_int, [_VP, _VP, _VP, _I32, _I32, _I32, _VP]),
     "anyv2v_first_frame_mask_u8": (C.c_int, [_VP, _VP, _VP, _I32, _I32, _I32, _I32, _VP]),
+    "anyv2v_resample_table": (C.c_int, [C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "anyv2v_resample_h_u8": (C.c_int, [_VP, _VP, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _VP, _VP, _I32, _VP]),
+    "anyv2v_resample_v_u8": (C.c_int, [_VP, _VP, _I32, _I32, _I32, _I32, _I32, _VP, _VP, _I32, _VP]),
     "anyv2v_ddim_step_f16": (C.c_int, [_VP, _VP, _VP, _F32, _F32, _F32, _F32, _I64, _VP]),
     "anyv2v_guided_step_f16": (C.c_int, [_VP, _I64, _I32, _I32, _I32, _F32, _F32, _I32, _F32, _F32, _F32, _F32, _VP, _VP, _VP]),
     "anyv2v_guided_step_noise_f16": (C.c_int, [_VP, _I64, _I32, _I32, _I32, _F32, _F32, _I32, _F32, _F32, _F32, _F32, _VP, _VP, _VP, _F32, _VP]),
@@ -168,7 +174,11 @@ def load():
             f"Build with `make -C {os.path.join(_HERE, 'csrc')}` (or `python -c 'import __graft_entry__ as g; g.build()'`).")
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in SYMBOLS.items():
-        fn = getattr(lib, name)  # AttributeError if the .so is stale
+        try:
+            fn = getattr(lib, name)
+        except AttributeError:   # a library built before the symbol existed (entry points are added without an ABI step)
+            raise HipExtensionMissing(f"{LIB_PATH} has no symbol {name}: it is older than this binding, rebuild it "
+                                      f"(`make -C {os.path.join(_HERE, 'csrc')}`)") from None
         fn.restype = res
         fn.argtypes = args
     if lib.anyv2v_version() < ABI_VERSION:   # descriptors carry no size field: a stale library would read past a shorter struct

@@ -25,6 +25,7 @@ from .masked_edit import finish_frames, make_edit_mask, masked, plan_from_config
 from .pipeline import I2VGenXLPipeline
 from .run_group_ddim_inversion import ddim_inversion
 from .pnp_utils import clear_time
+from .prepare import plan_from_config as prepare_plan_from_config
 from .run_group_pnp_edit import init_pnp
 from .schedulers import DDIMInverseScheduler, DDIMScheduler
 from .utils import export_to_video, load_image, wait_for_pending_writes
@@ -51,6 +52,7 @@ class AnyV2V_I2VGenXL:
     def __init__(self, model_path: str = MODEL_ID, device="cuda:0", tmp_dir: str = "_demo_temp", pipe: Optional[I2VGenXLPipeline] = None,
                  random_init_seed: Optional[int] = None, synthetic_encoders: bool = False) -> None:
         # default inversion / edit configuration of the demo (gradio_demo.py:60-78); ``pnp_config`` also takes the optional keys
+        # (``inverse_config`` takes the optional ``source_*`` keys of ``prepare.plan_from_config``: a source clip of any size)
         # ``eta`` / ``guidance_rescale`` (``config.sampler_options``; e.g. ``obj.config.pnp_config.eta = 0.5``) and the ``edit_mask_*`` keys of
         # ``masked_edit.plan_from_config`` whose mask needs no file: ``edit_mask_auto`` or ``edit_mask_first_frame`` (where the edited first
         # frame differs from the source's -- a local edit with no extra input) with their tuning keys, ``edit_mask_grow`` /
@@ -94,6 +96,12 @@ class AnyV2V_I2VGenXL:
         ddim_latents_path = os.path.join(tmp_dir, "ddim_latents")
         frame_list = read_frames(str(video_path))
         cfg = self.config
+        # optional keys ``source_fit`` / ``source_x_offset`` / ``source_y_offset`` / ``source_resample`` and ``source_size: [w, h]`` (default
+        # 512 x 512) of ``inverse_config`` (``prepare.plan_from_config``): a clip of any size is cropped and resized on the GPU first;
+        # absent, the clip runs at the size its frames have
+        source_plan = prepare_plan_from_config(cfg.inverse_config)
+        if source_plan is not None:
+            _, frame_list = source_plan.frames(self.pipe, frame_list, source_plan.source_size or (512, 512))
         cfg.inverse_config.image_size = list(frame_list[0].size)
         self.pipe.auto_vae_tiling(cfg.inverse_config.image_size[1], cfg.inverse_config.image_size[0])   # frames over one VAE tile
         cfg.inverse_config.n_steps = ddim_inversion_steps

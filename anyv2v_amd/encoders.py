@@ -56,6 +56,17 @@ def _pil_batch_to_device(frames: List[Image.Image], device) -> torch.Tensor:
     return _U8_LUT.to(device)[u8.to(device).long()].permute(0, 3, 1, 2).contiguous()
 
 
+def _u8_video_to_device(video: torch.Tensor, device, height, width) -> torch.Tensor:
+    """Frames that are already a uint8 [F, height, width, 3] tensor (``I2VGenXLPipeline.prepare_frames``), wherever they live -> what
+    ``_pil_batch_to_device`` makes of the same frames as PIL images (at the working size its centre crop changes nothing)."""
+    global _U8_LUT
+    if video.dtype != torch.uint8 or video.dim() != 4 or tuple(video.shape[1:]) != (height, width, 3):
+        raise ValueError(f"encode_video: a uint8 [F, {height}, {width}, 3] tensor expected, got {tuple(video.shape)} {video.dtype}")
+    if _U8_LUT is None:
+        _U8_LUT = torch.from_numpy(np.arange(256, dtype=np.float32) / 255.0) * 2.0 - 1.0
+    return _U8_LUT.to(device)[video.to(device).long()].permute(0, 3, 1, 2).contiguous()
+
+
 class SyntheticVAE:
     """8x area-pool + fixed orthogonal-ish 3->4 channel mix (and its pseudo-inverse for decoding).  Weight-free
     stand-in with the SD-VAE's shapes / scaling factor; deterministic (the real VAE *samples* its posterior with the
@@ -82,7 +93,10 @@ class SyntheticVAE:
         return self._enc(x).to(device=device, dtype=torch.float16)
 
     def encode_video(self, video: List[Image.Image], device, height, width):
-        lat = torch.cat([self._enc(_pil_to_tensor(_center_crop_wide(f, (width, height)))) for f in video])  # [F,4,h,w]
+        if isinstance(video, torch.Tensor):
+            lat = self._enc(_u8_video_to_device(video, "cpu", height, width))
+        else:
+            lat = torch.cat([self._enc(_pil_to_tensor(_center_crop_wide(f, (width, height)))) for f in video])  # [F,4,h,w]
         return lat.permute(1, 0, 2, 3)[None].to(device=device, dtype=torch.float16)
 
     def decode_video(self, latents, decode_chunk_size=None):
@@ -151,7 +165,10 @@ class NativeVAE:
         return self._encode(x, device).to(torch.float16)
 
     def encode_video(self, video: List[Image.Image], device, height, width):
-        x = _pil_batch_to_device([_center_crop_wide(f, (width, height)) for f in video], device)  # [F,3,H,W]
+        if isinstance(video, torch.Tensor):
+            x = _u8_video_to_device(video, device, height, width)
+        else:
+            x = _pil_batch_to_device([_center_crop_wide(f, (width, height)) for f in video], device)  # [F,3,H,W]
         return self._encode(x, device).permute(1, 0, 2, 3)[None].to(torch.float16)
 
     def decode_video(self, latents, decode_chunk_size=None):

@@ -786,6 +786,113 @@ def first_frame_mask(source: torch.Tensor, edited: torch.Tensor, threshold: int 
     return out.view(torch.bool)
 
 
+_RESAMPLE_TABLES = {}   # (in_size, in0, in1, out_size, filter) -> (ksize, bounds, coeffs) on the host
+_RESAMPLE_DEVICE = {}   # (pass geometry, device) -> the pass with its tables on the device
+
+
+def resample_table(in_size: int, in0: float, in1: float, out_size: int, resample: str = "lanczos"):
+    """The table of one side as ``anyv2v_resample_table`` builds it (host code, no GPU) -> ``(ksize, bounds int32 [out_size, 2],
+    coeffs int32 [out_size, ksize])`` on the CPU, cached per geometry.  ``ValueError`` for what the planner refuses."""
+    if resample not in _lib.RESAMPLE_FILTERS:
+        raise ValueError(f"resample={resample!r}: one of {sorted(_lib.RESAMPLE_FILTERS)} ('nearest' is not a resampling filter of this kind)")
+    key = (int(in_size), float(in0), float(in1), int(out_size), resample)
+    if key not in _RESAMPLE_TABLES:
+        lib = _lib.load()
+        args = key[:4] + (_lib.RESAMPLE_FILTERS[resample],)
+        ksize = lib.anyv2v_resample_table(*args, None, None)
+        if ksize > 0:
+            bounds = torch.empty((key[3], 2), dtype=torch.int32)
+            coeffs = torch.empty((key[3], ksize), dtype=torch.int32)
+            ptr = C.POINTER(C.c_int)
+            ksize = lib.anyv2v_resample_table(*args, C.cast(bounds.data_ptr(), ptr), C.cast(coeffs.data_ptr(), ptr))
+        if ksize <= 0:
+            msg = lib.anyv2v_last_error()
+            raise ValueError(f"resample_u8: {msg.decode() if msg else 'the table was refused'}")
+        if len(_RESAMPLE_TABLES) >= 64:
+            _RESAMPLE_TABLES.clear()
+        _RESAMPLE_TABLES[key] = (ksize, bounds, coeffs)
+    return _RESAMPLE_TABLES[key]
+
+
+def resample_passes(H: int, W: int, size, resample: str = "lanczos", box=None, window=None):
+    """What ``resample_u8`` launches for frames of H x W: ``(window, row0, rows, h, v)``.  ``h`` / ``v``: ``None`` where Pillow skips the
+    pass (that side's size unchanged and its box the whole side), else ``(ksize, bounds, coeffs)`` cut to the window's outputs, on the
+    CPU.  The horizontal pass (or the copy in its place) covers the input rows [row0, row0 + rows) that the vertical pass reads -- its
+    bounds count from row0 --, as in Pillow."""
+    try:
+        out_w, out_h = (int(v) for v in size)
+        ok = (out_w, out_h) == tuple(size)
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f"size={size!r}: (out_w, out_h), two integers")
+    try:
+        x0, y0, x1, y1 = (float(v) for v in ((0, 0, W, H) if box is None else box))
+    except (TypeError, ValueError):
+        raise ValueError(f"box={box!r}: (x0, y0, x1, y1) in source pixels") from None
+    try:
+        wx, wy, ww, wh = (int(v) for v in ((0, 0, out_w, out_h) if window is None else window))
+        ok = window is None or (wx, wy, ww, wh) == tuple(window)
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f"window={window!r}: (wx, wy, ww, wh), four integers")
+    need_h = out_w != W or x0 != 0.0 or x1 != float(W)
+    need_v = out_h != H or y0 != 0.0 or y1 != float(H)
+    # the tables first: a bad size or box is the planner's to refuse
+    th = resample_table(W, x0, x1, out_w, resample) if need_h else None
+    tv = resample_table(H, y0, y1, out_h, resample) if need_v else None
+    if not (0 <= wx and 0 <= wy and ww >= 1 and wh >= 1 and wx + ww <= out_w and wy + wh <= out_h):
+        raise ValueError(f"window={window!r} does not lie inside size={tuple(size)!r}")
+    h = v = None
+    row0, rows = wy, wh
+    if need_v:
+        bounds = tv[1][wy:wy + wh].clone()
+        row0 = int(bounds[0, 0])
+        rows = int(bounds[-1, 0] + bounds[-1, 1]) - row0
+        bounds[:, 0] -= row0
+        v = (tv[0], bounds, tv[2][wy:wy + wh].contiguous())
+    if need_h:
+        h = (th[0], th[1][wx:wx + ww].contiguous(), th[2][wx:wx + ww].contiguous())
+    return (wx, wy, ww, wh), row0, rows, h, v
+
+
+def resample_u8(frames: torch.Tensor, size, resample: str = "lanczos", box=None, window=None):
+    """Pillow's ``Image.resize(size, resample, box)`` of every frame, byte for byte, and optionally only the rectangle ``window`` of it
+    (equal to ``.crop`` of the whole): contiguous uint8 [F, H, W, C] on the GPU, C = 1 or 3 -> uint8 [F, wh, ww, C].  ``size = (out_w,
+    out_h)``; ``resample``: lanczos, bicubic, bilinear or box; ``box = (x0, y0, x1, y1)`` floats in source pixels (default: the frame);
+    ``window = (wx, wy, ww, wh)`` integers in output pixels (default: all of it).  Two launches (``anyv2v_resample_h_u8``,
+    ``anyv2v_resample_v_u8``; the definition is in ``include/anyv2v_hip.h``), one where Pillow skips a pass, a copy where it skips both."""
+    if not (isinstance(frames, torch.Tensor) and frames.dtype == torch.uint8 and frames.dim() == 4 and frames.is_contiguous() and frames.is_cuda
+            and frames.shape[0] >= 1 and frames.shape[3] in (1, 3)):
+        got = f"{tuple(frames.shape)} {frames.dtype} on {frames.device}" if isinstance(frames, torch.Tensor) else type(frames).__name__
+        raise ValueError(f"resample_u8: a contiguous uint8 [F, H, W, C] tensor on the GPU with C = 1 or 3 expected, got {got}")
+    F, H, W, Cc = (int(v) for v in frames.shape)
+    key = (H, W, tuple(size) if isinstance(size, (tuple, list)) else size, resample, None if box is None else tuple(box),
+           None if window is None else tuple(window), str(frames.device))
+    if key not in _RESAMPLE_DEVICE:
+        win, row0, rows, h, v = resample_passes(H, W, size, resample, box, window)
+        if len(_RESAMPLE_DEVICE) >= 64:
+            _RESAMPLE_DEVICE.clear()
+        _RESAMPLE_DEVICE[key] = (win, row0, rows) + tuple(None if p is None else (p[0], p[1].to(frames.device), p[2].to(frames.device))
+                                                          for p in (h, v))
+    (wx, wy, ww, wh), row0, rows, h, v = _RESAMPLE_DEVICE[key]
+    lib = _lib.load()
+    if h is None:
+        x = frames[:, row0:row0 + rows, wx:wx + ww].contiguous()
+        if v is None and x.data_ptr() == frames.data_ptr():
+            x = x.clone()
+    else:
+        x = torch.empty((F, rows, ww, Cc), dtype=torch.uint8, device=frames.device)
+        _lib.check(lib.anyv2v_resample_h_u8(_p(frames), _p(x), F, H, W, Cc, row0, rows, ww, _p(h[1]), _p(h[2]), h[0], _stream()),
+                   "anyv2v_resample_h_u8")
+    if v is None:
+        return x
+    out = torch.empty((F, wh, ww, Cc), dtype=torch.uint8, device=frames.device)
+    _lib.check(lib.anyv2v_resample_v_u8(_p(x), _p(out), F, rows, ww, Cc, wh, _p(v[1]), _p(v[2]), v[0], _stream()), "anyv2v_resample_v_u8")
+    return out
+
+
 def ddim_step(v: torch.Tensor, x: torch.Tensor, sa_t: float, sb_t: float, sa_p: float, sb_p: float, out=None):
     lib = _lib.load()
     v = v.to(torch.float16).contiguous()

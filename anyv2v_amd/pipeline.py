@@ -295,6 +295,19 @@ class I2VGenXLPipeline(MaskedEditMixin):
         if self.source_cache is not None:
             self.source_cache.bind(None)   # recorded source features were computed under the other setting
 
+    def prepare_frames(self, frames, height, width, fit="crop", x_offset=0.0, y_offset=0.0, resample="lanczos"):
+        """Source frames of any one size (a list of PIL images or a uint8 [F, H, W, 3] tensor) -> uint8 [F, height, width, 3] on this
+        pipeline's device: cover-resize and crop (``fit="crop"``, offsets in [-1, 1]) or plain resize (``"stretch"``), Pillow's
+        ``resize(...).crop(...)`` byte for byte (``anyv2v_amd.prepare``).  ``encode_vae_video`` takes the result as it is."""
+        from . import prepare
+        return prepare.prepare_frames(frames, height, width, fit, x_offset, y_offset, resample, device=self._execution_device)
+
+    def prepare_mask(self, mask, height, width, fit="crop", x_offset=0.0, y_offset=0.0):
+        """An edit mask at the source frames' size, [1 or F, H, W] -> uint8 0 / 255 [1 or F, height, width] through the same geometry
+        (``anyv2v_amd.prepare.prepare_mask``)."""
+        from . import prepare
+        return prepare.prepare_mask(mask, height, width, fit, x_offset, y_offset, device=self._execution_device)
+
     def encode_vae_video(self, video, device, height=576, width=1024):
         vae = self._need("vae")
         return vae.encode_video(video, device, height, width)

@@ -22,6 +22,8 @@ from .config import OmegaConf
 from .encoders import attach_synthetic_encoders
 from .parallel import FrameParallel, init_distributed, seed_for_entry, shard_entries
 from .pipeline import I2VGenXLPipeline
+from .prepare import load_source_clip, save_frames
+from .prepare import plan_from_config as prepare_plan_from_config
 from .schedulers import DDIMInverseScheduler, DDIMScheduler
 from .utils import (convert_video_to_frames, export_to_gif, export_to_video, inversion_is_complete, load_ddim_latents_at_t, load_video_frames,
                     seed_everything)
@@ -138,15 +140,25 @@ class Stage1:
             logger.info(f"### Skipping !!! {config.output_dir} already exists. ")
             return None
         logger.info(f"config: {OmegaConf.to_yaml(config)}")
-        try:
-            logger.info(f"Loading frames from: {config.video_frames_path}")
-            _, frame_list = load_video_frames(config.video_frames_path, config.n_frames, tuple(config.image_size))
-        except Exception:
-            logger.error(f"Failed to load frames from: {config.video_frames_path}")
-            logger.info(f"Converting mp4 video to frames: {config.video_path}")
-            frame_list = convert_video_to_frames(config.video_path, tuple(config.image_size), save_frames=True)
-            frame_list = frame_list[: config.n_frames]
-            export_to_gif(frame_list, os.path.join(config.video_frames_path, config.video_name + ".gif"))
+        source_plan = prepare_plan_from_config(config)   # optional keys ``source_*``; absent: None, and the frames must have the working size
+        if source_plan is not None:
+            # frames of any size, cropped and resized on the GPU (``anyv2v_amd.prepare``); what the model sees is written beside the
+            # latents, and frame 0 of it is the frame to edit.  (Frame-parallel: every rank prepares the clip, the bytes are the same.)
+            logger.info(f"Preparing frames from: {config.video_frames_path} ({source_plan})")
+            source = load_source_clip(config.video_frames_path, config.video_path, config.n_frames)
+            _, frame_list = source_plan.frames(self.pipe, source, tuple(config.image_size))
+            if self.writer:
+                save_frames(frame_list, os.path.join(config.output_dir, "prepared_frames"))
+        else:
+            try:
+                logger.info(f"Loading frames from: {config.video_frames_path}")
+                _, frame_list = load_video_frames(config.video_frames_path, config.n_frames, tuple(config.image_size))
+            except Exception:
+                logger.error(f"Failed to load frames from: {config.video_frames_path}")
+                logger.info(f"Converting mp4 video to frames: {config.video_path}")
+                frame_list = convert_video_to_frames(config.video_path, tuple(config.image_size), save_frames=True)
+                frame_list = frame_list[: config.n_frames]
+                export_to_gif(frame_list, os.path.join(config.video_frames_path, config.video_name + ".gif"))
         first_frame = frame_list[0]
         if config.inverse_config.inverse_static_video:
             logger.info("### Inverse a static video!")

@@ -24,6 +24,8 @@ from .encoders import attach_synthetic_encoders
 from .masked_edit import finish_frames, make_edit_mask, masked, plan_from_config
 from .parallel import FrameParallel, gather_latents, init_distributed, seed_for_entry, shard_entries
 from .pipeline import I2VGenXLPipeline
+from .prepare import load_source_clip, load_source_mask
+from .prepare import plan_from_config as prepare_plan_from_config
 from .pnp_utils import clear_time, register_conv_injection, register_spatial_attention_pnp, register_temp_attention_pnp
 from .schedulers import DDIMScheduler
 from .utils import (LatentTrajectory, convert_video_to_frames, export_to_gif, export_to_video, load_ddim_latents_at_t, load_edit_mask,
@@ -125,13 +127,19 @@ class Stage2:
         for k, v in config.items():  # logs only -- the reference's `continue` continues this inner loop (:89-93)
             if "ReplaceMe" in str(v):
                 logger.error(f"Field {k} contains 'ReplaceMe'")
-        try:
-            logger.info(f"Loading frames from: {config.video_frames_path}")
-            _, frame_list = load_video_frames(config.video_frames_path, config.n_frames, tuple(config.image_size))
-        except Exception:
-            logger.error(f"Failed to load frames from: {config.video_frames_path}")
-            frame_list = convert_video_to_frames(config.video_path, tuple(config.image_size), save_frames=True)
-            frame_list = frame_list[: config.n_frames]
+        source_plan = prepare_plan_from_config(config)   # optional keys ``source_*``; absent: None, and the frames must have the working size
+        if source_plan is not None:   # the same frames the inversion prepared (``anyv2v_amd.prepare``: the bytes are a function of the files)
+            logger.info(f"Preparing frames from: {config.video_frames_path} ({source_plan})")
+            source = load_source_clip(config.video_frames_path, config.video_path, config.n_frames)
+            _, frame_list = source_plan.frames(pipe, source, tuple(config.image_size))
+        else:
+            try:
+                logger.info(f"Loading frames from: {config.video_frames_path}")
+                _, frame_list = load_video_frames(config.video_frames_path, config.n_frames, tuple(config.image_size))
+            except Exception:
+                logger.error(f"Failed to load frames from: {config.video_frames_path}")
+                frame_list = convert_video_to_frames(config.video_path, tuple(config.image_size), save_frames=True)
+                frame_list = frame_list[: config.n_frames]
         src_1st_frame = frame_list[0]
         edited_1st_frame = load_image(config.edited_first_frame_path)
         edited_1st_frame = edited_1st_frame.resize(tuple(config.image_size), resample=Image.Resampling.LANCZOS)
@@ -161,7 +169,11 @@ class Stage2:
             if plan.source == "path":
                 if plan.track is not None and os.path.isdir(os.path.join(config.data_dir, plan.path)):
                     raise ValueError(f"edit_mask_track with a directory of masks ({plan.path}): every frame already has its mask")
-                loaded = load_edit_mask(os.path.join(config.data_dir, plan.path), config.n_frames, tuple(config.image_size))
+                if source_plan is not None:   # a mask drawn on the source-size frames goes through the frames' geometry
+                    loaded = source_plan.mask(pipe, load_source_mask(os.path.join(config.data_dir, plan.path), config.n_frames),
+                                              tuple(config.image_size))
+                else:
+                    loaded = load_edit_mask(os.path.join(config.data_dir, plan.path), config.n_frames, tuple(config.image_size))
             seed_everything(template_config.seed)
             source_latents = pipe.encode_vae_video(frame_list, device=pipe._execution_device, height=config.image_size[1],
                                                    width=config.image_size[0])

@@ -505,6 +505,50 @@ int anyv2v_mask_propagate_u8(const void* mask0, const void* flow, void* out, int
 int anyv2v_first_frame_mask_u8(const void* source, const void* edited, void* mask, int32_t H, int32_t W, int32_t threshold,
                                int32_t min_count, void* stream);
 
+/* Resampling of 8-bit frames (resample_plan.cpp, resample.hip): Pillow's `Image.resize` for 8-bit bands (its ImagingResample), which
+ * works in fixed point, so every byte is defined and the kernels are tested bit for bit against Pillow itself.  Two separable passes,
+ * horizontal first, with a uint8 intermediate image; a pass is skipped when that side's output size equals its input size and its box
+ * is the whole side (the caller decides; each entry below is one pass).
+ *
+ * anyv2v_resample_table: the table of one side.  in_size pixels, box [in0, in1) in source pixels, out_size outputs, a filter with its
+ * `support`.  All of this in IEEE double, no fused multiply-add:
+ *   scale = (in1 - in0) / out_size;  fs = max(scale, 1.0);  sup = support * fs;  ss = 1.0 / fs;  ksize = (int)ceil(sup) * 2 + 1
+ * and for output xx
+ *   center = in0 + (xx + 0.5) * scale
+ *   xmin = max((int)(center - sup + 0.5), 0);   n = min((int)(center + sup + 0.5), in_size) - xmin
+ *   w[x] = filter((x + xmin - center + 0.5) * ss) for x < n;   ww = sum of w[x], left to right;   w[x] /= ww when ww != 0
+ *   k[x] = (int)(w[x] * 2^22 + 0.5) for w[x] >= 0, (int)(w[x] * 2^22 - 0.5) otherwise
+ * Filters (the numbers are Pillow's `Image.Resampling` values):
+ *   ANYV2V_RESAMPLE_BOX       support 0.5: 1 for -0.5 < x <= 0.5
+ *   ANYV2V_RESAMPLE_BILINEAR  support 1: 1 - |x|
+ *   ANYV2V_RESAMPLE_BICUBIC   support 2: Keys' kernel with a = -0.5, as ((a + 2) |x| - (a + 3)) |x| |x| + 1 below 1 and
+ *                             (((|x| - 5) |x| + 8) |x| - 4) a below 2
+ *   ANYV2V_RESAMPLE_LANCZOS   support 3: sinc(x) sinc(x / 3) for -3 <= x < 3, sinc(x) = sin(pi x) / (pi x), sinc(0) = 1
+ * Returns ksize.  With bounds == NULL or coeffs == NULL it only returns ksize; otherwise it fills bounds[out_size][2] = (xmin, n) and
+ * coeffs[out_size][ksize] = k, zero past n.  A negative status (text: anyv2v_last_error()) for sides outside 1 .. ANYV2V_RESAMPLE_MAX_SIDE,
+ * a box that is empty or not inside [0, in_size], an unknown filter, or a table with a row of sum |k[x]| >= 2 * 2^22: below that,
+ * 255 * sum |k| + 2^21 < 2^31 and the kernels' int32 accumulator cannot overflow.  Host code only, no GPU is touched.
+ *
+ * An output sample of either pass, per band:   acc = 2^21 + sum over x < n of in[xmin + x] * k[x]   (int32)
+ *                                              out = clamp(acc >> 22, 0, 255)                        (arithmetic shift)
+ *
+ * anyv2v_resample_h_u8: src uint8 [F, H, W, C] -> dst uint8 [F, rows, out_w, C], the horizontal pass over the input rows
+ * [row0, row0 + rows) only (the rows a following vertical pass reads).  anyv2v_resample_v_u8: src [F, H, W, C] -> dst [F, out_h, W, C].
+ * C is 1 or 3; bounds int32 [out][2] and coeffs int32 [out][ksize] are DEVICE copies of a table as anyv2v_resample_table writes it (4-byte
+ * aligned); a window of the output is a slice of the table's rows.  src and dst need no alignment and may not overlap.  A table entry
+ * that points outside the side is cut to it (no read leaves src).  Element offsets are 64-bit; F <= 65535.  No atomics, a fixed grid:
+ * every output byte is written once, by one thread. */
+#define ANYV2V_RESAMPLE_LANCZOS 1
+#define ANYV2V_RESAMPLE_BILINEAR 2
+#define ANYV2V_RESAMPLE_BICUBIC 3
+#define ANYV2V_RESAMPLE_BOX 4
+#define ANYV2V_RESAMPLE_MAX_SIDE 16384
+int anyv2v_resample_table(int in_size, double in0, double in1, int out_size, int filter, int* bounds, int* coeffs);
+int anyv2v_resample_h_u8(const void* src, void* dst, int32_t F, int32_t H, int32_t W, int32_t C, int32_t row0, int32_t rows, int32_t out_w,
+                         const int32_t* bounds, const int32_t* coeffs, int32_t ksize, void* stream);
+int anyv2v_resample_v_u8(const void* src, void* dst, int32_t F, int32_t H, int32_t W, int32_t C, int32_t out_h, const int32_t* bounds,
+                         const int32_t* coeffs, int32_t ksize, void* stream);
+
 /* Plain elementwise DDIM / inverse-DDIM step (eta = 0, v-prediction) on same-layout tensors:
  * the generic `scheduler.step(model_output, t, sample).prev_sample` (pipeline_i2vgen_xl.py:868,1173,1418). */
 int anyv2v_ddim_step_f16(const void* V, const void* X, void* Y, float sa_t, float sb_t, float sa_p, float sb_p,
@@ -548,8 +592,9 @@ const char* anyv2v_last_error(void);
  * anyv2v_groupnorm_stats_floats, anyv2v_groupnorm_apply_stats_f16; nothing earlier changed (a 104 caller that zero-initialises its descriptors, as required,
  * must still be recompiled against this header because the structure grew).  anyv2v_freeu_f16, anyv2v_tile_blend_f16, anyv2v_latent_mask_f16,
  * anyv2v_masked_blend_f16, anyv2v_diff_map_accum_f16, anyv2v_diff_map_finish_f16, anyv2v_pixel_alpha_f16, anyv2v_composite_stats_u8,
- * anyv2v_composite_u8, anyv2v_luma_u8, anyv2v_block_match_u8, anyv2v_flow_median_i16, anyv2v_mask_propagate_u8 and
- * anyv2v_first_frame_mask_u8 were added under 105: new entry points, no structure changed
+ * anyv2v_composite_u8, anyv2v_luma_u8, anyv2v_block_match_u8, anyv2v_flow_median_i16, anyv2v_mask_propagate_u8,
+ * anyv2v_first_frame_mask_u8, anyv2v_resample_table, anyv2v_resample_h_u8 and anyv2v_resample_v_u8 were added under 105: new entry
+ * points, no structure changed
  * (a binding that needs them finds out when it resolves the symbol). */
 #define ANYV2V_ABI_VERSION 105
 int anyv2v_version(void);
