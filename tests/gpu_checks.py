@@ -1024,7 +1024,8 @@ GN_PLAN_HINT_CASE = (8, 16 * 1024, 320)   # (nsg, rows_per_group, C): 191 chunks
 
 def check_groupnorm_plan_edges():
     """The launch plan's edges: rows_per_group that is not a multiple of the rows per block or of the chunk size, the 256-chunk
-    cap, the same tensor under ``batch_hint(3, 2)`` (another chunk count: within KTOL and bit-reproducible call to call),
+    cap, the same tensor under ``batch_hint(3, 2)`` (another chunk count: within KTOL, bit-reproducible call to call, and bit-equal to
+    its rows of the 12-group launch it stands for),
     C = 2560 (one row per block), C = 8; every call writes nothing outside its output rows nor past the stats scratch."""
     out = []
     TAIL = 4096
@@ -1055,6 +1056,12 @@ def check_groupnorm_plan_edges():
     out.append(_res("groupnorm 8 x 16384 rows, offset 50 sigma: plain", plain, ref, KTOL))
     out.append(_res("groupnorm 8 x 16384 rows, offset 50 sigma: under batch_hint(3, 2)", h1, ref, KTOL))
     out.append(dict(name="groupnorm under batch_hint(3, 2): bit-reproducible call to call", err=0.0, tol=0.0, ok=bool(torch.equal(h1, h2))))
+    # ... and what the hint is for: the 8 groups are the last 8 of a 12-group launch, and their rows of that launch have the same bits
+    x12 = torch.cat([_offset_data(nsg // 2, rpg, C, 32, 50, seed=98), x], 0)
+    full = _gn_run(x12, None, ga, be, rpg, 32, 1e-5, True)
+    out.append(_res("groupnorm 12 x 16384 rows, offset 50 sigma: plain", full, _gn_ref64(x12, None, ga, be, rpg, 32, 1e-5, True), KTOL))
+    same = bool(torch.equal(h1, full[(nsg // 2) * rpg:]))
+    out.append(dict(name="groupnorm under batch_hint(3, 2) == rows [4 rpg, 12 rpg) of the 12-group launch, bit for bit", err=0.0 if same else 1.0, tol=0.0, ok=same))
     return out
 
 
@@ -5583,3 +5590,376 @@ def check_far_flat(which):
     del x, y
     torch.cuda.empty_cache()
     return rows
+
+
+# ------------------------------------------------------------------------------------------------ a branch subset under the batch hint
+# The invariant the source-feature cache and the two-branch replay engine rest on (ops.batch_hint): a launch on the last B - 1 of a
+# step's B branches, planned under batch_hint(B, B - 1), computes for its rows the BITS the launch on all B branches computes for them.
+# Cases: tests/batch_subset_spec.py (tests/test_batch_subset_host.py proves on the CPU that the hint is decisive for the `sharp` ones).
+# Rows of a case: the full launch against the reference of that kernel's existing check (KTOL: two equally wrong results do not pass);
+# hinted subset == the full launch's rows, bit for bit; and, informational, whether the subset WITHOUT the hint happens to coincide.
+def _bs_tail(full, r):
+    """The rows of the full launch's result (or record slice) that the subset launch stands for."""
+    return full[r:]
+
+
+def _bs_same(name, got, want):
+    same = bool(got.shape == want.shape and torch.equal(got, want))
+    err = 0.0
+    if not same:
+        err = float((got.float() - want.float()).abs().nan_to_num(nan=float("inf")).max()) if got.shape == want.shape else float("inf")
+        err = err or 1.0   # (-0.0 against 0.0, or NaN payloads: different bits, no distance)
+    return dict(name=name, err=err, l2=0.0, tol=0.0, ok=same)
+
+
+def _bs_info(name, got, want):
+    same = bool(got.shape == want.shape and torch.equal(got, want))
+    return dict(name=f"{name}: [info] subset WITHOUT the hint == full rows: {'yes (bits coincide)' if same else 'no (the hint is decisive)'}",
+                err=0.0, l2=0.0, tol=0.0, ok=True, informational=True, coincides=same)
+
+
+def _bs_rows(name, full, ref, tol, r, launch_subset, B, also=(), hint_free=False):
+    """``launch_subset()`` -> the subset's result (a tensor, or a tuple of tensors compared one by one with ``full``'s); ``r``: the first
+    row of the subset in each of them.  ``ref`` None: the caller adds the reference row.  ``hint_free``: the kernel's planner does not
+    read the hint, so the subset launched WITHOUT it must be bit-equal as well (a row, not a remark)."""
+    full = full if isinstance(full, tuple) else (full,)
+    with ops.batch_hint(B, B - 1):
+        sub = launch_subset()
+    plain = launch_subset()
+    torch.cuda.synchronize()
+    sub, plain = (sub if isinstance(sub, tuple) else (sub,)), (plain if isinstance(plain, tuple) else (plain,))
+    rows = [] if ref is None else [_res(f"{name}: full launch vs reference", full[0], ref, tol)]
+    for i, (f, s, p) in enumerate(zip(full, sub, plain)):
+        what = "output" if i == 0 else f"records / statistics {i}"
+        want = _bs_tail(f, r[i] if isinstance(r, tuple) else r)
+        rows.append(_bs_same(f"{name}: subset under batch_hint({B}, {B - 1}) == full rows, bit for bit ({what})", s, want))
+        if hint_free:
+            rows.append(_bs_same(f"{name}: subset WITHOUT the hint == full rows, bit for bit ({what})", p, want))
+        else:
+            rows.append(_bs_info(f"{name} ({what})", p, want))
+    return rows + list(also)
+
+
+def _bs_gemm_case(s, seed):
+    """(a0, w, kwargs of ops.gemm, fp32 reference) of one GEMM case of batch_subset_spec on T = B r rows."""
+    B, r, N, C0, C1, mode, act = s["B"], s["r"], s["N"], s["C0"], s["C1"], s["mode"], s["act"]
+    T, K = B * r, C0 + C1
+    if act == ops.ACT_GEGLU:
+        a, wp, bp, ref = _geglu_case(T, K, N // 2, seed=seed)
+        return a, wp, dict(bias=bp, act=act), ref
+    if s["ln"]:
+        x = (rnd(T, K, seed=seed).float() * 1.5 + 2.0).half()
+        gamma, beta = (1.0 + 0.3 * rnd(K, seed=seed + 1).float()).half(), (0.2 * rnd(K, seed=seed + 2).float()).half()
+        w, b = rnd(N, K, scale=1 / math.sqrt(K), seed=seed + 3), rnd(N, scale=0.1, seed=seed + 4)
+        wq, bq, c1 = ops.ln_fold(w, b, gamma, beta)
+        return x, wq, dict(bias=bq, ln=(c1, 1e-5)), F.layer_norm(x.float(), (K,), gamma.float(), beta.float(), 1e-5) @ w.float().t() + b.float()
+    a = rnd(T, K, seed=seed)
+    kw = dict(mode=mode)
+    if mode == ops.MODE_LINEAR:
+        w = rnd(N, K, scale=1 / math.sqrt(K), seed=seed + 1)
+        y = a.float() @ w.float().t()
+    elif mode == ops.MODE_CONV2D:
+        H, W = s["geo"]
+        w4 = rnd(N, K, 3, 3, scale=1 / math.sqrt(9 * K), seed=seed + 1)
+        w = _pack_conv(w4)
+        y = _to_tokens(F.conv2d(a.float().view(T // (H * W), H, W, K).permute(0, 3, 1, 2), w4.float(), padding=1))
+        kw["conv"] = (H, W, H, W, 1, 0)
+    else:
+        Fr, HW = s["geo"]
+        n = T // (Fr * HW)
+        wt = rnd(N, K, 3, scale=1 / math.sqrt(3 * K), seed=seed + 1)
+        w = wt.permute(0, 2, 1).reshape(N, 3 * K).contiguous()
+        y = F.conv1d(a.float().view(n, Fr, HW, K).permute(0, 2, 3, 1).reshape(n * HW, K, Fr), wt.float(), padding=1)
+        y = y.view(n, HW, N, Fr).permute(0, 3, 1, 2).reshape(T, N)
+        kw["temporal"] = (Fr, HW)
+    if "bias" in s["epi"]:
+        kw["bias"] = rnd(N, seed=seed + 2)
+        y = y + kw["bias"].float()
+    if "rowvec" in s["epi"]:
+        kw["rowvec"], kw["rowvec_div"] = rnd(B, N, seed=seed + 3), r
+        y = y + kw["rowvec"].float().repeat_interleave(r, 0)
+    if act:
+        kw["act"] = act
+        y = F.silu(y) if act == ops.ACT_SILU else F.gelu(y)
+    if "res" in s["epi"]:
+        kw["residual"] = rnd(T, N, seed=seed + 4)
+        y = y + kw["residual"].float()
+    a0, a1 = (a[:, :C0].contiguous(), a[:, C0:].contiguous()) if C1 else (a, None)
+    if a1 is not None:
+        kw["a1"] = a1
+    return a0, w, kw, y
+
+
+def _bs_gemm_subset_kw(kw, r):
+    k2 = dict(kw)
+    for key in ("residual", "a1"):
+        if k2.get(key) is not None:
+            k2[key] = k2[key][r:].contiguous()
+    if k2.get("rowvec") is not None:
+        k2["rowvec"] = k2["rowvec"][1:].contiguous()
+    return k2
+
+
+def check_subset_gemm(line):
+    """Every GEMM case of one table line of batch_subset_spec.GEMM_SPECS ("ln / ff" adds the fused feed-forward kernel)."""
+    import batch_subset_spec as bss
+    out = []
+    saved, saved_glds = ops.GEMM_FLAGS, ops.USE_GLDS
+    try:
+        ops.USE_GLDS = True
+        for idx, s in enumerate(bss.GEMM_SPECS):
+            if s["line"] != line:
+                continue
+            name = f"subset gemm[{s['line']}] {s['name']} r{s['r']} x {s['B']} N{s['N']} K{s['C0'] + s['C1']}"
+            if s["gpu_skip"]:
+                out.append(_skip_row(name, s["gpu_skip"]))
+                continue
+            ops.GEMM_FLAGS = ((saved & ~4) | s["flags"]) if s["flags"] else saved
+            a0, w, kw, ref = _bs_gemm_case(s, 1000 + 10 * idx)
+            r = s["r"]
+            full = ops.gemm(a0, w, **kw)
+            a0s, kws = a0[r:].contiguous(), _bs_gemm_subset_kw(kw, r)
+            out += _bs_rows(name, full, ref, KTOL, r, lambda: ops.gemm(a0s, w, **kws), s["B"])
+            del a0, w, kw, ref, full, a0s, kws
+        ops.GEMM_FLAGS = saved
+        if line == "ln / ff":
+            C, H = 320, 1280
+            B, r = bss.FF_SPEC["B"], bss.FF_SPEC["r"]
+            w1, b1 = rnd(2 * H, C, scale=1 / math.sqrt(C)), rnd(2 * H, scale=0.1)
+            w2, b2 = rnd(C, H, scale=1 / math.sqrt(H)), rnd(C, scale=0.1)
+            w1p, b1p = _geglu_pack(w1, b1, H)
+            w2s = ops.ff_pack_w2(w2)
+            x, res = rnd(B * r, C, seed=501), rnd(B * r, C, seed=502)
+            proj = x.float() @ w1.float().t() + b1.float()
+            hid = (proj[:, :H] * F.gelu(proj[:, H:])).half().float()
+            ref = (hid @ w2.float().t() + b2.float()).half().float() + res.float()
+            full = ops.ff_geglu(x, w1p, b1p, w2s, b2, residual=res)
+            xs, rs = x[r:].contiguous(), res[r:].contiguous()
+            out += _bs_rows(f"subset {bss.FF_SPEC['name']} r{r} x {B}", full, ref, KTOL, r, lambda: ops.ff_geglu(xs, w1p, b1p, w2s, b2, residual=rs), B)
+    finally:
+        ops.GEMM_FLAGS, ops.USE_GLDS = saved, saved_glds
+    return out
+
+
+def _bs_norm_data(s, seed):
+    import batch_subset_spec as bss
+    C, nsg = s["C0"] + s["C1"], s["per_branch"] * s["B"]
+    x = _offset_data(nsg, s["rpg"], C, 32, bss.NORM_OFFSET_SIGMA, seed=seed)
+    x0, x1 = (x[:, :s["C0"]].contiguous(), x[:, s["C0"]:].contiguous()) if s["C1"] else (x, None)
+    return x0, x1, _affine(C, seed + 1)
+
+
+def check_subset_groupnorm():
+    """``ops.groupnorm`` in one call: the chunk size follows the hinted group count (x0 only and x0 + x1, SiLU on and off, the (2, 1)
+    stem pair), on data 50 sigma off zero."""
+    import batch_subset_spec as bss
+    out = []
+    for i, s in enumerate(bss.NORM_SPECS):
+        x0, x1, (ga, be) = _bs_norm_data(s, 700 + 10 * i)
+        r = s["per_branch"] * s["rpg"]
+        full = _gn_run(x0, x1, ga, be, s["rpg"], 32, 1e-5, s["silu"])
+        ref = _gn_ref64(x0, x1, ga, be, s["rpg"], 32, 1e-5, s["silu"])
+        x0s, x1s = x0[r:].contiguous(), None if x1 is None else x1[r:].contiguous()
+        out += _bs_rows(f"subset {s['name']} rows/group {s['rpg']} x {s['per_branch'] * s['B']} silu={s['silu']}", full, ref, KTOL, r,
+                        lambda: _gn_run(x0s, x1s, ga, be, s["rpg"], 32, 1e-5, s["silu"]), s["B"])
+        del x0, x1, full, ref, x0s, x1s
+    return out
+
+
+def check_subset_groupnorm_two_phase_and_records():
+    """The two-phase entry points (pivot, partial sums about the pivot, apply; ``ops.groupnorm(shard=(1, ...))``): output, partial sums
+    [nsg][nchunks][G][2] and pivots [nsg][G] of the subset are the full launch's slices.  ``groupnorm_from_stats`` on the records of the
+    GEMM that produced its input: GEMM output, records [M / 16][G][3] and the normalised output likewise (the fold of 257 records per
+    group into runs of 2 does not depend on the first row)."""
+    import batch_subset_spec as bss
+    from anyv2v_amd import _lib
+    lib = _lib.load()
+    out = []
+    s = bss.NORM_TWO_PHASE
+    G, rpg, B, C = 32, s["rpg"], s["B"], s["C0"] + s["C1"]
+    x0, x1, (ga, be) = _bs_norm_data(s, 800)
+    r = s["per_branch"] * rpg
+
+    def two_phase(x0_, x1_):
+        M = x0_.shape[0]
+        n, npiv = int(lib.anyv2v_groupnorm_partial_floats(M, rpg, G, C)), (M // rpg) * G
+        stats = torch.zeros(ops.gn_scratch_floats(M, rpg, G), dtype=torch.float32, device=DEV)
+        y = ops.groupnorm(x0_, ga, be, stats, rpg, x1=x1_, groups=G, eps=1e-5, silu=s["silu"], shard=(1, lambda t: None))
+        return y, stats[:n].view(M // rpg, -1).clone(), stats[n:n + npiv].view(M // rpg, G).clone()
+    full = two_phase(x0, x1)
+    ref = _gn_ref64(x0, x1, ga, be, rpg, G, 1e-5, s["silu"])
+    x0s, x1s = x0[r:].contiguous(), None if x1 is None else x1[r:].contiguous()
+    out += _bs_rows(f"subset two-phase {s['name']} rows/group {rpg} x {s['per_branch'] * B}", full, ref, KTOL, (r, s["per_branch"], s["per_branch"]),
+                    lambda: two_phase(x0s, x1s), B)
+    del x0, x1, full, ref, x0s, x1s
+    # records of a producing GEMM
+    s = bss.NORM_RECORDS
+    rpg, B, C, K = s["rpg"], s["B"], s["C"], s["K"]
+    r = s["per_branch"] * rpg
+    T = B * r
+    a, w, bias = rnd(T, K, seed=811), rnd(C, K, scale=1 / math.sqrt(K), seed=812), (rnd(C, seed=813).float() + 3.0).half()
+    ga, be = _affine(C, 814)
+
+    def chain(a_):
+        M = a_.shape[0]
+        assert ops.gemm_gn_stats_floats(a_, w, rows_per_group=rpg, groups=G, bias=bias) == 3 * (M // 16) * G, "the producer's plan emits no records"
+        rec = torch.zeros(ops.gn_stats_floats(M, rpg, G), dtype=torch.float32, device=DEV)
+        c = ops.gemm(a_, w, bias=bias, gn=(rec, rpg, G))
+        y = ops.groupnorm_from_stats(c, ga, be, rec, rpg, groups=G, silu=True)
+        return y, c, rec[:3 * (M // 16) * G].view(M // 16, 3 * G).clone()
+    full = chain(a)
+    ref = _gn_ref64(full[1], None, ga, be, rpg, G, 1e-5, True)
+    a_s = a[r:].contiguous()
+    out += _bs_rows(f"subset {s['name']} rows/group {rpg} x {B}", full, ref, KTOL, (r, r, r // 16), lambda: chain(a_s), B,
+                    also=[_res(f"subset {s['name']}: the producing GEMM vs torch", full[1], _gemm_ref(a, w, bias), KTOL)])
+    return out
+
+
+def _bs_attn_layout(s, batch, Sq, Sk):
+    """(q rows, kv rows, inner, q strides, kv strides) of ``batch`` elements."""
+    if s["layout"] == "temporal":
+        HW = s["HW"]
+        st = (Sq * HW, 1, HW)
+        return batch // HW * Sq * HW, batch // HW * Sk * HW, HW, st, st
+    return batch * Sq, (batch // s.get("kv_div", 1)) * Sk, 1, (Sq, 0, 1), (Sk, 0, 1)
+
+
+def check_subset_attention():
+    """``ops.attention`` on the last two of three branches' batch elements, with and without the hint (the attention planner does not
+    read it): plain flash with a ragged last query tile, cross-attention with kv_div, the one-wave temporal kernel at a unit offset
+    that is no multiple of the 4 units of a block, the 96-key loop and whole-sequence kernels, 8-wave blocks against 4-wave blocks."""
+    import batch_subset_spec as bss
+    out = []
+    for i, s in enumerate(bss.ATTN_SPECS):
+        b, h, Sq, Sk, d, sub = s["batch"], s["heads"], s["Sq"], s["Sk"], s["d"], s["sub"]
+        C = h * d
+        Mq, Mk, inner, qst, kst = _bs_attn_layout(s, b, Sq, Sk)
+        fused = s["kv_div"] == 1 and Sq == Sk
+        if fused:
+            m = rnd(Mq, 3 * C, seed=900 + i)
+            q2, k2, v2 = m[:, :C], m[:, C:2 * C], m[:, 2 * C:]
+        else:
+            q2, kv = rnd(Mq, C, seed=900 + i), rnd(Mk, 2 * C, seed=950 + i)
+            k2, v2 = kv[:, :C], kv[:, C:]
+        extra = {} if d == 64 else dict(scale=d ** -0.5, head_dim=d)
+        kw = dict(heads=h, Sq=Sq, Sk=Sk, inner=inner, q_strides=qst, kv_strides=kst, kv_div=s["kv_div"])
+        full = ops.attention(q2, k2, v2, torch.zeros(Mq, C, dtype=torch.float16, device=DEV), batch=b, **kw, **extra)
+        only = None if b * h * Sq * Sk <= (1 << 26) else [0, sub, b - 1]
+        rows, ref = _attn_ref(q2, k2, v2, batch=b, d=d, only=only, **kw)
+        rq, rk = _bs_attn_layout(s, sub, Sq, Sk)[:2]
+        if fused:
+            ms = m[rq:].contiguous()
+            qs, ks, vs = ms[:, :C], ms[:, C:2 * C], ms[:, 2 * C:]
+        else:
+            qs, kvs = q2[rq:].contiguous(), kv[rk:].contiguous()
+            ks, vs = kvs[:, :C], kvs[:, C:]
+        name = f"subset attention[{s['full']} -> {s['subset']}] {s['name']}"
+        out.append(_res(f"{name}: full launch vs fp32 SDPA", full[rows], ref, KTOL))
+        out += _bs_rows(name, full, None, KTOL, rq, lambda: ops.attention(qs, ks, vs, torch.zeros(Mq - rq, C, dtype=torch.float16, device=DEV),
+                                                                         batch=b - sub, **kw, **extra), 3, hint_free=True)
+        del full, ref
+    return out
+
+
+def check_subset_attention_pnp():
+    """The PnP launch of a replayed site (unet.py: HipAttnProcessor.run, ``src_io = ("replay", buf)``): [negative, editing] with Q, K
+    read from the cached source rows [Ts, 2 C], V from the two-branch matrix, ``qk_mod = batch / 2`` -- against branches 1 and 2 of the
+    three-branch shared-softmax launch (``qk_mod = batch / 3``).  Flash form and the <= 16-frame one-wave form."""
+    import batch_subset_spec as bss
+    out = []
+    for i, s in enumerate(bss.ATTN_PNP_SPECS):
+        e, h, S = s["per_branch"], s["heads"], s["S"]
+        C = 64 * h
+        M3, _mk, inner, st, _ = _bs_attn_layout(s, 3 * e, S, S)
+        Ts = M3 // 3
+        qkv3 = rnd(M3, 3 * C, seed=980 + i)
+        kw = dict(heads=h, Sq=S, Sk=S, inner=inner, q_strides=st, kv_strides=st)
+        full = ops.attention(qkv3[:, :C], qkv3[:, C:2 * C], qkv3[:, 2 * C:], torch.zeros(M3, C, dtype=torch.float16, device=DEV), batch=3 * e, qk_mod=e, **kw)
+        rows, ref = _attn_ref(qkv3[:, :C], qkv3[:, C:2 * C], qkv3[:, 2 * C:], batch=3 * e, qk_mod=e, **kw)
+        src_qk = qkv3[:Ts, :2 * C].contiguous()
+        qkv2 = torch.full((2 * Ts, 3 * C), float("nan"), dtype=torch.float16, device=DEV)   # (Q, K columns of the two branches: never projected, never read)
+        qkv2[:, 2 * C:] = qkv3[Ts:, 2 * C:]
+
+        def replay():
+            return ops.attention(src_qk[:, :C], src_qk[:, C:], qkv2[:, 2 * C:], torch.zeros(2 * Ts, C, dtype=torch.float16, device=DEV), batch=2 * e,
+                                 qk_mod=e, **kw)
+        name = f"subset attention[{s['full']} -> {s['subset']}] {s['name']}"
+        out.append(_res(f"{name}: three-branch launch vs fp32 SDPA", full[rows], ref, KTOL))
+        out += _bs_rows(name, full, None, KTOL, Ts, replay, 3, hint_free=True)
+    return out
+
+
+def check_subset_step_kernels():
+    """The step kernels that take branch indices: the three-branch Vtok with (b_unc, b_cond) = (1, 2) against Vtok[1:] with (0, 1) --
+    cfg_ddim_step, guidance_stats (its records), cfg_ddim_step_ex with rescale and noise, guided_step."""
+    import batch_subset_spec as bss
+    import sampler_options_spec as sos
+    from anyv2v_amd.schedulers import DDIMScheduler
+    out = []
+    sp = bss.STEP_SPEC
+    C, Fr, H, W, ld, G = sp["C"], sp["F"], sp["H"], sp["W"], sp["ld"], sp["guidance"]
+    n1 = Fr * H * W
+    vt = (rnd(3 * n1, ld, seed=1201).float() + 0.25).half()
+    lat, noise = rnd(1, C, Fr, H, W, seed=1202), rnd(1, C, Fr, H, W, seed=1203)
+    vts = vt[n1:].contiguous()
+    coef = torch.tensor([0.8, 0.6, 0.9, math.sqrt(1 - 0.81)], dtype=torch.float32, device=DEV)
+    c = [float(t) for t in coef]
+    vv = vt[:, :C].double().view(3, Fr, H * W, C).permute(0, 3, 1, 2).reshape(3, C, Fr, H, W)
+    v = _h(vv[1].float() + _h(G * _h(vv[2].float() - vv[1].float()))).double()   # the kernel's fp16 CFG rounding points
+    xx = lat.double()[0]
+    ref = (c[2] * (c[0] * xx - c[1] * v) + c[3] * (c[0] * v + c[1] * xx))[None]
+    full = ops.cfg_ddim_step(vt, 1, 2, G, coef, lat, torch.empty_like(lat))
+    out += _bs_rows("subset cfg_ddim_step (1, 2) -> (0, 1)", full, ref, KTOL, 0, lambda: ops.cfg_ddim_step(vts, 0, 1, G, coef, lat, torch.empty_like(lat)), 3)
+    sch = DDIMScheduler()
+    sch.set_timesteps(50)
+    row = sch.coefficient_table([501], "cpu", eta=0.5, phi=0.7, n=lat.numel())[0]
+    drow = row.to(DEV)
+    ref = sos.fused_step(vt.cpu(), 1, 2, G, [float(t) for t in row], lat.cpu(), noise.cpu(), 0)
+
+    def ex(v_, bu, bc):
+        stats = ops.guidance_stats(v_, bu, bc, G, lat.shape)
+        y = ops.cfg_ddim_step_ex(v_, bu, bc, G, drow, lat, torch.empty_like(lat), prediction=0, stats=stats, phi=0.7, noise=noise)
+        return y, stats.clone()
+    out += _bs_rows("subset guidance_stats + cfg_ddim_step_ex (1, 2) -> (0, 1)", ex(vt, 1, 2), ref, KTOL, (0, 0), lambda: ex(vts, 0, 1), 3)
+    n = 4096 * 256 + 777   # past the grid cap: the grid-stride loop iterates
+    e, x = rnd(3, n, seed=1204), rnd(n, seed=1205)
+    es = e[1:].contiguous()
+    cf = (0.8, 0.6, 0.9, math.sqrt(1 - 0.81))
+    for pred in (0, 1, 2):
+        full = ops.guided_step(e, x, cf, b_unc=1, b_txt=2, g_txt=G, prediction=pred)
+        out += _bs_rows(f"subset guided_step prediction {pred} (1, 2) -> (0, 1)", full, _guided_ref(e, x, cf, 2, 1, -1, G, 1.0, pred), KTOL, 0,
+                        lambda: ops.guided_step(es, x, cf, b_unc=0, b_txt=1, g_txt=G, prediction=pred), 3)
+    return out
+
+
+def check_subset_layernorm_softmax():
+    """``layernorm`` and ``softmax_rows``: rows [T / 3, T) at an offset that is no multiple of the rows a block takes."""
+    import batch_subset_spec as bss
+    out = []
+    r, C = bss.LAYERNORM_SPEC["r"], bss.LAYERNORM_SPEC["C"]
+    x = (rnd(3 * r, C, seed=1301).float() * 1.5 + 2.0).half()
+    ga, be = _affine(C, 1302)
+    xs = x[r:].contiguous()
+    out += _bs_rows(f"subset layernorm r{r} x 3 C{C}", ops.layernorm(x, ga, be), _ln_ref64(x, ga, be, 1e-5), KTOL, r, lambda: ops.layernorm(xs, ga, be), 3)
+    r, cols = bss.SOFTMAX_SPEC["r"], bss.SOFTMAX_SPEC["cols"]
+    s = (rnd(3 * r, cols, seed=1303).float() * 8.0).contiguous()
+    ss = s[r:].contiguous()
+    out += _bs_rows(f"subset softmax_rows r{r} x 3 cols{cols}", ops.softmax_rows(s, 0.125), torch.softmax(0.125 * s.double(), 1), KTOL, r,
+                    lambda: ops.softmax_rows(ss, 0.125), 3)
+    return out
+
+
+def check_subset_hint_restored():
+    """After every ``with ops.batch_hint(...)`` above, a plain launch plans as un-hinted again: batch_subset_spec.HINT_PROBE is a
+    launch whose plan splits K on its own rows (no GroupNorm records) and emits records under batch_hint(3, 2) (the three-branch
+    launch does not split)."""
+    import batch_subset_spec as bss
+    p = bss.HINT_PROBE
+    a, w = torch.empty(p["M"], p["K"], dtype=torch.float16, device=DEV), torch.empty(p["N"], p["K"], dtype=torch.float16, device=DEV)
+    q = lambda: ops.gemm_gn_stats_floats(a, w, rows_per_group=p["M"], groups=32)
+    plain = q()
+    with ops.batch_hint(3, 2):
+        hinted = q()
+    after = q()
+    ok = plain == after == 0 and hinted == 3 * (p["M"] // 16) * 32 and ops._HINT == [1, 1]
+    return [dict(name=f"batch hint restored: records query plain {plain}, under batch_hint(3, 2) {hinted}, after {after}", err=0.0 if ok else 1.0, l2=0.0, tol=0.0, ok=ok)]
