@@ -52,7 +52,8 @@ class AnyV2V_I2VGenXL:
     def __init__(self, model_path: str = MODEL_ID, device="cuda:0", tmp_dir: str = "_demo_temp", pipe: Optional[I2VGenXLPipeline] = None,
                  random_init_seed: Optional[int] = None, synthetic_encoders: bool = False) -> None:
         # default inversion / edit configuration of the demo (gradio_demo.py:60-78); ``pnp_config`` also takes the optional keys
-        # (``inverse_config`` takes the optional ``source_*`` keys of ``prepare.plan_from_config``: a source clip of any size)
+        # (``inverse_config`` takes the optional ``source_*`` keys of ``prepare.plan_from_config``: a source clip of any size; ``pnp_config``
+        # takes ``source_restore`` / ``source_restore_resample``: the result goes back over the clip at its own size)
         # ``eta`` / ``guidance_rescale`` (``config.sampler_options``; e.g. ``obj.config.pnp_config.eta = 0.5``) and the ``edit_mask_*`` keys of
         # ``masked_edit.plan_from_config`` whose mask needs no file: ``edit_mask_auto`` or ``edit_mask_first_frame`` (where the edited first
         # frame differs from the source's -- a local edit with no extra input) with their tuning keys, ``edit_mask_grow`` /
@@ -99,7 +100,9 @@ class AnyV2V_I2VGenXL:
         # optional keys ``source_fit`` / ``source_x_offset`` / ``source_y_offset`` / ``source_resample`` and ``source_size: [w, h]`` (default
         # 512 x 512) of ``inverse_config`` (``prepare.plan_from_config``): a clip of any size is cropped and resized on the GPU first;
         # absent, the clip runs at the size its frames have
-        source_plan = prepare_plan_from_config(cfg.inverse_config)
+        # ``pnp_config`` takes ``source_restore`` / ``source_restore_resample`` beside them: the result is written at the clip's own size
+        source_plan = prepare_plan_from_config(cfg.inverse_config, restore_config=cfg.pnp_config)
+        source = frame_list   # the clip at its own size
         if source_plan is not None:
             _, frame_list = source_plan.frames(self.pipe, frame_list, source_plan.source_size or (512, 512))
         cfg.inverse_config.image_size = list(frame_list[0].size)
@@ -169,7 +172,12 @@ class AnyV2V_I2VGenXL:
             # with the composite: the decode the call above would have made, and the source frames pasted back outside the mask
             edited_video = finish_frames(self.pipe, plan, self.pipe.decode_latents(edited_video, decode_chunk_size=1), frame_list, mask) \
                 if comp else edited_video[0]
-        edited_video = [f.resize(tuple(cfg.inverse_config.image_size), resample=Image.LANCZOS) for f in edited_video]
+        if source_plan is not None and source_plan.restore:
+            alpha = self.pipe.composite_alpha(mask, grow=plan.grow, feather=plan.feather, grow_px=plan.composite["grow_px"],
+                                              feather_px=plan.composite["feather_px"]) if comp else None
+            edited_video = source_plan.restored(self.pipe, edited_video, source, alpha, prepared_from=source[0].size)
+        else:
+            edited_video = [f.resize(tuple(cfg.inverse_config.image_size), resample=Image.LANCZOS) for f in edited_video]
         output_path = os.path.join(tmp_dir, "edited_video.mp4")
         export_to_video(edited_video, output_path, fps=cfg.pnp_config.target_fps)
         trajectory.wait()  # the ddim_latents_{t}.pt files are complete when the call returns

@@ -8,26 +8,7 @@
 // Rows are W * C bytes, usually no multiple of 4, and the pointers carry no alignment: a dword is loaded where all four bytes are wanted and
 // the address allows (directly when aligned, as two aligned dwords and a byte-align when both lie inside the operand), bytes otherwise.
 // No atomics; every output byte is written once by one thread.
-#include "common.h"
-
-#define RS_THREADS 256
-#define RS_SHIFT 22
-#define RS_HALF (1 << (RS_SHIFT - 1))
-
-__device__ __forceinline__ int rs_mad(int acc, uint32_t sample, int k) { return __mul24((int)sample, k) + acc; }   // v_mad_i32_i24: |k| < 2^23
-__device__ __forceinline__ uint32_t rs_finish(int acc) { return (uint32_t)min(max(acc >> RS_SHIFT, 0), 255); }
-
-// four bytes at p, all inside [lo, hi)
-__device__ __forceinline__ uint32_t rs_load4(const uint8_t* p, const uint8_t* lo, const uint8_t* hi) {
-    const uint32_t a = (uint32_t)((uintptr_t)p & 3);
-    if (a == 0) return *(const uint32_t*)p;
-    const uint8_t* q = p - a;
-    if (q >= lo && q + 8 <= hi) {
-        const uint32_t* d = (const uint32_t*)q;
-        return __builtin_amdgcn_alignbyte(d[1], d[0], a);
-    }
-    return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
-}
+#include "resample_common.h"   // RS_*, rs_mad, rs_finish, rs_load4 (shared with restore.hip)
 
 // grid (ceil(ceil(RB / 4) / RS_THREADS), out_h, F), RB = W * C bytes per row
 __global__ __launch_bounds__(RS_THREADS) void resample_v_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int H, long long RB,

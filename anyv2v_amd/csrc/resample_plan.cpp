@@ -35,8 +35,10 @@ extern "C" int anyv2v_resample_table(int in_size, double in0, double in1, int ou
                 ANYV2V_RESAMPLE_MAX_SIDE);
     TABLE_CHECK(out_size >= 1 && out_size <= ANYV2V_RESAMPLE_MAX_SIDE, "resample_table: out_size = %d must lie in [1, %d]", out_size,
                 ANYV2V_RESAMPLE_MAX_SIDE);
-    // (written so that a NaN fails)
-    TABLE_CHECK(in0 >= 0.0 && in1 <= (double)in_size && in0 < in1, "resample_table: box [%g, %g) must be non-empty and inside [0, %d]", in0, in1,
+    // (written so that a NaN fails).  One float ulp of slack at the far end: Pillow checks a box given as C floats, then forms the width
+    // in1 - in0 in float, so that in0 + width -- what a caller who restates that hands over -- can pass in_size by a rounding; the taps are
+    // cut to the side below whatever the box says
+    TABLE_CHECK(in0 >= 0.0 && in1 <= (double)in_size * (1.0 + 1.0 / (1 << 23)) && in0 < in1, "resample_table: box [%g, %g) must be non-empty and inside [0, %d]", in0, in1,
                 in_size);
     double (*f)(double) = nullptr;
     double filter_support = 0.0;

@@ -284,15 +284,34 @@ class MaskedEditMixin:
         src = self._frames_u8("source_frames", source_frames)
         if tuple(src.shape) != (F, H, W, 3):
             raise ValueError(f"source_frames {tuple(src.shape)} do not match the video: [F, H, W, 3] = [{F}, {H}, {W}, 3] expected")
-        grow, feather = _grow_feather(grow, feather, unit="latent pixels")
-        grow_px = _int_in("grow_px", grow_px, 0, _lib.COMPOSITE_MAX_GROW, "pixels")
-        feather_px = _float_in("feather_px", feather_px, 0, _lib.COMPOSITE_MAX_RADIUS // 3, "pixels")
+        grow, feather, grow_px, feather_px = self._alpha_arguments(grow, feather, grow_px, feather_px)
         if not isinstance(match_color, bool):
             raise ValueError(f"match_color={match_color!r}: True or False")
         device = video.device
-        lm = ops.latent_mask(m.to(device), grow, feather)
-        alpha = ops.pixel_alpha(lm, grow_px, feather_px)
+        alpha = self._composite_alpha(m.to(device), grow, feather, grow_px, feather_px)
         return ops.composite(video.to(torch.float16).contiguous(), src.to(device).contiguous(), alpha, match_color)
+
+    @staticmethod
+    def _alpha_arguments(grow, feather, grow_px, feather_px):
+        grow, feather = _grow_feather(grow, feather, unit="latent pixels")
+        grow_px = _int_in("grow_px", grow_px, 0, _lib.COMPOSITE_MAX_GROW, "pixels")
+        feather_px = _float_in("feather_px", feather_px, 0, _lib.COMPOSITE_MAX_RADIUS // 3, "pixels")
+        return grow, feather, grow_px, feather_px
+
+    @staticmethod
+    def _composite_alpha(m, grow, feather, grow_px, feather_px):
+        """``m``: fp16 [Fm, H, W] of ``_edit_mask_fp16`` on the device -> the alpha ``ops.composite`` takes (``ops.pixel_alpha``'s)."""
+        return ops.pixel_alpha(ops.latent_mask(m, grow, feather), grow_px, feather_px)
+
+    @torch.no_grad()
+    def composite_alpha(self, mask, grow: int = 0, feather: float = 0.0, grow_px: int = 0, feather_px: float = 0.0):
+        """The alpha ``composite_over_source`` builds from the same arguments, on its own: fp32 [Fm, H, W] in [0, 1] on this pipeline's
+        device, Fm 1 or the mask's frame count (1 = the edit, 0 = the source).  ``restore_frames`` takes it to paste a composited edit over
+        the source clip at its own size."""
+        if getattr(self.unet, "frame_parallel", None) is not None:
+            raise NotImplementedError("composite on a frame-parallel clip: the masked edit it finishes is refused there")
+        m = self._edit_mask_fp16(mask)
+        return self._composite_alpha(m.to(self._execution_device), *self._alpha_arguments(grow, feather, grow_px, feather_px)).float()
 
     @staticmethod
     def _frames_u8(name, frames):

@@ -893,6 +893,120 @@ def resample_u8(frames: torch.Tensor, size, resample: str = "lanczos", box=None,
     return out
 
 
+_RESTORE_DEVICE = {}    # (geometry, device) -> the passes of ``restore_passes`` with their tables on the device
+
+
+def _dest(dest, sh, sw, what):
+    try:
+        dx0, dy0, dx1, dy1 = (int(v) for v in dest)
+        ok = (dx0, dy0, dx1, dy1) == tuple(dest)
+    except (TypeError, ValueError):
+        ok = False
+    if not ok or not (0 <= dx0 < dx1 <= sw and 0 <= dy0 < dy1 <= sh):
+        raise ValueError(f"{what}: dest={dest!r}: (dx0, dy0, dx1, dy1), a non-empty integer rectangle inside the {sw} x {sh} frame")
+    return dx0, dy0, dx1, dy1
+
+
+def restore_passes(h: int, w: int, dest, box, resample: str = "lanczos"):
+    """What ``restore_u8`` launches for an edit of h x w resized from ``box`` to the size of ``dest``: ``(edit, alpha)``, each
+    ``(row0, rows, hpass, vtable)`` on the CPU -- the input rows [row0, row0 + rows) the horizontal pass covers, its table (``None`` where
+    Pillow skips it) and the vertical table re-based to row0, an identity table (``ksize`` 1, coefficient ``1 << 22``) where Pillow skips
+    the vertical pass.  The edit's tables are of ``resample``, alpha's of bilinear.  ``box`` is taken the way Pillow takes it: its four
+    numbers as C floats and the width ``x1 - x0`` formed in float (``ImagingResample`` reads ``float box[4]``), so that the tables are the
+    ones Pillow builds for the same argument."""
+    f32 = lambda v: C.c_float(v).value
+    try:
+        x0, y0, x1, y1 = (f32(float(v)) for v in box)
+    except (TypeError, ValueError):
+        raise ValueError(f"box={box!r}: (x0, y0, x1, y1) in the edit's pixels") from None
+    x1, y1 = x0 + f32(x1 - x0), y0 + f32(y1 - y0)
+    dw, dh = int(dest[2]) - int(dest[0]), int(dest[3]) - int(dest[1])
+    passes = []
+    for name in (resample, "bilinear"):
+        _, row0, rows, hp, vp = resample_passes(h, w, (dw, dh), name, (x0, y0, x1, y1))
+        if vp is None:   # (dh == h and the box is the whole side)
+            vp = (1, torch.stack([torch.arange(dh, dtype=torch.int32), torch.ones(dh, dtype=torch.int32)], dim=1).contiguous(),
+                  torch.full((dh, 1), 1 << 22, dtype=torch.int32))
+        passes.append((row0, rows, hp, vp))
+    return tuple(passes)
+
+
+def restore_paste_u8(source: torch.Tensor, edit_h: torch.Tensor, alpha_h: Optional[torch.Tensor], dest, e_table, a_table=None,
+                     out: Optional[torch.Tensor] = None):
+    """``anyv2v_restore_paste_u8`` (the definition is in ``include/anyv2v_hip.h``): ``source`` uint8 [F, sh, sw, 3], ``edit_h`` uint8
+    [F, e_rows, dw, 3] and ``alpha_h`` uint8 [1 or F, a_rows, dw] or None, the horizontal intermediates; ``e_table`` / ``a_table``
+    ``(ksize, bounds, coeffs)`` on the device -> uint8 [F, sh, sw, 3]."""
+    ok = lambda t, nd: isinstance(t, torch.Tensor) and t.dtype == torch.uint8 and t.dim() == nd and t.is_contiguous() and t.is_cuda
+    if not (ok(source, 4) and source.shape[3] == 3 and source.shape[0] >= 1):
+        raise ValueError("restore_paste_u8: source: a contiguous uint8 [F, sh, sw, 3] tensor on the GPU expected")
+    F, sh, sw, _ = (int(v) for v in source.shape)
+    dx0, dy0, dx1, dy1 = _dest(dest, sh, sw, "restore_paste_u8")
+    dw, dh = dx1 - dx0, dy1 - dy0
+    if not (ok(edit_h, 4) and edit_h.shape[0] == F and edit_h.shape[1] >= 1 and tuple(edit_h.shape[2:]) == (dw, 3) and edit_h.device == source.device):
+        raise ValueError(f"restore_paste_u8: edit_h: a contiguous uint8 [{F}, rows, {dw}, 3] tensor on {source.device} expected")
+    if alpha_h is not None and not (ok(alpha_h, 3) and alpha_h.shape[0] in (1, F) and alpha_h.shape[1] >= 1 and alpha_h.shape[2] == dw
+                                    and alpha_h.device == source.device and a_table is not None):
+        raise ValueError(f"restore_paste_u8: alpha_h: a contiguous uint8 [1 or {F}, rows, {dw}] tensor on {source.device} with its table expected")
+    for t in (e_table,) + (() if alpha_h is None else (a_table,)):
+        ksize, bounds, coeffs = t
+        if not (bounds.dtype == torch.int32 and coeffs.dtype == torch.int32 and tuple(bounds.shape) == (dh, 2) and tuple(coeffs.shape) == (dh, ksize)
+                and bounds.is_contiguous() and coeffs.is_contiguous() and bounds.device == source.device and coeffs.device == source.device):
+            raise ValueError(f"restore_paste_u8: a table (ksize, int32 [{dh}, 2], int32 [{dh}, ksize]) on {source.device} expected")
+    if out is None:
+        out = torch.empty_like(source)
+    elif not (ok(out, 4) and out.shape == source.shape and out.device == source.device):
+        raise ValueError("restore_paste_u8: out: a contiguous uint8 tensor of the source's shape and device expected")
+    a = (1, 1, None, None, 1) if alpha_h is None else (int(alpha_h.shape[0]), int(alpha_h.shape[1]), _p(a_table[1]), _p(a_table[2]), a_table[0])
+    _lib.check(_lib.load().anyv2v_restore_paste_u8(_p(source), _p(edit_h), _p(alpha_h), _p(out), F, sh, sw, dx0, dy0, dx1, dy1,
+                                                   int(edit_h.shape[1]), _p(e_table[1]), _p(e_table[2]), e_table[0], *a, _stream()),
+               "anyv2v_restore_paste_u8")
+    return out
+
+
+def restore_u8(edited_u8: torch.Tensor, source_u8: torch.Tensor, dest, box, resample: str = "lanczos", alpha_u8: Optional[torch.Tensor] = None):
+    """An edit at the working size back at the source clip's own size, per frame Pillow's
+    ``out = S.copy(); out.paste(E.resize(dsize, resample, box), (dx0, dy0), mask=A.resize(dsize, BILINEAR, box))`` byte for byte (a plain
+    paste without alpha): ``edited_u8`` contiguous uint8 [F, h, w, 3] and ``source_u8`` [F, sh, sw, 3] on the GPU, ``dest = (dx0, dy0,
+    dx1, dy1)`` integers in source pixels, ``box`` floats in the edit's pixels (``prepare.restore_geometry`` makes both), ``alpha_u8``
+    uint8 [1 or F, h, w] (255 = the edit) -> uint8 [F, sh, sw, 3].  Outside ``dest`` the result holds the source's bytes.  Up to three
+    launches: ``anyv2v_resample_h_u8`` on the edit and on alpha, then ``anyv2v_restore_paste_u8``."""
+    ok = lambda t, nd: isinstance(t, torch.Tensor) and t.dtype == torch.uint8 and t.dim() == nd and t.is_contiguous() and t.is_cuda and t.shape[0] >= 1
+    got = lambda t: f"{tuple(t.shape)} {t.dtype} on {t.device}" if isinstance(t, torch.Tensor) else type(t).__name__
+    if not (ok(edited_u8, 4) and edited_u8.shape[3] == 3):
+        raise ValueError(f"restore_u8: edited_u8: a contiguous uint8 [F, h, w, 3] tensor on the GPU expected, got {got(edited_u8)}")
+    F, h, w, _ = (int(v) for v in edited_u8.shape)
+    if not (ok(source_u8, 4) and source_u8.shape[3] == 3 and source_u8.shape[0] == F and source_u8.device == edited_u8.device):
+        raise ValueError(f"restore_u8: source_u8: a contiguous uint8 [{F}, sh, sw, 3] tensor on {edited_u8.device} expected, got {got(source_u8)}")
+    if alpha_u8 is not None and not (ok(alpha_u8, 3) and alpha_u8.shape[0] in (1, F) and tuple(alpha_u8.shape[1:]) == (h, w)
+                                     and alpha_u8.device == edited_u8.device):
+        raise ValueError(f"restore_u8: alpha_u8: a contiguous uint8 [1 or {F}, {h}, {w}] tensor on {edited_u8.device} expected, got {got(alpha_u8)}")
+    sh, sw = int(source_u8.shape[1]), int(source_u8.shape[2])
+    dest = _dest(dest, sh, sw, "restore_u8")
+    dw = dest[2] - dest[0]
+    dev = edited_u8.device
+    key = (h, w, dest, tuple(box) if isinstance(box, (tuple, list)) else box, resample, str(dev))
+    if key not in _RESTORE_DEVICE:
+        passes = restore_passes(h, w, dest, box, resample)
+        if len(_RESTORE_DEVICE) >= 64:
+            _RESTORE_DEVICE.clear()
+        on = lambda t: None if t is None else (t[0], t[1].to(dev), t[2].to(dev))
+        _RESTORE_DEVICE[key] = tuple((row0, rows, on(hp), on(vp)) for row0, rows, hp, vp in passes)
+    lib = _lib.load()
+
+    def horizontal(x, p):   # x: [N, h, w, C] -> [N, rows, dw, C]
+        row0, rows, hp, _ = p
+        if hp is None:
+            return x[:, row0:row0 + rows].contiguous()
+        y = torch.empty((x.shape[0], rows, dw, x.shape[3]), dtype=torch.uint8, device=dev)
+        _lib.check(lib.anyv2v_resample_h_u8(_p(x), _p(y), int(x.shape[0]), h, w, int(x.shape[3]), row0, rows, dw, _p(hp[1]), _p(hp[2]), hp[0],
+                                            _stream()), "anyv2v_resample_h_u8")
+        return y
+    pe, pa = _RESTORE_DEVICE[key]
+    edit_h = horizontal(edited_u8, pe)
+    alpha_h = None if alpha_u8 is None else horizontal(alpha_u8[..., None], pa)[..., 0]
+    return restore_paste_u8(source_u8, edit_h, alpha_h, dest, pe[3], None if alpha_u8 is None else pa[3])
+
+
 def ddim_step(v: torch.Tensor, x: torch.Tensor, sa_t: float, sb_t: float, sa_p: float, sb_p: float, out=None):
     lib = _lib.load()
     v = v.to(torch.float16).contiguous()

@@ -308,6 +308,16 @@ class I2VGenXLPipeline(MaskedEditMixin):
         from . import prepare
         return prepare.prepare_mask(mask, height, width, fit, x_offset, y_offset, device=self._execution_device)
 
+    def restore_frames(self, edited, source_frames, fit="crop", x_offset=0.0, y_offset=0.0, resample="lanczos", alpha=None):
+        """The way back from ``prepare_frames``: ``edited`` (uint8 [F, h, w, 3] or PIL images at the working size) resized into the footprint
+        it was prepared from and pasted over ``source_frames`` at their own size -> uint8 [F, sh, sw, 3] on this pipeline's device, Pillow's
+        ``paste(resize(.., box), xy, mask)`` byte for byte; ``alpha``: None or fp32 [1 or F, h, w] in [0, 1] (``composite_alpha``), where it
+        is 0 the source's bytes stay (``anyv2v_amd.prepare.restore_frames``)."""
+        from . import prepare
+        if getattr(self.unet, "frame_parallel", None) is not None:
+            raise NotImplementedError("restore on a frame-parallel clip: the composite it follows is refused there")
+        return prepare.restore_frames(edited, source_frames, fit, x_offset, y_offset, resample, alpha, device=self._execution_device)
+
     def encode_vae_video(self, video, device, height=576, width=1024):
         vae = self._need("vae")
         return vae.encode_video(video, device, height, width)

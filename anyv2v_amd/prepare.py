@@ -4,8 +4,10 @@ reference's top-level ``prepare_video.py`` (``crop_and_resize_video``).  The res
 ``img.resize(resize_to, LANCZOS).crop(window)`` and an edit mask drawn on a source-size frame lands on the same pixels.
 
 ``fit_geometry`` is the reference's arithmetic; ``prepare_frames`` / ``prepare_mask`` run it (``I2VGenXLPipeline`` has them as methods on
-its own device); ``plan_from_config`` is the only reader of the OPTIONAL keys ``source_fit`` / ``source_x_offset`` / ``source_y_offset`` /
-``source_resample`` / ``source_size``, which the reference's files do not have: absent, nothing here runs."""
+its own device); ``restore_geometry`` is its inverse and ``restore_frames`` the way back to the source's own size, Pillow's
+``paste(resize(.., box), xy, mask)`` byte for byte (``ops.restore_u8``); ``plan_from_config`` is the only reader of the OPTIONAL keys
+``source_fit`` / ``source_x_offset`` / ``source_y_offset`` / ``source_resample`` / ``source_size`` / ``source_restore`` /
+``source_restore_resample``, which the reference's files do not have: absent, nothing here runs."""
 from __future__ import annotations
 
 import os
@@ -61,18 +63,37 @@ def fit_geometry(src_size, size, fit, x_offset=0.0, y_offset=0.0):
     return (new_w, new_h), (off_x, off_y, w, h)
 
 
-def _frames_tensor(frames, device):
+def restore_geometry(src_size, size, fit, x_offset=0.0, y_offset=0.0):
+    """The inverse of ``fit_geometry``: source ``(sw, sh)`` and working size ``(w, h)`` -> ``(dest, box)``.  The window ``(ox, oy, w, h)``
+    of the frame resized to ``(nw, nh)`` covers the real rectangle ``[ox sw / nw, (ox + w) sw / nw] x [oy sh / nh, (oy + h) sh / nh]`` of the
+    source.  ``dest = (dx0, dy0, dx1, dy1)`` is the largest integer rectangle inside it (``ceil`` / ``floor`` in exact integer arithmetic)
+    and ``box = (dx0 nw / sw - ox, ..)``, doubles clamped to ``[0, w] x [0, h]``, is its pre-image in the edited clip's coordinates: with them
+    ``E.resize((dx1 - dx0, dy1 - dy0), resample, box=box)`` samples the edited frame where ``prepare_frames`` sampled the source, and source
+    pixels that lie only partly inside the footprint stay the source's.  ``fit="stretch"``: the whole frame and ``(0, 0, w, h)``.  An empty
+    ``dest`` (a tiny source blown up to the working size) is a ``ValueError``."""
+    (nw, nh), (ox, oy, w, h) = fit_geometry(src_size, size, fit, x_offset, y_offset)
+    sw, sh = (int(v) for v in src_size)
+    dx0, dx1 = -((-ox * sw) // nw), min(((ox + w) * sw) // nw, sw)
+    dy0, dy1 = -((-oy * sh) // nh), min(((oy + h) * sh) // nh, sh)
+    if dx1 <= dx0 or dy1 <= dy0:
+        raise ValueError(f"restore_geometry: no whole pixel of the {sw} x {sh} source lies inside the window {w} x {h} at ({ox}, {oy}) of the "
+                         f"frame resized to {nw} x {nh}")
+    back = lambda d, n, s, o, hi: min(max((d * n - o * s) / s, 0.0), float(hi))   # (the numerator is an exact integer: one rounding)
+    return (dx0, dy0, dx1, dy1), (back(dx0, nw, sw, ox, w), back(dy0, nh, sh, oy, h), back(dx1, nw, sw, ox, w), back(dy1, nh, sh, oy, h))
+
+
+def _frames_tensor(frames, device, what="prepare_frames"):
     """A list of PIL images of one size, or a uint8 [F, H, W, 3] tensor -> contiguous uint8 [F, H, W, 3] on ``device``."""
     if isinstance(frames, torch.Tensor):
         if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3 or frames.shape[0] < 1:
-            raise ValueError(f"prepare_frames: a uint8 [F, H, W, 3] tensor expected, got {tuple(frames.shape)} {frames.dtype}")
+            raise ValueError(f"{what}: a uint8 [F, H, W, 3] tensor expected, got {tuple(frames.shape)} {frames.dtype}")
         return frames.to(device).contiguous()
     frames = list(frames)
     if not frames or not all(isinstance(f, Image.Image) for f in frames):
-        raise ValueError("prepare_frames: a non-empty list of PIL images or a uint8 [F, H, W, 3] tensor expected")
+        raise ValueError(f"{what}: a non-empty list of PIL images or a uint8 [F, H, W, 3] tensor expected")
     sizes = {f.size for f in frames}
     if len(sizes) != 1:
-        raise ValueError(f"prepare_frames: the frames have unequal sizes {sorted(sizes)}")
+        raise ValueError(f"{what}: the frames have unequal sizes {sorted(sizes)}")
     return torch.from_numpy(np.stack([np.asarray(f.convert("RGB"), dtype=np.uint8) for f in frames])).to(device)
 
 
@@ -98,6 +119,31 @@ def prepare_mask(mask, height, width, fit="crop", x_offset=0.0, y_offset=0.0, de
     return (out >= 128).to(torch.uint8) * 255
 
 
+def restore_frames(edited, source_frames, fit="crop", x_offset=0.0, y_offset=0.0, resample="lanczos", alpha=None, device="cuda"):
+    """The way back: ``edited`` (uint8 [F, h, w, 3] or F PIL images at the working size) resized into the footprint it was prepared from
+    and pasted over ``source_frames`` (at the source's own size, any) -> uint8 [F, sh, sw, 3] on ``device``, per frame Pillow's
+    ``S.paste(E.resize(dsize, resample, box), (dx0, dy0), mask=A.resize(dsize, BILINEAR, box))`` of ``restore_geometry`` byte for byte
+    (``ops.restore_u8``).  ``alpha``: None (the whole footprint is replaced) or fp32 [1 or F, h, w] in [0, 1], converted once by
+    ``rint(255 alpha)``: where it is 0 the result holds the source's bytes, where it is 1 the upscaled edit's."""
+    e = _frames_tensor(edited, device, "restore_frames: edited")
+    s = _frames_tensor(source_frames, device, "restore_frames: source_frames")
+    F, h, w, _ = (int(v) for v in e.shape)
+    if s.shape[0] != F:
+        raise ValueError(f"restore_frames: {F} edited frames against {s.shape[0]} source frames")
+    dest, box = restore_geometry((int(s.shape[2]), int(s.shape[1])), (w, h), fit, x_offset, y_offset)
+    a = None
+    if alpha is not None:
+        if not isinstance(alpha, torch.Tensor) or not alpha.is_floating_point() or alpha.dim() != 3 or alpha.shape[0] not in (1, F) \
+                or tuple(alpha.shape[1:]) != (h, w):
+            got = f"{tuple(alpha.shape)} {alpha.dtype}" if isinstance(alpha, torch.Tensor) else type(alpha).__name__
+            raise ValueError(f"restore_frames: alpha: a float [1 or {F}, {h}, {w}] tensor expected, got {got}")
+        a = alpha.to(device=device, dtype=torch.float32)
+        if not bool(((a >= 0.0) & (a <= 1.0)).all()):   # (false for NaN)
+            raise ValueError("restore_frames: alpha must lie in [0, 1]")
+        a = torch.round(a * 255.0).to(torch.uint8).contiguous()
+    return ops.restore_u8(e, s, dest, box, resample, a)
+
+
 # ------------------------------------------------------------------------------------------------ the configuration keys
 @dataclass(frozen=True)
 class PreparePlan:
@@ -108,6 +154,8 @@ class PreparePlan:
     y_offset: float = 0.0
     resample: str = "lanczos"
     source_size: Optional[tuple] = None
+    restore: bool = False               # ``source_restore``: the result goes back to the source clip's own size (``restored``)
+    restore_resample: str = "lanczos"
 
     def frames(self, pipe, frames, image_size):
         """PIL frames of any one size -> (uint8 [F, h, w, 3] on the pipeline's device, the same as PIL images)."""
@@ -119,18 +167,48 @@ class PreparePlan:
         w, h = image_size
         return pipe.prepare_mask(mask, h, w, fit=self.fit, x_offset=self.x_offset, y_offset=self.y_offset).cpu()
 
+    def restored(self, pipe, edited_u8, source_frames, alpha=None, prepared_from=None):
+        """The frames that would be written (uint8 [F, h, w, 3] or PIL images at the working size) back over the source clip at its own
+        size -> PIL images of the source's size (``pipe.restore_frames`` with this plan's geometry).  ``prepared_from``: the ``(w, h)``
+        the clip was prepared from; source frames of another size are refused (the geometry would point elsewhere)."""
+        if prepared_from is not None:
+            sizes = {tuple(f.size) for f in source_frames} if not isinstance(source_frames, torch.Tensor) else \
+                {(int(source_frames.shape[2]), int(source_frames.shape[1]))}
+            if sizes != {tuple(prepared_from)}:
+                raise ValueError(f"source_restore: source frames of {sorted(sizes)} against a clip prepared from {tuple(prepared_from)}")
+        out = pipe.restore_frames(edited_u8, source_frames, fit=self.fit, x_offset=self.x_offset, y_offset=self.y_offset,
+                                  resample=self.restore_resample, alpha=alpha)
+        return [Image.fromarray(f) for f in out.cpu().numpy()]
 
-def plan_from_config(config) -> Optional[PreparePlan]:
+    def tag(self):
+        """What ``source_restore`` adds to the name of an output directory ("" when it is off)."""
+        if not self.restore:
+            return ""
+        return "_restored" + ("" if self.restore_resample == "lanczos" else f"-{self.restore_resample}")
+
+
+def plan_from_config(config, restore_config=None) -> Optional[PreparePlan]:
     """The ``PreparePlan`` of a configuration (template YAML merged with a JSON entry, ``api``'s ``inverse_config``, or any plain
     namespace), or None when it has no ``source_fit``: then nothing is prepared and every name, file and error is what it was before the
-    keys existed.  A tuning key without ``source_fit`` has nothing to act on and is refused, not dropped."""
-    opt = lambda key: config.get(key, None) if hasattr(config, "get") else getattr(config, key, None)
+    keys existed.  A tuning key without ``source_fit`` has nothing to act on and is refused, not dropped.  ``source_restore`` (a bool)
+    and ``source_restore_resample`` are read from ``restore_config`` where one is given (``api``'s ``pnp_config``), else from ``config``."""
+    opt = lambda key, c=config: c.get(key, None) if hasattr(c, "get") else getattr(c, key, None)
+    ropt = lambda key: opt(key, config if restore_config is None else restore_config)
     fit = opt("source_fit")
     tuning = ("source_x_offset", "source_y_offset", "source_resample", "source_size")
+    restore, restore_resample = ropt("source_restore"), ropt("source_restore_resample")
+    if restore is not None and not isinstance(restore, bool):
+        raise ValueError(f"source_restore={restore!r}: true or false")
+    if restore_resample is not None and not restore:
+        raise ValueError("source_restore_resample without source_restore: there is no way back to tune")
+    if restore_resample is not None and restore_resample not in _lib.RESAMPLE_FILTERS:
+        raise ValueError(f"source_restore_resample={restore_resample!r}: one of {sorted(_lib.RESAMPLE_FILTERS)}")
     if fit is None:
         for k in tuning:
             if opt(k) is not None:
                 raise ValueError(f"{k} without source_fit: there is no preparation to tune")
+        if restore:
+            raise ValueError("source_restore without source_fit: nothing was prepared, there is no size to go back to")
         return None
     if fit not in FITS:
         raise ValueError(f"source_fit={fit!r}: one of {FITS}")
@@ -146,7 +224,7 @@ def plan_from_config(config) -> Optional[PreparePlan]:
         size = _size("source_size", size)
         if size[0] % 8 or size[1] % 8:
             raise ValueError(f"source_size={list(size)}: width and height must be multiples of 8")
-    return PreparePlan(fit, x, y, resample, size)
+    return PreparePlan(fit, x, y, resample, size, bool(restore), "lanczos" if restore_resample is None else restore_resample)
 
 
 def load_source_frames(frames_path, n_frames):

@@ -55,6 +55,8 @@ def output_suffix(config, ddim_init_latents_t_idx) -> str:
     eta, rescale = sampler_options(config)
     plan = plan_from_config(config)   # optional keys ``edit_mask_*``: a masked and an unmasked edit do not overwrite each other
     mask_tag = "" if plan is None else plan.tag()
+    source_plan = prepare_plan_from_config(config)   # optional key ``source_restore``: frames at the source's size get a directory of their own
+    mask_tag += "" if source_plan is None else source_plan.tag()
     return ("ddim_init_latents_t_idx_" + str(ddim_init_latents_t_idx) + "_nsteps_" + str(config.n_steps) + "_cfg_"
             + str(config.cfg) + "_pnpf" + str(config.pnp_f_t) + "_pnps" + str(config.pnp_spatial_attn_t) + "_pnpt"
             + str(config.pnp_temp_attn_t) + (f"_eta{eta}" if eta > 0 else "") + (f"_rescale{rescale}" if rescale > 0 else "") + mask_tag)
@@ -129,9 +131,12 @@ class Stage2:
                 logger.error(f"Field {k} contains 'ReplaceMe'")
         source_plan = prepare_plan_from_config(config)   # optional keys ``source_*``; absent: None, and the frames must have the working size
         if source_plan is not None:   # the same frames the inversion prepared (``anyv2v_amd.prepare``: the bytes are a function of the files)
+            if source_plan.restore and self.fp_mode:
+                raise NotImplementedError("source_restore on a frame-parallel clip: refused like the composite it follows")
             logger.info(f"Preparing frames from: {config.video_frames_path} ({source_plan})")
             source = load_source_clip(config.video_frames_path, config.video_path, config.n_frames)
             _, frame_list = source_plan.frames(pipe, source, tuple(config.image_size))
+            source_size = source[0].size   # what the frames were prepared from: ``restored`` goes back to it
         else:
             try:
                 logger.info(f"Loading frames from: {config.video_frames_path}")
@@ -224,7 +229,15 @@ class Stage2:
 
         output_dir = os.path.join(config.output_dir, output_suffix(config, t_idx))
         os.makedirs(output_dir, exist_ok=True)
-        edited_video = [frame.resize(tuple(config.image_size), resample=Image.LANCZOS) for frame in edited_video]
+        if source_plan is not None and source_plan.restore:
+            # (optional key ``source_restore``: what would be written goes back over the source clip at its own size; with the composite its
+            # alpha is applied again there, so that outside the mask the files hold the source's full-size bytes)
+            comp = None if plan is None else plan.composite
+            alpha = None if comp is None else pipe.composite_alpha(mask, grow=plan.grow, feather=plan.feather, grow_px=comp["grow_px"],
+                                                                   feather_px=comp["feather_px"])
+            edited_video = source_plan.restored(pipe, edited_video, source, alpha, prepared_from=source_size)
+        else:
+            edited_video = [frame.resize(tuple(config.image_size), resample=Image.LANCZOS) for frame in edited_video]
         name = "video"
         export_to_video(edited_video, os.path.join(output_dir, f"{name}.mp4"), fps=config.target_fps)
         export_to_gif(edited_video, os.path.join(output_dir, f"{name}.gif"))      # (no rate, as ``:179``: 100 ms per frame)

@@ -526,7 +526,8 @@ int anyv2v_first_frame_mask_u8(const void* source, const void* edited, void* mas
  *   ANYV2V_RESAMPLE_LANCZOS   support 3: sinc(x) sinc(x / 3) for -3 <= x < 3, sinc(x) = sin(pi x) / (pi x), sinc(0) = 1
  * Returns ksize.  With bounds == NULL or coeffs == NULL it only returns ksize; otherwise it fills bounds[out_size][2] = (xmin, n) and
  * coeffs[out_size][ksize] = k, zero past n.  A negative status (text: anyv2v_last_error()) for sides outside 1 .. ANYV2V_RESAMPLE_MAX_SIDE,
- * a box that is empty or not inside [0, in_size], an unknown filter, or a table with a row of sum |k[x]| >= 2 * 2^22: below that,
+ * a box that is empty or not inside [0, in_size] (in1 may pass in_size by one float ulp, in_size * 2^-23: Pillow forms the width of a
+ * float box in float, and in0 + width can land there), an unknown filter, or a table with a row of sum |k[x]| >= 2 * 2^22: below that,
  * 255 * sum |k| + 2^21 < 2^31 and the kernels' int32 accumulator cannot overflow.  Host code only, no GPU is touched.
  *
  * An output sample of either pass, per band:   acc = 2^21 + sum over x < n of in[xmin + x] * k[x]   (int32)
@@ -548,6 +549,34 @@ int anyv2v_resample_h_u8(const void* src, void* dst, int32_t F, int32_t H, int32
                          const int32_t* bounds, const int32_t* coeffs, int32_t ksize, void* stream);
 int anyv2v_resample_v_u8(const void* src, void* dst, int32_t F, int32_t H, int32_t W, int32_t C, int32_t out_h, const int32_t* bounds,
                          const int32_t* coeffs, int32_t ksize, void* stream);
+
+/* The way back to the source clip's own size (restore.hip): per frame, in Pillow's words,
+ *   out = S.copy();  out.paste(E.resize(dsize, filter, box), (dx0, dy0), mask = A.resize(dsize, BILINEAR, box))
+ * with S the source frame [sh, sw, 3], E the edited frame at the working size, A its alpha (one band) and dsize = (dx1 - dx0, dy1 - dy0).
+ * Pillow resizes horizontally first: the caller runs anyv2v_resample_h_u8 on E (3 bands) and on A (1 band) over the input rows the vertical
+ * tables read, and this entry does the rest in one launch over the whole output frame.
+ *   source   uint8 [F, sh, sw, 3]
+ *   edit_h   uint8 [F, e_rows, dw, 3], the horizontal intermediate of the edit, dw = dx1 - dx0
+ *   alpha_h  uint8 [mask_frames, a_rows, dw], the horizontal intermediate of alpha, mask_frames = 1 (every frame) or F; or NULL: m = 255
+ *            everywhere, a plain paste, and mask_frames / a_* are not looked at
+ *   e_bounds int32 [dh][2], e_coeffs int32 [dh][e_ksize], dh = dy1 - dy0: DEVICE copies of the vertical table of the edit's filter as
+ *            anyv2v_resample_table writes it, its (ymin, n) re-based to the intermediate's first row; a_bounds / a_coeffs [dh][a_ksize]: the
+ *            same for alpha (BILINEAR: another filter, hence another table and another row range).  Where Pillow skips the vertical pass the
+ *            caller hands an identity table (ksize 1, (r, 1), coefficient 2^22): the kernel does not branch on it
+ *   out      uint8 [F, sh, sw, 3]
+ * A byte outside dest = [dx0, dx1) x [dy0, dy1) is the source's.  A byte inside, per band, with d the source's byte:
+ *   e = clamp((2^21 + sum over y < n of edit_h[ymin + y] * k[y]) >> 22, 0, 255)        the vertical pass of anyv2v_resample_v_u8
+ *   m = the same form over alpha_h at the byte's pixel (255 without alpha)
+ *   t = d * (255 - m) + e * m + 128;   out = ((t >> 8) + t) >> 8                       Pillow's paste for 8-bit bands, all in uint32
+ * m = 0 returns d and m = 255 returns e exactly.  A negative status (text: anyv2v_last_error()) for a null source / edit_h / out or table,
+ * F outside 1 .. 65535, sides outside 1 .. ANYV2V_RESAMPLE_MAX_SIDE, a dest that is empty or not inside the frame, rows or ksize below 1,
+ * mask_frames other than 1 or F, tables that are not 4-byte aligned, or an out that overlaps any input.  A table entry that points outside
+ * its intermediate is cut to it (no read leaves a buffer).  No operand but the tables needs an alignment.  No atomics, a fixed grid: every
+ * output byte is written once, by one thread. */
+int anyv2v_restore_paste_u8(const void* source, const void* edit_h, const void* alpha_h, void* out, int32_t F, int32_t sh, int32_t sw,
+                            int32_t dx0, int32_t dy0, int32_t dx1, int32_t dy1, int32_t e_rows, const int32_t* e_bounds,
+                            const int32_t* e_coeffs, int32_t e_ksize, int32_t mask_frames, int32_t a_rows, const int32_t* a_bounds,
+                            const int32_t* a_coeffs, int32_t a_ksize, void* stream);
 
 /* Plain elementwise DDIM / inverse-DDIM step (eta = 0, v-prediction) on same-layout tensors:
  * the generic `scheduler.step(model_output, t, sample).prev_sample` (pipeline_i2vgen_xl.py:868,1173,1418). */
@@ -593,7 +622,7 @@ const char* anyv2v_last_error(void);
  * must still be recompiled against this header because the structure grew).  anyv2v_freeu_f16, anyv2v_tile_blend_f16, anyv2v_latent_mask_f16,
  * anyv2v_masked_blend_f16, anyv2v_diff_map_accum_f16, anyv2v_diff_map_finish_f16, anyv2v_pixel_alpha_f16, anyv2v_composite_stats_u8,
  * anyv2v_composite_u8, anyv2v_luma_u8, anyv2v_block_match_u8, anyv2v_flow_median_i16, anyv2v_mask_propagate_u8,
- * anyv2v_first_frame_mask_u8, anyv2v_resample_table, anyv2v_resample_h_u8 and anyv2v_resample_v_u8 were added under 105: new entry
+ * anyv2v_first_frame_mask_u8, anyv2v_resample_table, anyv2v_resample_h_u8, anyv2v_resample_v_u8 and anyv2v_restore_paste_u8 were added under 105: new entry
  * points, no structure changed
  * (a binding that needs them finds out when it resolves the symbol). */
 #define ANYV2V_ABI_VERSION 105
