@@ -100,6 +100,14 @@ class AttnDesc(C.Structure):
     ]
 
 
+class TattnDesc(C.Structure):
+    _fields_ = [
+        ("X", C.c_void_p), ("W", C.c_void_p), ("bias", C.c_void_p), ("ln_c1", C.c_void_p), ("O", C.c_void_p),
+        ("B", C.c_int32), ("F", C.c_int32), ("HW", C.c_int32), ("C", C.c_int32), ("heads", C.c_int32),
+        ("ldx", C.c_int32), ("ldo", C.c_int32), ("ln_eps", C.c_float), ("scale", C.c_float), ("flags", C.c_int32),
+    ]
+
+
 # every symbol include/anyv2v_hip.h declares: name -> (restype, argtypes)
 _VP, _I32, _I64, _F32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 SYMBOLS = {
@@ -121,6 +129,7 @@ SYMBOLS = {
     "anyv2v_attention_f16": (C.c_int, [C.POINTER(AttnDesc), _VP]),
     "anyv2v_attention_small_f16": (C.c_int, [C.POINTER(AttnDesc), _I32, _VP]),
     "anyv2v_attention_bias_f16": (C.c_int, [C.POINTER(AttnDesc), _I32, _VP, _VP]),
+    "anyv2v_temporal_qkv_attn_f16": (C.c_int, [C.POINTER(TattnDesc), _VP]),
     "anyv2v_softmax_rows_f32_f16": (C.c_int, [_VP, _I32, _VP, _I32, _I32, _I32, _F32, _VP]),
     "anyv2v_silu_f16": (C.c_int, [_VP, _VP, _I64, _VP]),
     "anyv2v_add_f16": (C.c_int, [_VP, _VP, _VP, _I64, _VP]),

@@ -21,6 +21,7 @@
 #include <type_traits>
 
 #include "attention_plan.h"
+#include "attn_short.h"
 #include "common.h"
 
 struct AttnK {
@@ -414,7 +415,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? (NV == 1 ? 4 : 2) : (NV == 1 ? (
 //                 2 KiB LDS image of V through ds_read_b64_tr_b16 (hardware 4x16 transpose; semantics pinned by
 //                 anyv2v_selftest): lane i of a 16-lane group supplies &V[4g + (i>>2)][d0 + 4(i&3)] and receives
 //                 V[4g + 0..3][d0 + i].
-typedef __fp16 fp16x4_t __attribute__((__vector_size__(8)));
+// (the per-sequence score / softmax / PV arithmetic is attn_short.h's, shared with the fused temporal kernel of tattn_fused.hip)
 
 // NB = 3: the PnP injection step (pnp_utils.py:295-302: the uncond / cond branches use the SOURCE branch's Q and K) as ONE wave per
 // (source element, head): Q, K are read and the softmax is taken once, then the three branches' V are applied one after the other --
@@ -458,30 +459,10 @@ __global__ __launch_bounds__(256) void short_attn_d64_kernel(const AttnK p) {
             vv[b][ps] = key < p.Sk ? *(const h8*)(p.V + (vbase + (long long)key * p.kv_seq) * p.ldv + h * 64 + (lane & 7) * 8) : zero8;
         }
     }
-    // S^T = K Q^T: D[key = 4 g + r][q = l15]
-    f4 s = {0.f, 0.f, 0.f, 0.f};
-    s = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf[0], qf[0], s, 0, 0, 0);
-    s = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf[1], qf[1], s, 0, 0, 0);
-    const float c = p.scale_log2;
-    float mx = -1e30f;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        if (4 * g + r >= p.Sk) s[r] = -1e30f;
-        mx = fmaxf(mx, s[r]);
-    }
-    mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-    float sum = 0.f;
+    // S^T = K Q^T: D[key = 4 g + r][q = l15], softmax over the keys (attn_short.h)
     h4 pf;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const float e = exp2f((s[r] - mx) * c);
-        sum += e;
-        pf[r] = (half_t)e;
-    }
-    sum += __shfl_xor(sum, 16, 64);
-    sum += __shfl_xor(sum, 32, 64);
-    const float inv = 1.0f / sum;
+    float inv;
+    short_attn_softmax(kf, qf, g, p.Sk, p.scale_log2, pf, inv);
     half_t* const ow = os[w];
 #pragma unroll
     for (int b = 0; b < NB; ++b) {
@@ -492,23 +473,9 @@ __global__ __launch_bounds__(256) void short_attn_d64_kernel(const AttnK p) {
         for (int ps = 0; ps < 2; ++ps) *(h8*)(&vs[w][(8 * ps + (lane >> 3)) * 64 + (lane & 7) * 8]) = vv[b][ps];
         // O^T[d][q] = sum_key V^T[d][key] P^T[key][q]
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        // The MFMA leaves lane (q = l15, g) with 4 of every 16 output channels: stored directly that is 32-byte pieces of 16
-        // different rows per instruction.  Turn the tile through LDS (row stride 144 bytes) so that 8 lanes write one
-        // full 128-byte row segment: two 1-KiB store instructions instead of four scattered 512-byte ones.
-#pragma unroll
-        for (int db = 0; db < 4; ++db) {
-            const half_t* src = &vs[w][(4 * g + (l15 >> 2)) * 64 + 16 * db + 4 * (l15 & 3)];
-            const fp16x4_t vt = __builtin_amdgcn_ds_read_tr16_b64_v4f16((__attribute__((address_space(3))) fp16x4_t*)src);
-            h4 vf;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) vf[j] = (half_t)vt[j];
-            f4 o = {0.f, 0.f, 0.f, 0.f};
-            o = __builtin_amdgcn_mfma_f32_16x16x16f16(vf, pf, o, 0, 0, 0);
-            h4 ov;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) ov[r] = (half_t)(o[r] * inv);
-            *(h4*)(ow + l15 * 72 + 16 * db + 4 * g) = ov;
-        }
+        // the output tile is turned through LDS (row stride 144 bytes): two 1-KiB store instructions instead of four scattered
+        // 512-byte ones (attn_short.h)
+        short_attn_pv(vs[w], ow, pf, inv, l15, g);
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
 #pragma unroll
         for (int ps = 0; ps < 2; ++ps) {

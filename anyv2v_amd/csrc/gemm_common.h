@@ -194,6 +194,39 @@ __device__ __forceinline__ void lgkm_wait(int n) {  // n is a constant after unr
     }
 }
 
+// ---- the arithmetic of the weight-stationary kernels' K-step and LayerNorm fold, shared by gemm_ws.hip and tattn_fused.hip: both
+// kernels call these, so a row's projection has the same bits whichever of them computes it (same MFMA shape, same K order, same
+// statistics, same fold).  D = W x^T: lane (token l & 15, l >> 4) holds output channels 4 (l >> 4) .. + 3 of a 16-channel fragment.
+// one weight fragment against the two 16-token halves of a strip
+__device__ __forceinline__ void ws_mfma_pair(const h8& wfr, const h8& x0, const h8& x1, f4& acc0, f4& acc1) {
+    acc0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(wfr, x0, acc0, 0, 0, 0);
+    acc1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(wfr, x1, acc1, 0, 0, 0);
+}
+// row statistics of one K-step out of the matrix pipe: the activation fragment with itself (Gram matrix: its diagonal is sum x^2)
+// and with a fragment of ones (sum x)
+__device__ __forceinline__ void ws_ln_stats_step(const h8& x, const h8& ones, f4& accq, f4& accs) {
+    accq = __builtin_amdgcn_mfma_f32_16x16x32_f16(x, x, accq, 0, 0, 0);
+    accs = __builtin_amdgcn_mfma_f32_16x16x32_f16(ones, x, accs, 0, 0, 0);
+}
+// mean / rstd of token l15 over K channels from the two statistics accumulators.  D[i][j] of the Gram MFMA sits in lane (j = l15,
+// lq = i >> 2), register i & 3: token j's own sum x^2 is register l15 & 3 of the lane with lq == l15 >> 2 -- select, then fetch it
+// from that lane; sum x is in every register
+template <int K>
+__device__ __forceinline__ void ws_ln_row_stats(const f4& accq, const f4& accs, int l15, float eps, float& mean_out, float& rstd_out) {
+    const int r3 = l15 & 3;
+    float d = r3 == 0 ? accq[0] : (r3 == 1 ? accq[1] : (r3 == 2 ? accq[2] : accq[3]));
+    d = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(((l15 >> 2) * 16 + l15) * 4, __builtin_bit_cast(int, d)));
+    const float mean = accs[0] * (1.0f / K);
+    const float var = fmaxf(d * (1.0f / K) - mean * mean, 0.0f);
+    mean_out = mean;
+    rstd_out = __builtin_amdgcn_rsqf(var + eps);
+}
+// LN(x) W^T + b = rstd (x W'^T - mean c1) + b' on one accumulator fragment
+__device__ __forceinline__ void ws_ln_fold(f4& acc, const f4& c1, const h4& b, float mean, float rstd) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) acc[r] = fmaf(fmaf(-mean, c1[r], acc[r]), rstd, (float)b[r]);
+}
+
 // accumulator element -> VGPR, AT the use (one-wave kernels, accumulators in AGPRs): left to hipcc, the AGPR -> VGPR copies of all 240
 // accumulators are hoisted to the top of the epilogue (they are copies of phi values), which overflows the 256 arch VGPRs into AGPRs
 // and the accumulators into scratch

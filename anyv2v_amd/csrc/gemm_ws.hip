@@ -199,13 +199,9 @@ __global__ __launch_bounds__(512) void gemm_ws_kernel(const GemmK p, const WsPla
         for (int nf = 0; nf < WS_NF; ++nf) {   // (two nested fully unrolled loops: one flat loop of 128 iterations is only partly unrolled)
             const int idx = s * WS_NF + nf;
             if (idx + WQ - 1 < NFR) wq[(idx + WQ - 1) % WQ] = wfrag(idx + WQ - 1);
-            acc[0][nf] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wq[idx % WQ], fr[s & 1][0], acc[0][nf], 0, 0, 0);
-            acc[1][nf] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wq[idx % WQ], fr[s & 1][1], acc[1][nf], 0, 0, 0);
+            ws_mfma_pair(wq[idx % WQ], fr[s & 1][0], fr[s & 1][1], acc[0][nf], acc[1][nf]);
             if constexpr (LN) {
-                if (nf == 4 || nf == 5) {   // row statistics of this K-step, row block nf - 4
-                    accq[nf - 4] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fr[s & 1][nf - 4], fr[s & 1][nf - 4], accq[nf - 4], 0, 0, 0);
-                    accs[nf - 4] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ones, fr[s & 1][nf - 4], accs[nf - 4], 0, 0, 0);
-                }
+                if (nf == 4 || nf == 5) ws_ln_stats_step(fr[s & 1][nf - 4], ones, accq[nf - 4], accs[nf - 4]);   // row statistics of this K-step, row block nf - 4
             }
             if (nf == 2 && s + 1 < WS_KS) {   // next K-step's fragments, seven MFMA pairs ahead of their first use
                 fr[(s + 1) & 1][0] = to_frag(a[(s + 1) % WS_R][0]);
@@ -230,26 +226,14 @@ __global__ __launch_bounds__(512) void gemm_ws_kernel(const GemmK p, const WsPla
         float ln_mean[2] = {0.f, 0.f}, ln_rstd[2] = {1.f, 1.f};
         if constexpr (LN) {
 #pragma unroll
-            for (int mf = 0; mf < 2; ++mf) {
-                // D[i][j] of the Gram MFMA sits in lane (j = l15, lq = i >> 2), register i & 3: token j's own sum x^2 is register
-                // l15 & 3 of the lane with lq == l15 >> 2 -- select, then fetch it from that lane; sum x is in every register
-                const int r3 = l15_e & 3;
-                float d = r3 == 0 ? accq[mf][0] : (r3 == 1 ? accq[mf][1] : (r3 == 2 ? accq[mf][2] : accq[mf][3]));
-                d = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(((l15_e >> 2) * 16 + l15_e) * 4, __builtin_bit_cast(int, d)));
-                const float mean = accs[mf][0] * (1.0f / WS_K);
-                const float var = fmaxf(d * (1.0f / WS_K) - mean * mean, 0.0f);
-                ln_mean[mf] = mean;
-                ln_rstd[mf] = __builtin_amdgcn_rsqf(var + p.ln_eps);
-            }
+            for (int mf = 0; mf < 2; ++mf) ws_ln_row_stats<WS_K>(accq[mf], accs[mf], l15_e, p.ln_eps, ln_mean[mf], ln_rstd[mf]);
 #pragma unroll
             for (int mf = 0; mf < 2; ++mf)
 #pragma unroll
                 for (int nf = 0; nf < WS_NF; ++nf) {
                     const f4 c1 = *(const f4*)((const char*)bias_l + WS_NS * 2 + (nf * 16 + 4 * lq_e) * 4);
                     const h4 b = *(const h4*)(bias_l + nf * 16 + 4 * lq_e);
-#pragma unroll
-                    for (int r = 0; r < 4; ++r)
-                        acc[mf][nf][r] = fmaf(fmaf(-ln_mean[mf], c1[r], acc[mf][nf][r]), ln_rstd[mf], (float)b[r]);
+                    ws_ln_fold(acc[mf][nf], c1, b, ln_mean[mf], ln_rstd[mf]);
                 }
         }
 #pragma unroll

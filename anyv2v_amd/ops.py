@@ -374,6 +374,56 @@ def attention(q, k, v, out, *, batch, heads, Sq, Sk, inner=1, q_strides, kv_stri
     return out
 
 
+# A/B switch: temporal self-attention with its QKV projection inside (tattn_fused.hip) vs the LayerNorm-folded QKV GEMM + attention
+TATTN_FUSED_DEFAULT = "1"
+
+
+def tattn_fused_enabled() -> bool:
+    """ANYV2V_TATTN_FUSED, read when asked (a test or an A/B run flips it without re-importing the package)."""
+    return os.environ.get("ANYV2V_TATTN_FUSED", TATTN_FUSED_DEFAULT).strip() == "1"
+
+
+TATTN_MIN_ROWS = 32768   # rows of one branch from which the LayerNorm-folded weight-stationary GEMM is taken (csrc/tattn_plan.h)
+
+
+def temporal_qkv_attn_supported(rows_per_branch: int, C: int, heads: int, F: int, HW: int, x: Optional[torch.Tensor] = None) -> bool:
+    """Where ``temporal_qkv_attn`` stands for ``gemm(x, W', bias=b', ln=...)`` + ``attention`` (bit-equal) AND pays: the plan of
+    csrc/tattn_plan.cpp (16 frames, 320 channels = 5 heads of 64, even HW) from the row count at which the two launches take the
+    weight-stationary path.  ``rows_per_branch``: the rows of ONE batch element (F * HW), as ``_fold(..., per_branch=True)`` sees
+    them -- every engine decides alike whatever batch it runs.  ``x``: the operand; a tensor off the GPU says no."""
+    if not tattn_fused_enabled() or FORCE_NAIVE or not USE_GLDS or (x is not None and not x.is_cuda):
+        return False
+    if GEMM_FLAGS & (_lib.ANYV2V_GEMM_NO_WS | _lib.ANYV2V_GEMM_NO_BIG) or ATTN_FLAGS & 3:   # the two launches would not be the ones it equals
+        return False
+    return (F == 16 and C == 320 and heads == 5 and HW > 0 and HW % 2 == 0 and rows_per_branch == F * HW
+            and rows_per_branch >= TATTN_MIN_ROWS)
+
+
+def temporal_qkv_attn(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, c1: torch.Tensor, eps: float, *, B: int, F: int, HW: int,
+                      heads: int, scale: float = 0.125, out: Optional[torch.Tensor] = None):
+    """out[(b f) hw, C] = temporal attention of QKV = LN-folded ``x`` W'^T + b' (``ln_fold`` operands, W' = [Wq; Wk; Wv] diag(gamma))
+    in one kernel (``anyv2v_temporal_qkv_attn_f16``): the QKV tensor is never written.  Shapes outside the kernel's coverage are an
+    error, not a fallback -- ask ``temporal_qkv_attn_supported`` first."""
+    lib = _lib.load()
+    _rowmajor(x, "X")
+    _rowmajor(w, "W")
+    Cc = x.shape[1]
+    assert x.shape[0] == B * F * HW and tuple(w.shape) == (3 * Cc, Cc) and w.is_contiguous()
+    assert bias is not None and bias.dtype == torch.float16 and bias.is_cuda and bias.numel() == 3 * Cc and bias.is_contiguous()
+    assert c1.dtype == torch.float32 and c1.is_cuda and c1.numel() == 3 * Cc and c1.is_contiguous()
+    if out is None:
+        out = torch.empty((x.shape[0], Cc), dtype=torch.float16, device=x.device)
+    _rowmajor(out, "O")
+    assert out.shape[0] == x.shape[0] and out.shape[1] == Cc
+    d = _lib.TattnDesc()
+    d.X, d.W, d.bias, d.ln_c1, d.O = _p(x), _p(w), _p(bias), _p(c1), _p(out)
+    d.B, d.F, d.HW, d.C, d.heads = B, F, HW, Cc, heads
+    d.ldx, d.ldo = x.stride(0), out.stride(0)
+    d.ln_eps, d.scale, d.flags = float(eps), float(scale), 0
+    _lib.check(lib.anyv2v_temporal_qkv_attn_f16(C.byref(d), _stream()), "anyv2v_temporal_qkv_attn_f16")
+    return out
+
+
 def silu(x: torch.Tensor, out=None):
     lib = _lib.load()
     assert x.is_contiguous() and x.dtype == torch.float16

@@ -289,6 +289,13 @@ class HipAttnProcessor:
         o = torch.empty((T, Cq), dtype=torch.float16, device=h.device)
         if kv is None:  # self-attention
             inject = pnp_on(self.t, self.injection_schedule)
+            if (ln_in is not None and geom.kind == "temporal" and not inject and self.src_io is None
+                    and ops.temporal_qkv_attn_supported(T // geom.B, Cq, attn.heads, geom.F, geom.HW, h)):
+                # plain temporal self-attention at the 64x64 level: projection and attention in one kernel, bit-equal to the two
+                # launches below (tattn_fused.hip) -- QKV never reaches HBM; one branch's rows decide, as in ``_fold``
+                ops.temporal_qkv_attn(h, w_in, b_in, c1_in, ln_eps, B=geom.B, F=geom.F, HW=geom.HW, heads=attn.heads, scale=attn.scale,
+                                      out=o)
+                return ops.gemm(o, attn.to_out[0].weight, bias=attn.to_out[0].bias, residual=residual)
             io = self.src_io if inject else None
             if io is not None and io[0] == "replay":
                 # [negative, editing] with the source branch's Q, K from the cache: only V is projected here; the kernel aliases

@@ -258,6 +258,31 @@ int anyv2v_attention_small_f16(const AnyV2VAttnDesc* d, int32_t head_dim, void* 
  * (seine/models/attention.py:815-817,870-889; seine/pnp_utils.py:386-451 is its hooked form).  Generic kernel, head_dim <= 160. */
 int anyv2v_attention_bias_f16(const AnyV2VAttnDesc* d, int32_t head_dim, const float* bias, void* stream);
 
+/* Temporal self-attention with its LayerNorm-folded QKV projection inside (plain form: every batch element attends with its own
+ * Q and K): O = attention(QKV) with QKV = rstd (X W^T - mean ln_c1) + bias as anyv2v_gemm_f16 computes it with ln_c1 set, for the token
+ * matrix X [(B F) HW][ldx] of TransformerTemporalModel: sequence (b, pixel) is rows b F HW + pixel + f HW, f = 0..F-1.  W [3 C][C] =
+ * [Wq; Wk; Wv] diag(gamma) (fp16), bias [3 C] (fp16), ln_c1 [3 C] (fp32) as for AnyV2VGemmDesc; head h reads rows 64 h .. 64 h + 63 of
+ * each third and writes columns [64 h, 64 h + 64) of O [(B F) HW][ldo].  The [rows, 3 C] QKV tensor is never written.  Bit for bit the
+ * result of anyv2v_gemm_f16 (weight-stationary LayerNorm-fold kernel) followed by anyv2v_attention_f16 (temporal strides) on the same
+ * operands; a row's result does not depend on what else is in the launch.  Implemented for F = 16, C = 320, heads = 5 (head_dim 64),
+ * even HW; anything else returns ANYV2V_EUNSUPPORTED and the caller runs the two launches.  X, O, W, ln_c1 16-byte aligned, bias
+ * 8-byte aligned, ldx and ldo multiples of 8. */
+typedef struct AnyV2VTattnDesc {
+    const void* X;
+    const void* W;
+    const void* bias;
+    const float* ln_c1;
+    void* O;
+    int32_t B, F, HW;
+    int32_t C, heads;
+    int32_t ldx, ldo;
+    float ln_eps;
+    float scale;         /* softmax scale, 1 / sqrt(64) */
+    int32_t flags;       /* reserved, 0 */
+} AnyV2VTattnDesc;
+
+int anyv2v_temporal_qkv_attn_f16(const AnyV2VTattnDesc* d, void* stream);
+
 /* ---- elementwise / layout --------------------------------------------------------------------- */
 /* y = silu(x) (n elements) */
 int anyv2v_silu_f16(const void* X, void* Y, int64_t n, void* stream);

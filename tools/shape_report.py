@@ -86,6 +86,12 @@ def main():
         return ((M, C, H, "res" if residual is not None else ""), 2.0 * M * (2 * H * C + H * C),
                 (M * C * (3 if residual is not None else 2) + 3 * H * C) * 2.0)
 
+    def tattn_key(x, w, bias, c1, eps, *, B, F, HW, heads, scale=0.125, out=None):
+        M, C = x.shape   # QKV projection + 16 x 16 attention per (pixel, head); x read once, O written once, W' once
+        return ((B, F, HW, C, heads), 2.0 * M * 3 * C * C + 4.0 * B * HW * heads * F * F * 64, (2 * M * C + 3 * C * C) * 2.0)
+
+    saved_tattn = ops.temporal_qkv_attn
+    ops.temporal_qkv_attn = rec("tattn_fused", ops.temporal_qkv_attn, tattn_key)
     saved_ff = ops.ff_geglu
     ops.ff_geglu = rec("ff_fused", ops.ff_geglu, ff_key)
     saved = (ops.gemm, ops.groupnorm, ops.layernorm, ops.attention)
@@ -94,6 +100,7 @@ def main():
     pipe.unet(sample, t, **cond)
     ops.gemm, ops.groupnorm, ops.layernorm, ops.attention = saved
     ops.ff_geglu = saved_ff
+    ops.temporal_qkv_attn = saved_tattn
     torch.cuda.synchronize()
 
     # whole-forward eager time for reference
