@@ -78,6 +78,8 @@ TRACK_MAX_RADIUS = 32
 # anyv2v_resample_table: the filters (Pillow's Image.Resampling numbers) and the largest side (ANYV2V_RESAMPLE_* of include/anyv2v_hip.h)
 RESAMPLE_FILTERS = {"lanczos": 1, "bilinear": 2, "bicubic": 3, "box": 4}
 RESAMPLE_MAX_SIDE = 16384
+# anyv2v_detail_gate_u8: the largest box radius (ANYV2V_DETAIL_MAX_RADIUS of include/anyv2v_hip.h)
+DETAIL_MAX_RADIUS = 16
 
 
 class FFDesc(C.Structure):
@@ -162,6 +164,9 @@ SYMBOLS = {
     "anyv2v_resample_v_u8": (C.c_int, [_VP, _VP, _I32, _I32, _I32, _I32, _I32, _VP, _VP, _I32, _VP]),
     "anyv2v_restore_paste_u8": (C.c_int, [_VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _VP, _VP, _I32, _I32, _I32, _VP, _VP,
                                           _I32, _VP]),
+    "anyv2v_detail_gate_u8": (C.c_int, [_VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _I32, _VP, _I64, _VP]),
+    "anyv2v_restore_detail_u8": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _VP, _VP, _I32, _I32, _I32,
+                                           _I32, _VP, _VP, _I32, _VP]),
     "anyv2v_ddim_step_f16": (C.c_int, [_VP, _VP, _VP, _F32, _F32, _F32, _F32, _I64, _VP]),
     "anyv2v_guided_step_f16": (C.c_int, [_VP, _I64, _I32, _I32, _I32, _F32, _F32, _I32, _F32, _F32, _F32, _F32, _VP, _VP, _VP]),
     "anyv2v_guided_step_noise_f16": (C.c_int, [_VP, _I64, _I32, _I32, _I32, _F32, _F32, _I32, _F32, _F32, _F32, _F32, _VP, _VP, _VP, _F32, _VP]),

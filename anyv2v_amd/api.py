@@ -101,6 +101,7 @@ class AnyV2V_I2VGenXL:
         # 512 x 512) of ``inverse_config`` (``prepare.plan_from_config``): a clip of any size is cropped and resized on the GPU first;
         # absent, the clip runs at the size its frames have
         # ``pnp_config`` takes ``source_restore`` / ``source_restore_resample`` beside them: the result is written at the clip's own size
+        # (with ``source_restore_detail`` and its ``_lo`` / ``_hi`` / ``_radius``: carrying the source's fine detail where the edit kept the content)
         source_plan = prepare_plan_from_config(cfg.inverse_config, restore_config=cfg.pnp_config)
         source = frame_list   # the clip at its own size
         if source_plan is not None:
@@ -175,7 +176,7 @@ class AnyV2V_I2VGenXL:
         if source_plan is not None and source_plan.restore:
             alpha = self.pipe.composite_alpha(mask, grow=plan.grow, feather=plan.feather, grow_px=plan.composite["grow_px"],
                                               feather_px=plan.composite["feather_px"]) if comp else None
-            edited_video = source_plan.restored(self.pipe, edited_video, source, alpha, prepared_from=source[0].size)
+            edited_video = source_plan.restored(self.pipe, edited_video, source, alpha, prepared_from=source[0].size, prepared=frame_list)
         else:
             edited_video = [f.resize(tuple(cfg.inverse_config.image_size), resample=Image.LANCZOS) for f in edited_video]
         output_path = os.path.join(tmp_dir, "edited_video.mp4")

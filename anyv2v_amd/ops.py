@@ -1033,7 +1033,14 @@ def restore_u8(edited_u8: torch.Tensor, source_u8: torch.Tensor, dest, box, resa
     sh, sw = int(source_u8.shape[1]), int(source_u8.shape[2])
     dest = _dest(dest, sh, sw, "restore_u8")
     dw = dest[2] - dest[0]
-    dev = edited_u8.device
+    pe, pa = _restore_device_passes(h, w, dest, box, resample, edited_u8.device)
+    edit_h = _restore_horizontal(edited_u8, pe, dw)
+    alpha_h = None if alpha_u8 is None else _restore_horizontal(alpha_u8[..., None], pa, dw)[..., 0]
+    return restore_paste_u8(source_u8, edit_h, alpha_h, dest, pe[3], None if alpha_u8 is None else pa[3])
+
+
+def _restore_device_passes(h, w, dest, box, resample, dev):
+    """``restore_passes`` with the tables on ``dev``, cached per geometry and device."""
     key = (h, w, dest, tuple(box) if isinstance(box, (tuple, list)) else box, resample, str(dev))
     if key not in _RESTORE_DEVICE:
         passes = restore_passes(h, w, dest, box, resample)
@@ -1041,20 +1048,86 @@ def restore_u8(edited_u8: torch.Tensor, source_u8: torch.Tensor, dest, box, resa
             _RESTORE_DEVICE.clear()
         on = lambda t: None if t is None else (t[0], t[1].to(dev), t[2].to(dev))
         _RESTORE_DEVICE[key] = tuple((row0, rows, on(hp), on(vp)) for row0, rows, hp, vp in passes)
-    lib = _lib.load()
+    return _RESTORE_DEVICE[key]
 
-    def horizontal(x, p):   # x: [N, h, w, C] -> [N, rows, dw, C]
-        row0, rows, hp, _ = p
-        if hp is None:
-            return x[:, row0:row0 + rows].contiguous()
-        y = torch.empty((x.shape[0], rows, dw, x.shape[3]), dtype=torch.uint8, device=dev)
-        _lib.check(lib.anyv2v_resample_h_u8(_p(x), _p(y), int(x.shape[0]), h, w, int(x.shape[3]), row0, rows, dw, _p(hp[1]), _p(hp[2]), hp[0],
-                                            _stream()), "anyv2v_resample_h_u8")
-        return y
-    pe, pa = _RESTORE_DEVICE[key]
-    edit_h = horizontal(edited_u8, pe)
-    alpha_h = None if alpha_u8 is None else horizontal(alpha_u8[..., None], pa)[..., 0]
-    return restore_paste_u8(source_u8, edit_h, alpha_h, dest, pe[3], None if alpha_u8 is None else pa[3])
+
+def _restore_horizontal(x, p, dw):
+    """The horizontal pass of one operand of the way back: x uint8 [N, h, w, C] -> [N, rows, dw, C] (a copy of the rows where Pillow skips it)."""
+    row0, rows, hp, _ = p
+    if hp is None:
+        return x[:, row0:row0 + rows].contiguous()
+    N, h, w, Cc = (int(v) for v in x.shape)
+    y = torch.empty((N, rows, dw, Cc), dtype=torch.uint8, device=x.device)
+    _lib.check(_lib.load().anyv2v_resample_h_u8(_p(x), _p(y), N, h, w, Cc, row0, rows, dw, _p(hp[1]), _p(hp[2]), hp[0], _stream()),
+               "anyv2v_resample_h_u8")
+    return y
+
+
+def detail_gate_u8(edit_u8: torch.Tensor, prepared_u8: torch.Tensor, lo: int = 8, hi: int = 32, radius: int = 2):
+    """Where the edit stayed close to the prepared source (``anyv2v_detail_gate_u8``; the definition is in ``include/anyv2v_hip.h``): both
+    contiguous uint8 [F, h, w, 3] on the GPU -> uint8 [F, h, w], 255 where the mean over a ``(2 radius + 1)^2`` box of ``max_c |E - P|`` is
+    at most ``lo``, 0 where it is at least ``hi``, a linear ramp between.  Integers, ``0 <= lo < hi <= 255``, ``0 <= radius <= 16``.  Two
+    launches (row sums into a uint16 scratch, column sums and the ramp)."""
+    ok = lambda t: isinstance(t, torch.Tensor) and t.dtype == torch.uint8 and t.dim() == 4 and t.is_contiguous() and t.is_cuda \
+        and t.shape[0] >= 1 and t.shape[3] == 3
+    got = lambda t: f"{tuple(t.shape)} {t.dtype} on {t.device}" if isinstance(t, torch.Tensor) else type(t).__name__
+    if not ok(edit_u8):
+        raise ValueError(f"detail_gate_u8: edit_u8: a contiguous uint8 [F, h, w, 3] tensor on the GPU expected, got {got(edit_u8)}")
+    if not (ok(prepared_u8) and prepared_u8.shape == edit_u8.shape and prepared_u8.device == edit_u8.device):
+        raise ValueError(f"detail_gate_u8: prepared_u8: a contiguous uint8 {list(edit_u8.shape)} tensor on {edit_u8.device} expected, "
+                         f"got {got(prepared_u8)}")
+    lo, hi, radius = detail_parameters(lo, hi, radius, "detail_gate_u8: ")
+    F, h, w, _ = (int(v) for v in edit_u8.shape)
+    out = torch.empty((F, h, w), dtype=torch.uint8, device=edit_u8.device)
+    scratch = torch.empty((F, h, w), dtype=torch.int16, device=edit_u8.device)
+    _lib.check(_lib.load().anyv2v_detail_gate_u8(_p(edit_u8), _p(prepared_u8), _p(out), F, h, w, lo, hi, radius, _p(scratch), 2 * scratch.numel(),
+                                                 _stream()), "anyv2v_detail_gate_u8")
+    return out
+
+
+def detail_parameters(lo, hi, radius, what=""):
+    """The gate's parameters as integers, or a ``ValueError``: ``0 <= lo < hi <= 255``, ``0 <= radius <= 16``."""
+    whole = lambda v: not isinstance(v, bool) and isinstance(v, (int, float)) and int(v) == v
+    if not (whole(lo) and whole(hi) and 0 <= lo < hi <= 255):
+        raise ValueError(f"{what}lo={lo!r}, hi={hi!r}: integers, 0 <= lo < hi <= 255")
+    if not (whole(radius) and 0 <= radius <= _lib.DETAIL_MAX_RADIUS):
+        raise ValueError(f"{what}radius={radius!r}: an integer, 0 <= radius <= {_lib.DETAIL_MAX_RADIUS}")
+    return int(lo), int(hi), int(radius)
+
+
+def restore_detail_u8(edited_u8: torch.Tensor, prepared_u8: torch.Tensor, gate_u8: torch.Tensor, source_u8: torch.Tensor, dest, box,
+                      resample: str = "lanczos", alpha_u8: Optional[torch.Tensor] = None):
+    """``restore_u8`` with the source's fine detail carried into the upscaled edit (``anyv2v_restore_detail_u8``; the definition is in
+    ``include/anyv2v_hip.h``): ``prepared_u8`` uint8 [F, h, w, 3] is the frame the model saw (``prepare_frames`` of the source), ``gate_u8``
+    uint8 [1 or F, h, w] says where the detail ``S - up(P)`` is added (255) and where not (0) -- ``detail_gate_u8`` makes one, any other is
+    taken as it is.  A gate of 0 gives ``restore_u8``; ``edited_u8 == prepared_u8`` under a gate of 255 gives the source.  Up to five
+    launches: ``anyv2v_resample_h_u8`` on the edit, the prepared source, the gate and alpha, then ``anyv2v_restore_detail_u8``."""
+    ok = lambda t, nd: isinstance(t, torch.Tensor) and t.dtype == torch.uint8 and t.dim() == nd and t.is_contiguous() and t.is_cuda and t.shape[0] >= 1
+    got = lambda t: f"{tuple(t.shape)} {t.dtype} on {t.device}" if isinstance(t, torch.Tensor) else type(t).__name__
+    if not (ok(edited_u8, 4) and edited_u8.shape[3] == 3):
+        raise ValueError(f"restore_detail_u8: edited_u8: a contiguous uint8 [F, h, w, 3] tensor on the GPU expected, got {got(edited_u8)}")
+    F, h, w, _ = (int(v) for v in edited_u8.shape)
+    dev = edited_u8.device
+    if not (ok(prepared_u8, 4) and prepared_u8.shape == edited_u8.shape and prepared_u8.device == dev):
+        raise ValueError(f"restore_detail_u8: prepared_u8: a contiguous uint8 [{F}, {h}, {w}, 3] tensor on {dev} expected, got {got(prepared_u8)}")
+    if not (ok(source_u8, 4) and source_u8.shape[3] == 3 and source_u8.shape[0] == F and source_u8.device == dev):
+        raise ValueError(f"restore_detail_u8: source_u8: a contiguous uint8 [{F}, sh, sw, 3] tensor on {dev} expected, got {got(source_u8)}")
+    for name, t in (("gate_u8", gate_u8),) + (() if alpha_u8 is None else (("alpha_u8", alpha_u8),)):
+        if not (ok(t, 3) and t.shape[0] in (1, F) and tuple(t.shape[1:]) == (h, w) and t.device == dev):
+            raise ValueError(f"restore_detail_u8: {name}: a contiguous uint8 [1 or {F}, {h}, {w}] tensor on {dev} expected, got {got(t)}")
+    sh, sw = int(source_u8.shape[1]), int(source_u8.shape[2])
+    dx0, dy0, dx1, dy1 = dest = _dest(dest, sh, sw, "restore_detail_u8")
+    dw = dx1 - dx0
+    pe, pa = _restore_device_passes(h, w, dest, box, resample, dev)
+    edit_h, prep_h = _restore_horizontal(edited_u8, pe, dw), _restore_horizontal(prepared_u8, pe, dw)
+    gate_h = _restore_horizontal(gate_u8[..., None], pa, dw)
+    alpha_h = None if alpha_u8 is None else _restore_horizontal(alpha_u8[..., None], pa, dw)
+    out = torch.empty_like(source_u8)
+    _lib.check(_lib.load().anyv2v_restore_detail_u8(_p(source_u8), _p(edit_h), _p(prep_h), _p(gate_h), _p(alpha_h), _p(out), F, sh, sw, dx0, dy0,
+                                                    dx1, dy1, int(edit_h.shape[1]), _p(pe[3][1]), _p(pe[3][2]), pe[3][0], int(gate_u8.shape[0]),
+                                                    1 if alpha_u8 is None else int(alpha_u8.shape[0]), int(gate_h.shape[1]), _p(pa[3][1]),
+                                                    _p(pa[3][2]), pa[3][0], _stream()), "anyv2v_restore_detail_u8")
+    return out
 
 
 def ddim_step(v: torch.Tensor, x: torch.Tensor, sa_t: float, sb_t: float, sa_p: float, sb_p: float, out=None):

@@ -318,6 +318,17 @@ class I2VGenXLPipeline(MaskedEditMixin):
             raise NotImplementedError("restore on a frame-parallel clip: the composite it follows is refused there")
         return prepare.restore_frames(edited, source_frames, fit, x_offset, y_offset, resample, alpha, device=self._execution_device)
 
+    def restore_frames_detail(self, edited, source_frames, prepared=None, fit="crop", x_offset=0.0, y_offset=0.0, resample="lanczos", alpha=None,
+                              source_resample="lanczos", gate_lo=8, gate_hi=32, gate_radius=2):
+        """``restore_frames`` with the source's fine detail carried into the upscaled edit wherever the edit stayed close to ``prepared``,
+        the frames the model saw (None: ``prepare_frames`` of the source with ``source_resample``); an edit that changes nothing gives the
+        source back byte for byte (``anyv2v_amd.prepare.restore_frames_detail``).  The gate's defaults are not validated on real edits."""
+        from . import prepare
+        if getattr(self.unet, "frame_parallel", None) is not None:
+            raise NotImplementedError("restore on a frame-parallel clip: the composite it follows is refused there")
+        return prepare.restore_frames_detail(edited, source_frames, prepared, fit, x_offset, y_offset, resample, alpha, source_resample, gate_lo,
+                                             gate_hi, gate_radius, device=self._execution_device)
+
     def encode_vae_video(self, video, device, height=576, width=1024):
         vae = self._need("vae")
         return vae.encode_video(video, device, height, width)

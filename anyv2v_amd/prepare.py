@@ -7,7 +7,9 @@ reference's top-level ``prepare_video.py`` (``crop_and_resize_video``).  The res
 its own device); ``restore_geometry`` is its inverse and ``restore_frames`` the way back to the source's own size, Pillow's
 ``paste(resize(.., box), xy, mask)`` byte for byte (``ops.restore_u8``); ``plan_from_config`` is the only reader of the OPTIONAL keys
 ``source_fit`` / ``source_x_offset`` / ``source_y_offset`` / ``source_resample`` / ``source_size`` / ``source_restore`` /
-``source_restore_resample``, which the reference's files do not have: absent, nothing here runs."""
+``source_restore_resample`` / ``source_restore_detail`` (with ``_lo`` / ``_hi`` / ``_radius``), which the reference's files do not have:
+absent, nothing here runs.  ``restore_frames_detail`` is ``restore_frames`` with the source's fine detail carried into the upscaled edit
+where the edit left the content alone (``ops.detail_gate_u8``, ``ops.restore_detail_u8``)."""
 from __future__ import annotations
 
 import os
@@ -131,17 +133,48 @@ def restore_frames(edited, source_frames, fit="crop", x_offset=0.0, y_offset=0.0
     if s.shape[0] != F:
         raise ValueError(f"restore_frames: {F} edited frames against {s.shape[0]} source frames")
     dest, box = restore_geometry((int(s.shape[2]), int(s.shape[1])), (w, h), fit, x_offset, y_offset)
-    a = None
-    if alpha is not None:
-        if not isinstance(alpha, torch.Tensor) or not alpha.is_floating_point() or alpha.dim() != 3 or alpha.shape[0] not in (1, F) \
-                or tuple(alpha.shape[1:]) != (h, w):
-            got = f"{tuple(alpha.shape)} {alpha.dtype}" if isinstance(alpha, torch.Tensor) else type(alpha).__name__
-            raise ValueError(f"restore_frames: alpha: a float [1 or {F}, {h}, {w}] tensor expected, got {got}")
-        a = alpha.to(device=device, dtype=torch.float32)
-        if not bool(((a >= 0.0) & (a <= 1.0)).all()):   # (false for NaN)
-            raise ValueError("restore_frames: alpha must lie in [0, 1]")
-        a = torch.round(a * 255.0).to(torch.uint8).contiguous()
-    return ops.restore_u8(e, s, dest, box, resample, a)
+    return ops.restore_u8(e, s, dest, box, resample, _alpha_u8(alpha, F, h, w, device, "restore_frames"))
+
+
+def _alpha_u8(alpha, F, h, w, device, what):
+    """The alpha of the way back: None, or fp32 [1 or F, h, w] in [0, 1] -> uint8 on ``device`` by ``rint(255 alpha)``."""
+    if alpha is None:
+        return None
+    if not isinstance(alpha, torch.Tensor) or not alpha.is_floating_point() or alpha.dim() != 3 or alpha.shape[0] not in (1, F) \
+            or tuple(alpha.shape[1:]) != (h, w):
+        got = f"{tuple(alpha.shape)} {alpha.dtype}" if isinstance(alpha, torch.Tensor) else type(alpha).__name__
+        raise ValueError(f"{what}: alpha: a float [1 or {F}, {h}, {w}] tensor expected, got {got}")
+    a = alpha.to(device=device, dtype=torch.float32)
+    if not bool(((a >= 0.0) & (a <= 1.0)).all()):   # (false for NaN)
+        raise ValueError(f"{what}: alpha must lie in [0, 1]")
+    return torch.round(a * 255.0).to(torch.uint8).contiguous()
+
+
+def restore_frames_detail(edited, source_frames, prepared=None, fit="crop", x_offset=0.0, y_offset=0.0, resample="lanczos", alpha=None,
+                          source_resample="lanczos", gate_lo=8, gate_hi=32, gate_radius=2, device="cuda"):
+    """``restore_frames`` that gives the source's fine detail back: with ``P`` the prepared source (the frames the model saw), ``S - up(P)``
+    is the detail the trip down and up destroys, and it is added to the upscaled edit wherever the edit stayed close to ``P``
+    (``ops.detail_gate_u8``: the mean over a ``(2 gate_radius + 1)^2`` box of ``max_c |E - P|``, full at ``gate_lo`` and below, none at
+    ``gate_hi`` and above), so that old texture does not ghost into new content.  An edit that changes nothing restores the source byte
+    for byte.  ``prepared``: uint8 [F, h, w, 3] or F PIL images of the edit's size, or None: the source is prepared on the spot with
+    ``source_resample``.  Everything else as in ``restore_frames`` -> uint8 [F, sh, sw, 3] on ``device``."""
+    what = "restore_frames_detail"
+    e = _frames_tensor(edited, device, f"{what}: edited")
+    s = _frames_tensor(source_frames, device, f"{what}: source_frames")
+    F, h, w, _ = (int(v) for v in e.shape)
+    if s.shape[0] != F:
+        raise ValueError(f"{what}: {F} edited frames against {s.shape[0]} source frames")
+    lo, hi, radius = ops.detail_parameters(gate_lo, gate_hi, gate_radius, f"{what}: gate: ")
+    if prepared is None:
+        p = prepare_frames(s, h, w, fit, x_offset, y_offset, source_resample, device=device)
+    else:
+        p = _frames_tensor(prepared, device, f"{what}: prepared")
+        if p.shape != e.shape:
+            raise ValueError(f"{what}: prepared frames of {tuple(p.shape)} against edited frames of {tuple(e.shape)}: the same clip at the same "
+                             "working size expected")
+    dest, box = restore_geometry((int(s.shape[2]), int(s.shape[1])), (w, h), fit, x_offset, y_offset)
+    a = _alpha_u8(alpha, F, h, w, device, what)
+    return ops.restore_detail_u8(e, p, ops.detail_gate_u8(e, p, lo, hi, radius), s, dest, box, resample, a)
 
 
 # ------------------------------------------------------------------------------------------------ the configuration keys
@@ -156,6 +189,10 @@ class PreparePlan:
     source_size: Optional[tuple] = None
     restore: bool = False               # ``source_restore``: the result goes back to the source clip's own size (``restored``)
     restore_resample: str = "lanczos"
+    restore_detail: bool = False        # ``source_restore_detail``: the way back carries the source's fine detail (``restore_frames_detail``)
+    detail_lo: int = 8
+    detail_hi: int = 32
+    detail_radius: int = 2
 
     def frames(self, pipe, frames, image_size):
         """PIL frames of any one size -> (uint8 [F, h, w, 3] on the pipeline's device, the same as PIL images)."""
@@ -167,31 +204,43 @@ class PreparePlan:
         w, h = image_size
         return pipe.prepare_mask(mask, h, w, fit=self.fit, x_offset=self.x_offset, y_offset=self.y_offset).cpu()
 
-    def restored(self, pipe, edited_u8, source_frames, alpha=None, prepared_from=None):
+    def restored(self, pipe, edited_u8, source_frames, alpha=None, prepared_from=None, prepared=None):
         """The frames that would be written (uint8 [F, h, w, 3] or PIL images at the working size) back over the source clip at its own
         size -> PIL images of the source's size (``pipe.restore_frames`` with this plan's geometry).  ``prepared_from``: the ``(w, h)``
-        the clip was prepared from; source frames of another size are refused (the geometry would point elsewhere)."""
+        the clip was prepared from; source frames of another size are refused (the geometry would point elsewhere).  ``prepared``: the
+        frames the inversion saw, looked at only with ``source_restore_detail`` (``pipe.restore_frames_detail``; None: prepared again)."""
         if prepared_from is not None:
             sizes = {tuple(f.size) for f in source_frames} if not isinstance(source_frames, torch.Tensor) else \
                 {(int(source_frames.shape[2]), int(source_frames.shape[1]))}
             if sizes != {tuple(prepared_from)}:
                 raise ValueError(f"source_restore: source frames of {sorted(sizes)} against a clip prepared from {tuple(prepared_from)}")
-        out = pipe.restore_frames(edited_u8, source_frames, fit=self.fit, x_offset=self.x_offset, y_offset=self.y_offset,
-                                  resample=self.restore_resample, alpha=alpha)
+        if self.restore_detail:
+            out = pipe.restore_frames_detail(edited_u8, source_frames, prepared, fit=self.fit, x_offset=self.x_offset, y_offset=self.y_offset,
+                                             resample=self.restore_resample, alpha=alpha, source_resample=self.resample,
+                                             gate_lo=self.detail_lo, gate_hi=self.detail_hi, gate_radius=self.detail_radius)
+        else:
+            out = pipe.restore_frames(edited_u8, source_frames, fit=self.fit, x_offset=self.x_offset, y_offset=self.y_offset,
+                                      resample=self.restore_resample, alpha=alpha)
         return [Image.fromarray(f) for f in out.cpu().numpy()]
 
     def tag(self):
         """What ``source_restore`` adds to the name of an output directory ("" when it is off)."""
         if not self.restore:
             return ""
-        return "_restored" + ("" if self.restore_resample == "lanczos" else f"-{self.restore_resample}")
+        tag = "_restored" + ("" if self.restore_resample == "lanczos" else f"-{self.restore_resample}")
+        if self.restore_detail:
+            params = (self.detail_lo, self.detail_hi, self.detail_radius)
+            tag += "_detail" + ("" if params == (8, 32, 2) else "-%d-%d-%d" % params)
+        return tag
 
 
 def plan_from_config(config, restore_config=None) -> Optional[PreparePlan]:
     """The ``PreparePlan`` of a configuration (template YAML merged with a JSON entry, ``api``'s ``inverse_config``, or any plain
     namespace), or None when it has no ``source_fit``: then nothing is prepared and every name, file and error is what it was before the
     keys existed.  A tuning key without ``source_fit`` has nothing to act on and is refused, not dropped.  ``source_restore`` (a bool)
-    and ``source_restore_resample`` are read from ``restore_config`` where one is given (``api``'s ``pnp_config``), else from ``config``."""
+    and ``source_restore_resample`` are read from ``restore_config`` where one is given (``api``'s ``pnp_config``), else from ``config``;
+    so are ``source_restore_detail`` (a bool, valid only beside ``source_restore``) and its tuning keys ``source_restore_detail_lo`` /
+    ``_hi`` / ``_radius`` (integers, 0 <= lo < hi <= 255, 0 <= radius <= 16; refused without the switch)."""
     opt = lambda key, c=config: c.get(key, None) if hasattr(c, "get") else getattr(c, key, None)
     ropt = lambda key: opt(key, config if restore_config is None else restore_config)
     fit = opt("source_fit")
@@ -203,6 +252,24 @@ def plan_from_config(config, restore_config=None) -> Optional[PreparePlan]:
         raise ValueError("source_restore_resample without source_restore: there is no way back to tune")
     if restore_resample is not None and restore_resample not in _lib.RESAMPLE_FILTERS:
         raise ValueError(f"source_restore_resample={restore_resample!r}: one of {sorted(_lib.RESAMPLE_FILTERS)}")
+    detail = ropt("source_restore_detail")
+    if detail is not None and not isinstance(detail, bool):
+        raise ValueError(f"source_restore_detail={detail!r}: true or false")
+    if detail and not restore:
+        raise ValueError("source_restore_detail without source_restore: there is no way back to carry the detail on")
+    params = {}
+    for k, default in (("lo", 8), ("hi", 32), ("radius", 2)):
+        v = ropt(f"source_restore_detail_{k}")
+        if v is not None and not detail:
+            raise ValueError(f"source_restore_detail_{k} without source_restore_detail: there is no gate to tune")
+        if v is not None and (isinstance(v, bool) or not isinstance(v, int)):
+            raise ValueError(f"source_restore_detail_{k}={v!r}: an integer")
+        params[k] = default if v is None else v
+    if detail:
+        if not 0 <= params["lo"] < params["hi"] <= 255:
+            raise ValueError(f"source_restore_detail_lo={params['lo']}, source_restore_detail_hi={params['hi']}: 0 <= lo < hi <= 255")
+        if not 0 <= params["radius"] <= _lib.DETAIL_MAX_RADIUS:
+            raise ValueError(f"source_restore_detail_radius={params['radius']}: 0 <= radius <= {_lib.DETAIL_MAX_RADIUS}")
     if fit is None:
         for k in tuning:
             if opt(k) is not None:
@@ -224,7 +291,8 @@ def plan_from_config(config, restore_config=None) -> Optional[PreparePlan]:
         size = _size("source_size", size)
         if size[0] % 8 or size[1] % 8:
             raise ValueError(f"source_size={list(size)}: width and height must be multiples of 8")
-    return PreparePlan(fit, x, y, resample, size, bool(restore), "lanczos" if restore_resample is None else restore_resample)
+    return PreparePlan(fit, x, y, resample, size, bool(restore), "lanczos" if restore_resample is None else restore_resample, bool(detail),
+                       params["lo"], params["hi"], params["radius"])
 
 
 def load_source_frames(frames_path, n_frames):

@@ -235,7 +235,8 @@ class Stage2:
             comp = None if plan is None else plan.composite
             alpha = None if comp is None else pipe.composite_alpha(mask, grow=plan.grow, feather=plan.feather, grow_px=comp["grow_px"],
                                                                    feather_px=comp["feather_px"])
-            edited_video = source_plan.restored(pipe, edited_video, source, alpha, prepared_from=source_size)
+            # (``source_restore_detail``: the frames the inversion saw say where the edit left the content alone)
+            edited_video = source_plan.restored(pipe, edited_video, source, alpha, prepared_from=source_size, prepared=frame_list)
         else:
             edited_video = [frame.resize(tuple(config.image_size), resample=Image.LANCZOS) for frame in edited_video]
         name = "video"

@@ -603,6 +603,46 @@ int anyv2v_restore_paste_u8(const void* source, const void* edit_h, const void* 
                             const int32_t* e_coeffs, int32_t e_ksize, int32_t mask_frames, int32_t a_rows, const int32_t* a_bounds,
                             const int32_t* a_coeffs, int32_t a_ksize, void* stream);
 
+/* Detail-preserving restore (restore_detail.hip): the way back above, with the fine detail of the source carried into the upscaled edit.
+ * With S the source frame and P the prepared source -- the frame the model saw, at the working size like the edit E --, S - up(P) is the
+ * detail that the trip down and up destroys; it is added to up(E) wherever a gate says that E stayed close to P.  All 8-bit integers.
+ *
+ * anyv2v_detail_gate_u8: edit, prepared uint8 [F, h, w, 3] -> gate_out uint8 [F, h, w]; lo, hi integers with 0 <= lo < hi <= 255, radius
+ * 0 .. ANYV2V_DETAIL_MAX_RADIUS.  Per pixel:
+ *   c[y, x] = max over the 3 bands of |E - P|
+ *   b[y, x] = sum of c over the (2 radius + 1)^2 window, coordinates clamped to the frame (replicate edge)
+ *   n = (2 radius + 1)^2;   mean = (b + n / 2) / n                                      (integer division)
+ *   G = 255 where mean <= lo;   G = 0 where mean >= hi;   otherwise G = (255 * (hi - mean) + (hi - lo) / 2) / (hi - lo)
+ * The box is separable: two launches, row sums into scratch (uint16 [F, h, w]: 255 * 33 < 65536; at least 2 F h w bytes, 2-byte aligned),
+ * then column sums and the ramp.  Work is O(radius) per pixel.  No other operand needs an alignment; gate_out and scratch may overlap
+ * nothing.  No read leaves a buffer.
+ *
+ * anyv2v_restore_detail_u8: anyv2v_restore_paste_u8's sibling.  The caller runs anyv2v_resample_h_u8 on E and P (3 bands, the edit's
+ * filter) and on G and A (1 band, BILINEAR):
+ *   prep_h   uint8 [F, e_rows, dw, 3], the horizontal intermediate of P: the same filter, the same box and the same row range as edit_h
+ *   gate_h   uint8 [gate_frames, a_rows, dw], the horizontal intermediate of G, gate_frames = 1 (every frame) or F; never NULL, so the
+ *            a_* tables (alpha's: BILINEAR) are always read
+ *   alpha_h  uint8 [mask_frames, a_rows, dw] or NULL (m = 255), as above
+ * A byte outside dest is the source's.  A byte inside, per band, with d the source's byte:
+ *   e = the vertical pass over edit_h (as above);   p = the same table over prep_h
+ *   g = the vertical pass of the a_* table over gate_h at the byte's pixel;   m = the same over alpha_h, or 255
+ *   wt = g + (g >> 7)                                                                   0 .. 256, 255 maps to 256
+ *   add = ((d - p) * wt + 128) >> 8                                                     arithmetic shift of a signed int32
+ *   e2 = clamp(e + add, 0, 255)
+ *   t = d * (255 - m) + e2 * m + 128;   out = ((t >> 8) + t) >> 8                       Pillow's paste, as above
+ * g = 0 gives exactly anyv2v_restore_paste_u8 (and so Pillow); g = 255 with e = p gives d; m = 0 gives d.  Hence an edit that changes
+ * nothing (E = P, whose gate is 255 everywhere, and a constant 255 resamples to 255) restores the source byte for byte.  Refused, like
+ * above: null pointers, sizes out of range, an empty dest or one outside the frame, gate_frames / mask_frames other than 1 or F, tables that
+ * are not 4-byte aligned, an out that overlaps any input.  A table entry that points outside its intermediate is cut to it.  No atomics, a
+ * fixed grid: every output byte is written once, by one thread. */
+#define ANYV2V_DETAIL_MAX_RADIUS 16
+int anyv2v_detail_gate_u8(const void* edit, const void* prepared, void* gate_out, int32_t F, int32_t h, int32_t w, int32_t lo, int32_t hi,
+                          int32_t radius, void* scratch, int64_t scratch_bytes, void* stream);
+int anyv2v_restore_detail_u8(const void* source, const void* edit_h, const void* prep_h, const void* gate_h, const void* alpha_h, void* out,
+                             int32_t F, int32_t sh, int32_t sw, int32_t dx0, int32_t dy0, int32_t dx1, int32_t dy1, int32_t e_rows,
+                             const int32_t* e_bounds, const int32_t* e_coeffs, int32_t e_ksize, int32_t gate_frames, int32_t mask_frames,
+                             int32_t a_rows, const int32_t* a_bounds, const int32_t* a_coeffs, int32_t a_ksize, void* stream);
+
 /* Plain elementwise DDIM / inverse-DDIM step (eta = 0, v-prediction) on same-layout tensors:
  * the generic `scheduler.step(model_output, t, sample).prev_sample` (pipeline_i2vgen_xl.py:868,1173,1418). */
 int anyv2v_ddim_step_f16(const void* V, const void* X, void* Y, float sa_t, float sb_t, float sa_p, float sb_p,
@@ -647,7 +687,7 @@ const char* anyv2v_last_error(void);
  * must still be recompiled against this header because the structure grew).  anyv2v_freeu_f16, anyv2v_tile_blend_f16, anyv2v_latent_mask_f16,
  * anyv2v_masked_blend_f16, anyv2v_diff_map_accum_f16, anyv2v_diff_map_finish_f16, anyv2v_pixel_alpha_f16, anyv2v_composite_stats_u8,
  * anyv2v_composite_u8, anyv2v_luma_u8, anyv2v_block_match_u8, anyv2v_flow_median_i16, anyv2v_mask_propagate_u8,
- * anyv2v_first_frame_mask_u8, anyv2v_resample_table, anyv2v_resample_h_u8, anyv2v_resample_v_u8 and anyv2v_restore_paste_u8 were added under 105: new entry
+ * anyv2v_first_frame_mask_u8, anyv2v_resample_table, anyv2v_resample_h_u8, anyv2v_resample_v_u8 and anyv2v_restore_paste_u8 were added under 105, and anyv2v_detail_gate_u8 and anyv2v_restore_detail_u8 after them: new entry
  * points, no structure changed
  * (a binding that needs them finds out when it resolves the symbol). */
 #define ANYV2V_ABI_VERSION 105
